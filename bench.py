@@ -2,12 +2,12 @@
 """bench.py -- BASELINE.json's metric on MI355X: BN128 Groth16 prove ms @ 2^20 constraints (configs[3]), with the G1 MSM
 (configs[1]) and the NTT (configs[2]) figures of the same metric string carried in the same line.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 
 A "step" is one whole proof (CALC_H + 5 MSMs + assembly) of the SURVEY.md section 8d C4 circuit -- synthetic R1CS, domain
 2^20, 1-3 non-zeros per COLUMN of A and B (every variable present), valid witness, key from known toxic waste -- with
-the key and the witness already resident in HBM.  Every timed proof is checked (first and last) against the toxic-waste
-closed form.  For N > 1 the driver launches one rank per GPU (torch.distributed.run, backend nccl = RCCL): the same proof
+the key and the witness already resident in HBM.  With --full the first and the last timed proof are checked against the
+toxic-waste closed form.  For N > 1 the driver launches one rank per GPU (torch.distributed.run, backend nccl = RCCL): the same proof
 strong-scaled -- every rank holds a POINTS shard of the key (1/N of every section, wsnark_pkey_load_shard), CALC_H runs on the
 distributed four-step transform (three all-to-alls), ONE all_gather of the 592-byte records of partial sums per proof, host-side
 EC sum + assembly on every rank (RCCL has no elliptic-curve reduction); a mode that fails or disagrees with the closed form on
@@ -15,7 +15,8 @@ any rank falls through to the next (native -> Python orchestration -> replicated
 one-call prover, no collective.
 
 Rank 0 prints ONE JSON line.  `value` = ms per proof (max over ranks), witness resident in HBM (the contract keeps PCIe out of
-`value`; the drop-in call from a HOST witness sits beside it).  Objects beside the contract's fields:
+`value`; the drop-in call from a HOST witness sits beside it).  A plain run sets up, warms up, times the steps and prints the
+contract's fields (plus `config`); --dump-outputs DIR writes the last timed step's result as .npy files.  --full adds, beside them:
   roofline          dominant kernel msm_accumulate_g1: algorithmic bytes (96 B/pair) per launch / mean launch duration from HIP events
                     on the launching queue over the timed region (IN SITU: two-queue schedule), plus the same kernel ALONE (a few
                     more proofs on one queue, same run) and what the committed rocprofv3 summaries of this command say (in situ under
@@ -50,6 +51,34 @@ EXTRA_REPS = int(os.environ.get("WSNARK_BENCH_EXTRA_REPS", "20"))   # repetition
 
 def kernel_ms(report, per=1):
     return {k: round(v[0] / max(per, 1), 4) for k, v in sorted(report.items())}
+
+
+def limbs32(v):
+    """A 256-bit value (int or decimal string) -> its eight 32-bit limbs, least significant first: exact in float64."""
+    v = int(v)
+    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+
+
+def proof_arrays(p):
+    """The proof object a caller of groth16GenProof receives ({pi_a, pi_b, pi_c} of decimal strings) as limb arrays:
+    pi_a, pi_c (3, 8), pi_b (3, 2, 8)."""
+    return {"pi_a": [limbs32(v) for v in p["pi_a"]], "pi_b": [[limbs32(v) for v in c] for c in p["pi_b"]],
+            "pi_c": [limbs32(v) for v in p["pi_c"]]}
+
+
+def point_arrays(name, jac):
+    """An MSM result (Jacobian-Montgomery bytes, 32 B per coordinate) as (coordinates, 8) limbs."""
+    return {name: [limbs32(int.from_bytes(jac[i:i + 32], "little")) for i in range(0, len(jac), 32)]}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array of what the last timed step returned."""
+    if not out_dir:
+        return
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def build_prover(bn, logd, style, seed=1, keep_h=False, container="auto", load=True, cold_probe=False, sections=True):
@@ -131,11 +160,17 @@ def main():
                                                      "of every rank generating and holding the whole key in host memory.  'auto' = a file under $WSNARK_BENCH_KEY_DIR "
                                                      "or the temp directory; or a path on a file system all ranks see")
     ap.add_argument("--log-n", type=int, default=20, help="--workload msm / extras: pairs per MSM")
-    ap.add_argument("--extras", default="msm,ntt,cold,inflight,power,sparse,node", help="comma list (N=1 only): msm, ntt, cold, inflight, power, sparse, node")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: closed-form checks, rooflines, per-kernel times, the one-queue pass, the drop-in call, "
+                         "the extras and the CPU baseline.  Without it a run sets up, warms up, times the steps and prints the contract's fields")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float64; every 256-bit value as "
+                         "eight little-endian 32-bit limbs, exact in float64)")
+    ap.add_argument("--extras", default="msm,ntt,cold,inflight,power,sparse,node", help="--full, N=1 only: comma list: msm, ntt, cold, inflight, power, sparse, node")
+    ap.add_argument("--no-extras", action="store_true", help="--full: no extras")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--no-alone-pass", action="store_true",
-                    help="skip the one-queue proofs that time the dominant kernel alone (the in-situ rocprofv3 pass of tools/gpu_session.sh: "
+                    help="--full: skip the one-queue proofs that time the dominant kernel alone (the in-situ rocprofv3 pass of tools/gpu_session.sh: "
                          "its kernel summary must hold two-queue launches only)")
     ap.add_argument("--shard", choices=["points", "windows"], default="points", help="--workload msm, N>1")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -413,13 +448,13 @@ def bench_prove(ctx):
     from wasmsnark_amd import dist as wdist, synth
     logd = args.prove_log_domain
     use_file = bool(args.key_file) and world > 1
-    circ, key, wit, info = build_prover(bn, logd, args.circuit, container=args.key_container, load=(world == 1), cold_probe=(world == 1),
-                                        sections=not (use_file and rank != 0))
+    circ, key, wit, info = build_prover(bn, logd, args.circuit, container=args.key_container, load=(world == 1),
+                                        cold_probe=(world == 1 and args.full), sections=not (use_file and rank != 0))
     info.pop("h_points", None)
     cold = info.pop("_cold")
     sec = info.pop("_sections", None)
     r32, s32 = bytes(range(32)), bytes(range(32, 64))
-    want = circ.expected_proof(r32, s32)
+    want = circ.expected_proof(r32, s32) if (args.full or world > 1) else None      # (N > 1: the orchestration is chosen by it)
     runs = cold.pop("_runs", None)
     if world == 1 and runs:
         cold["first_proof_ms"] = runs["ms"][0]
@@ -505,6 +540,26 @@ def bench_prove(ctx):
     key = holder["key"]
     first = step()
     dt, kt, last = timed(ctx, step, args.steps, args.warmup)
+    if rank == 0:
+        dump_outputs(args.dump_outputs, proof_arrays(last))
+    ms = dt / args.steps * 1e3
+    out = {"metric": "BN128 Groth16 prove ms @ 2^%d constraints" % logd, "value": round(ms, 3), "unit": "ms", "n_gpus": world,
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": False,
+           "scaling": "strong", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+           "config": {"workload": "BN128 full Groth16 prove, synthetic 2^%d-constraint R1CS (1-3 non-zeros per column of A and B, "
+                                  "every variable present), key and witness resident in HBM, r and s injected" % logd
+                                  if args.circuit == "columns" else
+                                  "BN128 full Groth16 prove, synthetic 2^%d-constraint R1CS, round-1 sparse generator (1-2 terms per row)" % logd,
+                      "circuit": info, "parallelism": ((("key POINTS-sharded: 1/%d of every section resident per rank (wsnark_pkey_load_shard), one C call per proof "
+                                                         "(wsnark_groth16_prove_dist), " % world) if calc_h_mode == "native" else ("MSM windows sharded w %% %d == rank, " % world))
+                                                       + ("CALC_H on the distributed four-step NTT (3 all-to-alls per proof: 3 + 2 + 1 vectors of %d B per rank and peer), H sum points-sharded, "
+                                                          % ((circ.domain // world // world) * 32) if calc_h_mode in ("dist", "native") else "CALC_H %s, " % calc_h_mode)
+                                                       + "1 all_gather of 576 B records per proof"
+                                                       + ("; fell through: " + "; ".join(fell) if fell else ""))
+                      + ("" if args.backend == "nccl" else " [transport gloo with host staging: ranks may share a GPU -- functional check, not a scaling figure]")
+                      if world > 1 else "1 GPU, no collective", "lanes": int(os.environ.get("WSNARK_LANES", "2")), "device": bn.device_info}}
+    if not args.full:
+        return out if rank == 0 else None
     ok = bool(first == want and last == want)
     # per-kernel breakdown: two more (untimed) proofs with every kernel bracketed
     bn.lib.c.wsnark_timing_reset()
@@ -559,7 +614,6 @@ def bench_prove(ctx):
         host_ok = bool(hp == want)
     if rank != 0:
         return None
-    ms = dt / args.steps * 1e3
     nv, dom = circ.n_vars, circ.domain
     peak = measure_peaks(bn)                  # (rank 0, any world size: ~30 ms after the timed region)
     # passes over the points per sum: the rows of the key's fixed-base tables (13 at 2^20), or the windows of the plain method
@@ -583,21 +637,7 @@ def bench_prove(ctx):
     g2 = kt.get("msm_accumulate_g2")
     # algorithmic bytes of one proof
     alg_bytes = 32 * nv + 8 * nv + 36 * info["nnz_A_plus_B"] + 64 * nv * 2 + 128 * nv + 64 * (nv - circ.n_public - 1) + 64 * dom + 64 * 6 * dom
-    out = {"metric": "BN128 Groth16 prove ms @ 2^%d constraints" % logd, "value": round(ms, 3), "unit": "ms", "n_gpus": world,
-           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": False,
-           "scaling": "strong", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-           "config": {"workload": "BN128 full Groth16 prove, synthetic 2^%d-constraint R1CS (1-3 non-zeros per column of A and B, "
-                                  "every variable present), key and witness resident in HBM, r and s injected" % logd
-                                  if args.circuit == "columns" else
-                                  "BN128 full Groth16 prove, synthetic 2^%d-constraint R1CS, round-1 sparse generator (1-2 terms per row)" % logd,
-                      "circuit": info, "parallelism": ((("key POINTS-sharded: 1/%d of every section resident per rank (wsnark_pkey_load_shard), one C call per proof "
-                                                         "(wsnark_groth16_prove_dist), " % world) if calc_h_mode == "native" else ("MSM windows sharded w %% %d == rank, " % world))
-                                                       + ("CALC_H on the distributed four-step NTT (3 all-to-alls per proof: 3 + 2 + 1 vectors of %d B per rank and peer), H sum points-sharded, "
-                                                          % ((circ.domain // world // world) * 32) if calc_h_mode in ("dist", "native") else "CALC_H %s, " % calc_h_mode)
-                                                       + "1 all_gather of 576 B records per proof"
-                                                       + ("; fell through: " + "; ".join(fell) if fell else ""))
-                      + ("" if args.backend == "nccl" else " [transport gloo with host staging: ranks may share a GPU -- functional check, not a scaling figure]")
-                      if world > 1 else "1 GPU, no collective", "lanes": int(os.environ.get("WSNARK_LANES", "2")), "device": bn.device_info},
+    out.update({
            "proofs_match_toxic_waste_closed_form": ok,
            "proofs_per_s": round(1e3 / ms, 2),
            "drop_in_call": None if host_ms is None else {
@@ -623,7 +663,7 @@ def bench_prove(ctx):
            "kernel_event_spans_two_queues_ms_per_proof": dict(kernel_ms(kt_all, 2), _what="event-bracket SPANS on the launching queue under the shipped two-queue "
                                                               "schedule: a span contains whatever the other queue's kernels took from the chip meanwhile -- NOT kernel times, "
                                                               "they add up to more than a proof"),
-           "reference_wasm_8_workers_prove_2p20_s": {"value": REF_WASM_PROVE_2P20_S, "where": "BASELINE.md: survey container (8 vCPU), NOT this box: the reference may not travel"}}
+           "reference_wasm_8_workers_prove_2p20_s": {"value": REF_WASM_PROVE_2P20_S, "where": "BASELINE.md: survey container (8 vCPU), NOT this box: the reference may not travel"}})
     want_extras = set() if (args.no_extras or world > 1) else set(x for x in args.extras.split(",") if x)
     extras = {}
     if "inflight" in want_extras:
@@ -740,7 +780,6 @@ def bench_group(ctx):
     sec, _ = circ.build_sections()
     wit = circ.witness_bin()
     r32, s32 = bytes(range(32)), bytes(range(32, 64))
-    want = circ.expected_proof(r32, s32)
     g = bn128.Group(lib=bn.lib, devices=devs)
     t0 = time.perf_counter()
     key = g.load_key(sections=sec)
@@ -754,14 +793,7 @@ def bench_group(ctx):
         last = step()
     dt = time.perf_counter() - t0
     ms = dt / args.steps * 1e3
-    # the one-GPU call on the same inputs, same process, for the ratio
-    one = bn.load_key(sections=sec)
-    for _ in range(3):
-        p1 = bn.groth16GenProof(wit, one, r=r32, s=s32)
-    t0 = time.perf_counter()
-    for _ in range(max(4, args.steps // 2)):
-        p1 = bn.groth16GenProof(wit, one, r=r32, s=s32)
-    ms1 = (time.perf_counter() - t0) / max(4, args.steps // 2) * 1e3
+    dump_outputs(args.dump_outputs, proof_arrays(last))
     out = {"metric": "BN128 Groth16 prove ms @ 2^%d constraints" % logd, "value": round(ms, 3), "unit": "ms", "n_gpus": len(devs),
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": False, "scaling": "strong",
            "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
@@ -770,11 +802,23 @@ def bench_group(ctx):
                       "parallelism": "ONE process, %d devices %s: wsnark_group_prove (a context + host thread per device, %s, 1 gather of 576 B records in host memory)"
                                      % (len(devs), devs, "CALC_H on the distributed four-step NTT: 3 device-to-device exchanges (hipMemcpyPeerAsync) per proof"
                                         if key.distributed_calc_h else "CALC_H complete on every device"),
-                      "device": bn.device_info},
-           "proofs_match_toxic_waste_closed_form": bool(first == want and last == want),
-           "proofs_per_s": round(1e3 / ms, 2), "group_key_load_s": round(t_load, 2),
-           "one_gpu_same_call_ms": round(ms1, 3), "one_gpu_proof_matches": bool(p1 == want), "speedup_over_one_gpu_same_call": round(ms1 / ms, 3),
-           "note": ("several contexts share device(s) %s: a functional check, not a scaling figure" % sorted(set(devs))) if len(set(devs)) < len(devs) else None}
+                      "device": bn.device_info}}
+    if not args.full:
+        key.free(); g.terminate()
+        return out
+    want = circ.expected_proof(r32, s32)
+    # the one-GPU call on the same inputs, same process, for the ratio
+    one = bn.load_key(sections=sec)
+    for _ in range(3):
+        p1 = bn.groth16GenProof(wit, one, r=r32, s=s32)
+    t0 = time.perf_counter()
+    for _ in range(max(4, args.steps // 2)):
+        p1 = bn.groth16GenProof(wit, one, r=r32, s=s32)
+    ms1 = (time.perf_counter() - t0) / max(4, args.steps // 2) * 1e3
+    out.update({"proofs_match_toxic_waste_closed_form": bool(first == want and last == want),
+                "proofs_per_s": round(1e3 / ms, 2), "group_key_load_s": round(t_load, 2),
+                "one_gpu_same_call_ms": round(ms1, 3), "one_gpu_proof_matches": bool(p1 == want), "speedup_over_one_gpu_same_call": round(ms1 / ms, 3),
+                "note": ("several contexts share device(s) %s: a functional check, not a scaling figure" % sorted(set(devs))) if len(set(devs)) < len(devs) else None})
     key.free(); one.free(); g.terminate()
     return out
 
@@ -1152,20 +1196,22 @@ def bench_msm(ctx):
         part = bn.g1_multiexp_dev(d_s.data_ptr(), d_p.data_ptr(), n, shard=shard)
         return wdist.sharded_msm(bn, 1, part, dev) if world > 1 else part
 
-    dt, kt, _ = timed(ctx, step, args.steps, args.warmup)
+    dt, kt, last = timed(ctx, step, args.steps, args.warmup)
     if rank != 0:
         return None
+    dump_outputs(args.dump_outputs, point_arrays("msm_g1", bn.g1_sum(last)))      # (g1_sum of one point: its affine-normalised form)
     ms = dt / args.steps * 1e3
-    W_all = 16 if args.log_n >= 20 else (255 + args.log_n - 5) // max(args.log_n - 4, 4)
-    hbm, alu = rooflines(kt, "msm_accumulate_g1", n, len(range(rank, W_all, world)) if windows else W_all, 96, 10)
     out = {"metric": "BN128 G1 MSM Mpoints/s (2^%d pairs/GPU)" % args.log_n,
            "value": round((1 if windows else world) * n / (dt / args.steps) / 1e6, 3), "unit": "Mpoints/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
            "scaling": "strong" if windows else "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
            "config": {"workload": "BN128 G1 Pippenger MSM, 2^%d random (scalar,point) pairs per GPU, inputs resident in HBM" % args.log_n,
                       "pairs_per_gpu": n, "parallelism": ("windows-sharded x%d" if windows else "points-sharded x%d") % world + ", 1 all_gather of 96 B partials",
-                      "device": bn.device_info},
-           "roofline": hbm, "roofline_int_alu": alu}
+                      "device": bn.device_info}}
+    if not args.full:
+        return out
+    W_all = 16 if args.log_n >= 20 else (255 + args.log_n - 5) // max(args.log_n - 4, 4)
+    out["roofline"], out["roofline_int_alu"] = rooflines(kt, "msm_accumulate_g1", n, len(range(rank, W_all, world)) if windows else W_all, 96, 10)
     if not args.no_cpu_baseline and world == 1:
         try:
             from oracle import pyoracle as orc

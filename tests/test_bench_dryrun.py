@@ -22,7 +22,7 @@ def _line(out):
 def test_bench_single_gpu_line():
     from emul_util import emul_bn128
     emul_bn128()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dryrun.py"), "--prove-log-domain", "6", "--log-n", "8",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dryrun.py"), "--full", "--prove-log-domain", "6", "--log-n", "8",
                           "--steps", "2", "--warmup", "1", "--extras", "msm,inflight"],
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, WSNARK_BENCH_EXTRA_REPS="2"))
     d = _line(out)
@@ -52,7 +52,7 @@ def test_bench_two_ranks_line():
     from emul_util import emul_bn128
     emul_bn128()
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29657", os.path.join(ROOT, "tools", "bench_dryrun.py"), "--gpus", "2", "--prove-log-domain", "6",
+                          "--master-port", "29657", os.path.join(ROOT, "tools", "bench_dryrun.py"), "--full", "--gpus", "2", "--prove-log-domain", "6",
                           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1", WSNARK_EMUL_DEVICES="2"))
     d = _line(out)
@@ -70,7 +70,7 @@ def test_bench_two_ranks_from_a_key_file(tmp_path):
     from emul_util import emul_bn128
     emul_bn128()
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29661", os.path.join(ROOT, "tools", "bench_dryrun.py"), "--gpus", "2", "--prove-log-domain", "6",
+                          "--master-port", "29661", os.path.join(ROOT, "tools", "bench_dryrun.py"), "--full", "--gpus", "2", "--prove-log-domain", "6",
                           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--key-file", "auto"],
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1", WSNARK_EMUL_DEVICES="2", WSNARK_BENCH_KEY_DIR=str(tmp_path)))
     d = _line(out)
@@ -88,7 +88,7 @@ def test_bench_two_ranks_falls_through_when_an_orchestration_fails():
     emul_bn128()
     for fail, ran in (("native", "CALC_H on the distributed four-step NTT"), ("native,dist", "CALC_H replicated")):
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                              "--master-port", "29659", os.path.join(ROOT, "tools", "bench_dryrun.py"), "--gpus", "2", "--prove-log-domain", "6",
+                              "--master-port", "29659", os.path.join(ROOT, "tools", "bench_dryrun.py"), "--full", "--gpus", "2", "--prove-log-domain", "6",
                               "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
                              capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1", WSNARK_BENCH_FAIL=fail))
         d = _line(out)
@@ -103,7 +103,7 @@ def test_bench_single_process_group_line():
     from emul_util import emul_bn128
     emul_bn128()
     for devs, ndev in (("0,0", "1"), ("0,1", "2")):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dryrun.py"), "--gpus", "2", "--single-process", "--group-devices", devs,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dryrun.py"), "--full", "--gpus", "2", "--single-process", "--group-devices", devs,
                               "--prove-log-domain", "6", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900,
                              env=dict(os.environ, WSNARK_EMUL_DEVICES=ndev))
         d = _line(out)
@@ -114,3 +114,95 @@ def check_group_line(d, shared):
     assert d["n_gpus"] == 2 and d["proofs_match_toxic_waste_closed_form"] is True and d["one_gpu_proof_matches"] is True
     assert "wsnark_group_prove" in d["config"]["parallelism"] and "four-step" in d["config"]["parallelism"]
     assert ("functional check" in d["note"]) if shared else d["note"] is None      # (two contexts on ONE device is not a scaling figure)
+
+
+PLAIN = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+         "dtype", "data", "config")
+R32, S32 = bytes(range(32)), bytes(range(32, 64))        # bench.py's injected blinding
+
+
+def _dump(out_dir, names):
+    import numpy as np
+    assert sorted(os.listdir(out_dir)) == sorted(n + ".npy" for n in names)
+    arrays = {n: np.load(os.path.join(out_dir, n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    return arrays
+
+
+def _int(limbs):
+    return sum(int(x) << (32 * i) for i, x in enumerate(limbs))
+
+
+def _proof(arrays):
+    assert arrays["pi_a"].shape == (3, 8) and arrays["pi_b"].shape == (3, 2, 8) and arrays["pi_c"].shape == (3, 8)
+    return {"pi_a": [str(_int(v)) for v in arrays["pi_a"]], "pi_b": [[str(_int(v)) for v in c] for c in arrays["pi_b"]],
+            "pi_c": [str(_int(v)) for v in arrays["pi_c"]]}
+
+
+def test_bench_plain_line_and_dumped_proof(tmp_path):
+    """Without --full the line holds the contract's fields and the configuration, nothing measured or checked beside them;
+    --dump-outputs writes the proof of the last timed step: the same on every run, and the toxic-waste closed form."""
+    from emul_util import emul_bn128
+    from wasmsnark_amd import synth
+    bn = emul_bn128()
+    proofs = []
+    for run in range(2):
+        d_out = tmp_path / ("run%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dryrun.py"), "--prove-log-domain", "6", "--steps", "3",
+                              "--warmup", "1", "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=900)
+        d = _line(out)
+        assert set(d) == set(PLAIN) and d["n_gpus"] == 1 and d["unit"] == "ms" and d["higher_is_better"] is False
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] == d["value"] > 0
+        proofs.append(_proof(_dump(d_out, ("pi_a", "pi_b", "pi_c"))))
+    circ = synth.NativeCircuit(bn.lib, 6, n_public=5, seed=1, style="columns")
+    assert proofs[0] == proofs[1] == circ.expected_proof(R32, S32)
+
+
+def test_bench_plain_msm_line_and_dumped_sum(tmp_path):
+    import numpy as np
+    from emul_util import emul_bn128
+    bn = emul_bn128()
+    d_out = tmp_path / "msm"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dryrun.py"), "--workload", "msm", "--log-n", "8", "--steps", "2",
+                          "--warmup", "1", "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=900)
+    d = _line(out)
+    assert set(d) == set(PLAIN) and d["unit"] == "Mpoints/s" and d["higher_is_better"] is True and d["steps"] == 2
+    got = _dump(d_out, ("msm_g1",))["msm_g1"]
+    # bench.py's seeded inputs (msm_inputs, seed 1234), summed here through the host-pointer call and normalised the same way
+    rng = np.random.default_rng(1234)
+    sc = rng.integers(0, 256, size=(256, 32), dtype=np.uint8)
+    sc[:, 31] &= 0x1F
+    ks = rng.integers(0, 256, size=(256, 32), dtype=np.uint8)
+    ks[:, 31] &= 0x1F
+    want = bn.g1_sum(bn.g1_multiexp(sc.tobytes(), bn.mul_base(1, ks.tobytes())))
+    assert got.shape == (3, 8) and [_int(v) for v in got] == [int.from_bytes(want[i:i + 32], "little") for i in range(0, 96, 32)]
+
+
+def test_bench_plain_two_ranks_dump_the_same_proof(tmp_path):
+    from emul_util import emul_bn128
+    from wasmsnark_amd import synth
+    bn = emul_bn128()
+    d_out = tmp_path / "n2"
+    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+                          "--master-port", "29663", os.path.join(ROOT, "tools", "bench_dryrun.py"), "--gpus", "2", "--prove-log-domain", "6",
+                          "--steps", "2", "--warmup", "1", "--dump-outputs", str(d_out)],
+                         capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1", WSNARK_EMUL_DEVICES="2"))
+    d = _line(out)
+    assert set(d) == set(PLAIN) and d["n_gpus"] == 2 and "wsnark_groth16_prove_dist" in d["config"]["parallelism"]
+    circ = synth.NativeCircuit(bn.lib, 6, n_public=5, seed=1, style="columns")
+    assert _proof(_dump(d_out, ("pi_a", "pi_b", "pi_c"))) == circ.expected_proof(R32, S32)
+
+
+def test_bench_plain_single_process_group_dumps_the_same_proof(tmp_path):
+    """--single-process (bench_group, two contexts on the emulator's one device): the plain line and the dumped last proof."""
+    from emul_util import emul_bn128
+    from wasmsnark_amd import synth
+    bn = emul_bn128()
+    d_out = tmp_path / "group"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dryrun.py"), "--gpus", "2", "--single-process", "--group-devices", "0,0",
+                          "--prove-log-domain", "6", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d_out)],
+                         capture_output=True, text=True, timeout=900, env=dict(os.environ, WSNARK_EMUL_DEVICES="1"))
+    d = _line(out)
+    assert set(d) == set(PLAIN) and d["n_gpus"] == 2 and d["steps"] == 2 and "wsnark_group_prove" in d["config"]["parallelism"]
+    circ = synth.NativeCircuit(bn.lib, 6, n_public=5, seed=1, style="columns")
+    assert _proof(_dump(d_out, ("pi_a", "pi_b", "pi_c"))) == circ.expected_proof(R32, S32)

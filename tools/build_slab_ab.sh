@@ -1,6 +1,6 @@
 # Cold path with smaller slabs of the background table build (fewer workgroups of the build resident at a time): proofs beside it vs its duration
 for l in ${LANES:-65536 262144}; do
-  WSNARK_TABLE_SLAB_LANES=$l timeout 150 python bench.py --no-extras --no-cpu-baseline --no-alone-pass --steps 5 --warmup 2 2>/dev/null > /tmp/slab_$l.json
+  WSNARK_TABLE_SLAB_LANES=$l timeout 150 python bench.py --full --no-extras --no-cpu-baseline --no-alone-pass --steps 5 --warmup 2 2>/dev/null > /tmp/slab_$l.json
   python - "$l" <<'P'
 import json,sys
 l=sys.argv[1]

@@ -2,6 +2,7 @@
 # One gpurun call: environment probe, GPU parity tests, bench, rocprof kernel stats, PMC traffic.
 #   TAG=r02_s1 [SKIP="tests pmc"] [PYTEST_K="expr for -k"] tools/gpu_session.sh
 cd "$GRAFT_REPO_ROOT" || exit 1
+ROOT=$(pwd)
 TAG=${TAG:-r02}
 O=gpurun_out/$TAG
 mkdir -p "$O"
@@ -18,14 +19,14 @@ if ! skip tests; then
   echo "pytest rc=$?" >> "$O/env.log"
 fi
 if ! skip bench; then
-  timeout 1500 python bench.py $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err"
+  timeout 1500 python bench.py --full $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err"
   echo "bench rc=$?" >> "$O/env.log"
 fi
 # rocprofv3 --kernel-trace --stats of the bench command, PROOFS ONLY (no extras: every msm_accumulate launch then has the shape
 # bench.py's roofline is quoted on), twice: the shipped two-queue schedule (in situ), and WSNARK_PROVE_OVERLAP=0 (one queue: every
 # kernel alone -- where the profiler and the bench's HIP events must agree).  The bench line of each profiled run is kept beside
 # its summary (the events of THAT run are the ones to compare with its csv).
-PROF_CMD="python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+PROF_CMD="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 if ! skip prof; then
   ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$O/prof" -o prof -- $PROF_CMD --no-alone-pass ) > "$O/prof.log" 2>&1
   echo "rocprof rc=$?" >> "$O/env.log"
@@ -48,7 +49,7 @@ fi
 # HBM traffic counters: separate --pmc passes, kernel-trace only (never combined with sys/hip/hsa traces)
 if ! skip pmc; then
   for CTR in FETCH_SIZE WRITE_SIZE; do
-    ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --pmc $CTR --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/$O/pmc_$CTR" -o pmc -- python "$GRAFT_REPO_ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-extras ) > "$O/pmc_$CTR.log" 2>&1
+    ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --pmc $CTR --kernel-trace --output-format csv -d "$ROOT/$O/pmc_$CTR" -o pmc -- python "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras ) > "$O/pmc_$CTR.log" 2>&1
     echo "pmc $CTR rc=$?" >> "$O/env.log"
   done
   python tools/pmc_summary.py "$O" > "$O/pmc_traffic.json" 2>> "$O/env.log"
@@ -59,7 +60,7 @@ if ! skip sq; then
   I=0
   for GROUP in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VALU_INT64 SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" "SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU"; do
     I=$((I+1))
-    ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --pmc $GROUP --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/$O/sq/pmc_sq$I" -o pmc -- python "$GRAFT_REPO_ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --extras msm,ntt ) > "$O/pmc_sq$I.log" 2>&1
+    ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --pmc $GROUP --kernel-trace --output-format csv -d "$ROOT/$O/sq/pmc_sq$I" -o pmc -- python "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --extras msm,ntt ) > "$O/pmc_sq$I.log" 2>&1
     echo "pmc sq$I rc=$?" >> "$O/env.log"
   done
   python tools/pmc_counters.py "$O/sq" --rates "$O/issue_classes.json" > "$O/pmc_sq_counters.json" 2>> "$O/env.log"

@@ -30,8 +30,8 @@ PORT=29700
 run_bench() {   # run_bench <n> <extra args...>
   local n=$1; shift
   PORT=$((PORT + 1))
-  if [ "$n" -eq 1 ]; then timeout 1800 python bench.py --gpus 1 --steps 20 --warmup 5 "$@"
-  else timeout 1800 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$n" --steps 20 --warmup 5 "$@"
+  if [ "$n" -eq 1 ]; then timeout 1800 python bench.py --full --gpus 1 --steps 20 --warmup 5 "$@"
+  else timeout 1800 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus "$n" --steps 20 --warmup 5 "$@"
   fi
 }
 run_bench 1 > "$O/bench_n1.json" 2> "$O/bench_n1.err"; echo "bench n=1 rc=$?" | tee -a "$O/env.log"
@@ -46,7 +46,7 @@ timeout 1800 python -m pytest tests/test_gpu_group.py -m gpu -q --timeout 900 -p
 echo "pytest group rc=$?" | tee -a "$O/env.log"
 for n in 2 4 8; do
   [ "$n" -le "$NG" ] || continue
-  timeout 1800 python bench.py --gpus "$n" --single-process --steps 20 --warmup 5 > "$O/bench_group_n$n.json" 2> "$O/bench_group_n$n.err"; echo "bench group n=$n rc=$?" | tee -a "$O/env.log"
+  timeout 1800 python bench.py --full --gpus "$n" --single-process --steps 20 --warmup 5 > "$O/bench_group_n$n.json" 2> "$O/bench_group_n$n.err"; echo "bench group n=$n rc=$?" | tee -a "$O/env.log"
 done
 DEVS=$(python -c "print(','.join(str(i) for i in range($NG)))")
 NODE_BENCH_DEVICES=$DEVS timeout 900 python tools/node_bench.py 20 20 > "$O/node_bench_group.json" 2> "$O/node_bench_group.err"; echo "node group rc=$?" | tee -a "$O/env.log"

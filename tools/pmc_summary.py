@@ -59,7 +59,7 @@ try:
 except Exception:  # noqa: BLE001
     pass
 print(json.dumps({"how": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes (--kernel-trace only) around "
-                         "`python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras` (proofs only: every msm_accumulate launch has "
+                         "`python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras` (proofs only: every msm_accumulate launch has "
                          "the shape below); mean bytes per launch = counter (KiB) x 1024; "
                          "FETCH_SIZE raw except *_corrected_x2 (gfx950 tallies wide coalesced 128-B requests at 64 B)",
                   "msm_accumulate_shape": shape, "kernels": kern}, indent=1))
