@@ -247,6 +247,24 @@ void wsnark_host_free(void* p);
  * coordinates of the proof are ignored: (x, y) is the point. */
 int wsnark_groth16_verify(const void* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proof384, int* valid);
 
+/* MANY proofs against ONE key, on the device (csrc/pairing.hip): status[i] is what wsnark_groth16_verify(vk, vk_len, inputs_i,
+ * n_inputs, proof_i, &v) says about proof i -- 1 = valid, 0 = invalid, 2 = malformed (a coordinate of proof i, its z
+ * coordinates included, is not a reduced field element: the case in which the single call returns WSNARK_ERR_FORMAT).  Every rule
+ * of the single call holds per proof (z ignored; an input >= r is invalid, not an error; an off-curve point or a G2 point outside
+ * the order-r subgroup is invalid before anything is paired).
+ * vk: the single call's layout, in HOST memory in both variants.  inputs: count x n_inputs x 32 bytes (proof i's public signals
+ * one after the other), proofs384: count x 384 bytes, each record as wsnark_groth16_prove writes it; host memory (staged through
+ * the upload ring) or, for _dev, device memory read on `stream` (NULL = the lane's queue).  status: count bytes, host memory.
+ * What the key alone decides is decided once per call, on the host: an unreduced key coordinate is WSNARK_ERR_FORMAT for the call,
+ * fewer IC points than n_inputs + 1 WSNARK_ERR_SIZE (nothing is written); a key point that fails its curve / subgroup test makes
+ * every status 0 (2 for a malformed proof).  count == 0 is WSNARK_OK and touches nothing; count > 2^24 is WSNARK_ERR_SIZE.
+ * Unlike the single call these need wsnark_init (WSNARK_ERR_NOINIT otherwise); callable from any thread, each call takes a lane of
+ * the context like an MSM does.  Both return when status has been written. */
+int wsnark_groth16_verify_batch(const void* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proofs384, uint64_t count,
+                                uint8_t* status);
+int wsnark_groth16_verify_batch_dev(const void* vk, size_t vk_len, const void* d_inputs, uint64_t n_inputs, const void* d_proofs384,
+                                    uint64_t count, uint8_t* status_host, void* stream);
+
 /* The two 32-byte blinding values of the last proof assembled by the CALLING THREAD (wsnark_groth16_prove[_dev] or
  * _prove_finish), whether injected or drawn from the OS CSPRNG: the reference keeps them the same way, "for tests",
  * as this._pr / this._ps (src/bn128.js:662-664).  WSNARK_ERR_ARG if this thread has not proved yet. */
@@ -423,6 +441,12 @@ int wsnark_selftest_field(int which, int impl, int op, const void* a, const void
  *   them, field29.h) followed by its narrowing, 8 = timesScalar (src/build_timesscalar.js:20-80): q's bytes are NOT a point
  *   but a little-endian scalar in bytes [0, 64) and its length -- 32 or 64 -- in byte 64 (impl 0-3). */
 int wsnark_selftest_curve(int g, int impl, int op, const void* p, const void* q, void* out, uint64_t n);
+/* The Fp12 arithmetic of the batch verifier (csrc/fp12.h), one lane per element.
+ * op 0 = a * b, 1 = a^2, 2 = 1 / a, 3 = a^(p^2), 4 = final exponentiation of a (the shipped path: easy part by inversion,
+ * conjugation and Frobenius, then the hard exponent), 5 = final exponentiation by the plain exponent (p^12 - 1)/r;
+ * impl 0 = the device Fp12 of pairing.hip, 2 = the host Fp12 of the single-proof verifier (ops 2-5 there by plain exponentiation:
+ * the yardstick).  a, b, out: n x 384 bytes, twelve PLAIN little-endian Fq values, coefficient i of w^i = (c0, c1); n <= 2^16. */
+int wsnark_selftest_fp12(int impl, int op, const void* a, const void* b, void* out, uint64_t n);
 
 /* ---- measurement hooks (bench.py) ---- */
 /* A/B switches of the library (queue arrangement of a proof, reduction-tail geometry, ...; the names are the WSNARK_<name>

@@ -1,0 +1,354 @@
+"""Shared checks of the batch verifier (wsnark_groth16_verify_batch, csrc/pairing.hip) and of its Fp12 self-test hook, run by
+tests/test_emul_verify_batch.py on the thread-emulator build of the kernel sources and by tests/test_gpu_verify_batch.py on the
+device.  The judge everywhere is the pinned single-proof HOST verifier (wsnark_groth16_verify): status[i] of a batch must be
+what that call says about proof i (1 valid, 0 invalid, 2 = it returns WSNARK_ERR_FORMAT because of the proof).
+
+Also here, and NOT in the product: the forger.  With the toxic waste of a synthetic setup (wasmsnark_amd/synth.py) a VALID
+proof for ANY public input vector x costs three fixed-base multiplications and no proving: pick a, b, set
+c = (a b - alpha beta - sum_i x_i (beta a_i + alpha b_i + c_i)) / delta, A = a G1, B = b G2, C = c G1."""
+import ctypes as C
+import json
+import os
+import random
+import subprocess
+import sys
+
+from conftest import GOLDEN, ROOT, load_golden
+
+Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+OK, ERR_SIZE, ERR_FORMAT, ERR_NOINIT = 0, 1, 2, 5
+
+
+# ---- the two calls, raw ----
+def _inputs_bytes(inputs):
+    return b"".join(int(v).to_bytes(32, "little") for v in inputs)
+
+
+def host_status(lib, vkb, n_in, inputs_b, proof_b):
+    """What the single host call says: 1 / 0, or 2 when it returns WSNARK_ERR_FORMAT."""
+    v = C.c_int(0)
+    rc = lib.c.wsnark_groth16_verify(vkb, len(vkb), inputs_b if n_in else None, n_in, proof_b, C.byref(v))
+    if rc == ERR_FORMAT:
+        return 2
+    assert rc == OK, rc
+    return v.value
+
+
+def batch_status(lib, vkb, n_in, inputs_b, proofs_b, expect_rc=OK):
+    n = len(proofs_b) // 384
+    st = (C.c_uint8 * max(n, 1))(*([7] * max(n, 1)))
+    rc = lib.c.wsnark_groth16_verify_batch(vkb, len(vkb), inputs_b if n_in else None, n_in, proofs_b, n, st)
+    assert rc == expect_rc, (rc, (lib.c.wsnark_last_error() or b"").decode())
+    return list(st)[:n]
+
+
+def _vk(name):
+    return json.load(open(os.path.join(GOLDEN, "keys", name + ".vk.json"))), json.load(open(os.path.join(GOLDEN, "keys", name + ".public.json")))
+
+
+# ---- 1. Fp12 ----
+def _f12_bytes(coeffs):
+    assert len(coeffs) == 12
+    return b"".join((c % Q).to_bytes(32, "little") for c in coeffs)
+
+
+def _fp12(lib, impl, op, a, b=None):
+    n = len(a) // 384
+    out = (C.c_uint8 * (n * 384))()
+    rc = lib.c.wsnark_selftest_fp12(impl, op, a, b if b is not None else a, out, n)
+    assert rc == OK, (impl, op, rc, (lib.c.wsnark_last_error() or b"").decode())
+    return bytes(out)
+
+
+def fp12_elements(n_random, seed=11):
+    rnd = random.Random(seed)
+    rand = [[rnd.randrange(Q) for _ in range(12)] for _ in range(n_random)]
+    edge = [[0] * 12, [1] + [0] * 11, [Q - 1] + [0] * 11, [rnd.randrange(Q), rnd.randrange(Q)] + [0] * 10, [Q - 1] * 12]
+    return rand, edge
+
+
+def check_fp12(bn, n_random=8):
+    """ops 0-5, device (impl 0) against host (impl 2), on random elements and the edge grid; op 4 == op 5 on both; op 4 of a^r is 1."""
+    lib = bn.lib
+    rand, edge = fp12_elements(n_random)
+    elems = rand + edge
+    a = b"".join(_f12_bytes(e) for e in elems)
+    b = b"".join(_f12_bytes(e) for e in elems[3:] + elems[:3])
+    for op in range(6):
+        aa, bb = a, b
+        if op == 2:     # 1 / 0 is not defined
+            keep = [i for i, e in enumerate(elems) if any(e)]
+            aa = b"".join(a[384 * i:384 * i + 384] for i in keep)
+            bb = aa
+        dev, host = _fp12(lib, 0, op, aa, bb), _fp12(lib, 2, op, aa, bb)
+        n = len(aa) // 384
+        for i in range(n):
+            assert dev[384 * i:384 * i + 384] == host[384 * i:384 * i + 384], ("op", op, "element", i)
+    ra = b"".join(_f12_bytes(e) for e in rand)
+    assert len(rand) >= 8
+    e4 = _fp12(lib, 0, 4, ra)
+    assert e4 == _fp12(lib, 0, 5, ra) == _fp12(lib, 2, 4, ra) == _fp12(lib, 2, 5, ra)
+    # a^r by square-and-multiply on the host Fp12 (ops 0 / 1, impl 2); its final exponentiation is a^(p^12 - 1) = 1
+    x = _f12_bytes(rand[0])
+    acc = x
+    for bit in bin(R)[3:]:
+        acc = _fp12(lib, 2, 1, acc)
+        if bit == "1":
+            acc = _fp12(lib, 2, 0, acc, x)
+    one = _f12_bytes([1] + [0] * 11)
+    assert acc != one
+    assert _fp12(lib, 0, 4, acc) == one and _fp12(lib, 0, 5, acc) == one
+
+
+# ---- 2. the reference's own verifier data ----
+def check_golden_verify(bn):
+    from wasmsnark_amd.bn128 import proof_to_bytes, vk_to_bytes
+    g = load_golden("verify.json")
+    vk, cases = g["verification_key"], g["cases"]
+    assert len(cases) == 18 and sum(c["reference_verdict"] for c in cases) == 3
+    n_in = len(cases[0]["inputs"])
+    assert n_in == 58 and all(len(c["inputs"]) == n_in for c in cases)
+    vkb = vk_to_bytes(vk, n_in)
+    want = [int(bool(c["reference_verdict"])) for c in cases]
+    got = batch_status(bn.lib, vkb, n_in, b"".join(_inputs_bytes(c["inputs"]) for c in cases), b"".join(proof_to_bytes(c["proof"]) for c in cases))
+    assert got == want
+    for c, w in zip(cases, want):
+        assert batch_status(bn.lib, vkb, n_in, _inputs_bytes(c["inputs"]), proof_to_bytes(c["proof"])) == [w], (c["proof_file"], c["label"])
+    # the Python entry point, over the same cases
+    assert bn.groth16VerifyBatch(vk, [c["inputs"] for c in cases], [c["proof"] for c in cases]) == [bool(w) for w in want]
+    assert bn.groth16VerifyBatch(vk, [c["inputs"] for c in cases], [c["proof"] for c in cases], return_status=True) == want
+
+
+# ---- 3. the golden proofs of the two synthetic keys ----
+def check_golden_proofs(bn, name):
+    vk, pub = _vk(name)
+    inputs, proofs, want = [], [], []
+    for c in load_golden("proofs.json")[name]:
+        assert c["reference_verifies"] and c["reference_rejects_wrong_public"]
+        inputs += [pub, [str((int(pub[0]) + 1) % R)] + pub[1:], pub]
+        proofs += [c["proof"], c["proof"], dict(c["proof"], pi_a=c["proof"]["pi_c"])]
+        want += [True, False, False]
+    assert len(proofs) >= 3
+    assert bn.groth16VerifyBatch(vk, inputs, proofs) == want
+
+
+# ---- 4. malformed points between valid neighbours ----
+def _f2_mul(a, b):
+    return ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
+
+
+def _f2_inv(a):
+    n = pow((a[0] * a[0] + a[1] * a[1]) % Q, Q - 2, Q)
+    return (a[0] * n % Q, (-a[1]) * n % Q)
+
+
+def _f2_sqrt(a):
+    """sqrt in Fq[u]/(u^2 + 1), q = 3 mod 4 (complex method); None if a is not a square."""
+    if a == (0, 0):
+        return (0, 0)
+    norm = (a[0] * a[0] + a[1] * a[1]) % Q
+    s = pow(norm, (Q + 1) // 4, Q)
+    if s * s % Q != norm:
+        return None
+    half = pow(2, Q - 2, Q)
+    for sign in (1, -1):
+        t = (a[0] + sign * s) * half % Q
+        x0 = pow(t, (Q + 1) // 4, Q)
+        if x0 * x0 % Q == t and x0:
+            x1 = a[1] * pow(2 * x0 % Q, Q - 2, Q) % Q
+            if _f2_mul((x0, x1), (x0, x1)) == (a[0] % Q, a[1] % Q):
+                return (x0, x1)
+    return None
+
+
+def twist_point_outside_g2():
+    """A point on the twist y^2 = x^3 + 3/(9 + u), almost surely not in the order-r subgroup (the cofactor is ~2^254)."""
+    b2 = _f2_mul((3, 0), _f2_inv((9, 1)))
+    k = 1
+    while True:
+        x = (k, 7 * k + 1)
+        x3 = _f2_mul(_f2_mul(x, x), x)
+        y = _f2_sqrt(((x3[0] + b2[0]) % Q, (x3[1] + b2[1]) % Q))
+        if y is not None:
+            return [[str(x[0]), str(x[1])], [str(y[0]), str(y[1])], ["1", "0"]]
+        k += 1
+
+
+def malformed_cases(good, good2, pub):
+    """(label, inputs, proof) on the t6 key: the cases of test_verify.py::test_malformed_points_are_invalid_not_paired and friends."""
+    bump = lambda p: [p[0], str((int(p[1]) + 1) % Q), p[2]]
+    b = good["pi_b"]
+    return [
+        ("valid", pub, good),
+        ("valid other proof", pub, good2),
+        ("pi_a off the curve", pub, dict(good, pi_a=bump(good["pi_a"]))),
+        ("pi_c off the curve", pub, dict(good, pi_c=bump(good["pi_c"]))),
+        ("pi_b off the twist", pub, dict(good, pi_b=[b[0], [b[1][0], str((int(b[1][1]) + 1) % Q)], b[2]])),
+        ("pi_b outside the subgroup", pub, dict(good, pi_b=twist_point_outside_g2())),
+        ("z coordinates 0 and 5", pub, dict(good, pi_a=[good["pi_a"][0], good["pi_a"][1], "0"], pi_c=good["pi_c"][:2] + ["5"])),
+        ("proof at infinity", pub, {"pi_a": ["0", "1", "0"], "pi_b": [["0", "0"], ["1", "0"], ["0", "0"]], "pi_c": ["0", "1", "0"]}),
+        ("an input >= r", [str(R + 1)] + pub[1:], good),
+        ("an input = r", pub[:-1] + [str(R)], good),
+        ("coordinate >= q in pi_a", pub, dict(good, pi_a=[str(Q + 5), good["pi_a"][1], "1"])),
+        ("coordinate = q in pi_b", pub, dict(good, pi_b=[b[0], [str(Q), b[1][1]], b[2]])),
+        ("z coordinate >= q in pi_c", pub, dict(good, pi_c=good["pi_c"][:2] + [str(Q + 1)])),
+        ("wrong public input", [str((int(pub[0]) + 1) % R)] + pub[1:], good),
+    ]
+
+
+def check_mixed_batches(bn, sizes=(1, 2, 63, 65, 131), seed=5):
+    from wasmsnark_amd.bn128 import proof_to_bytes, vk_to_bytes
+    lib = bn.lib
+    vk, pub = _vk("t6")
+    gp = load_golden("proofs.json")["t6"]
+    cases = malformed_cases(gp[1]["proof"], gp[0]["proof"], pub)
+    n_in = len(pub)
+    vkb = vk_to_bytes(vk, n_in)
+    enc = [(_inputs_bytes(i), proof_to_bytes(p)) for _, i, p in cases]
+    single = [host_status(lib, vkb, n_in, ib, pb) for ib, pb in enc]        # the judge, once per distinct proof
+    by_label = dict(zip((c[0] for c in cases), single))
+    assert by_label["valid"] == 1 and by_label["valid other proof"] == 1 and by_label["z coordinates 0 and 5"] == 1
+    assert by_label["coordinate >= q in pi_a"] == 2 and by_label["coordinate = q in pi_b"] == 2 and by_label["z coordinate >= q in pi_c"] == 2
+    assert all(by_label[c[0]] == 0 for c in cases if by_label[c[0]] not in (1, 2)) and sorted(set(single)) == [0, 1, 2]
+    rnd = random.Random(seed)
+    for n in sizes:
+        # every case once where the size allows, the rest half valid proofs, half random cases; a seeded random order
+        if n >= len(cases):
+            pick = list(range(len(cases))) + [rnd.randrange(2) if j % 2 else rnd.randrange(len(cases)) for j in range(n - len(cases))]
+        else:
+            pick = [rnd.randrange(len(cases)) for _ in range(n)]
+        rnd.shuffle(pick)
+        got = batch_status(lib, vkb, n_in, b"".join(enc[k][0] for k in pick), b"".join(enc[k][1] for k in pick))
+        want = [single[k] for k in pick]
+        assert got == want, (n, [(cases[k][0], g, w) for k, g, w in zip(pick, got, want) if g != w])
+
+
+# ---- 5. what the key alone decides ----
+def check_key_level(bn, so_path):
+    from wasmsnark_amd.bn128 import proof_to_bytes, vk_to_bytes
+    lib = bn.lib
+    vk, pub = _vk("t6")
+    gp = load_golden("proofs.json")["t6"]
+    good = [gp[0]["proof"], gp[1]["proof"], gp[0]["proof"]]
+    n_in = len(pub)
+    ib, pb = _inputs_bytes(pub) * 3, b"".join(proof_to_bytes(p) for p in good)
+    assert batch_status(lib, vk_to_bytes(vk, n_in), n_in, ib, pb) == [1, 1, 1]
+    bump = lambda p: [p[0], str((int(p[1]) + 1) % Q), p[2]]
+    rogue = twist_point_outside_g2()
+    bad_keys = [dict(vk, vk_alfa_1=bump(vk["vk_alfa_1"])), dict(vk, vk_gamma_2=rogue), dict(vk, vk_delta_2=rogue),
+                dict(vk, IC=[bump(vk["IC"][0])] + vk["IC"][1:]), dict(vk, IC=vk["IC"][:-1] + [bump(vk["IC"][-1])])]
+    for k in bad_keys:
+        kb = vk_to_bytes(k, n_in)
+        assert batch_status(lib, kb, n_in, ib, pb) == [0, 0, 0]
+        assert [host_status(lib, kb, n_in, _inputs_bytes(pub), proof_to_bytes(p)) for p in good] == [0, 0, 0]
+    # an unreduced key coordinate: WSNARK_ERR_FORMAT for the call, nothing written
+    for k in (dict(vk, vk_alfa_1=[str(Q + 1), vk["vk_alfa_1"][1], "1"]), dict(vk, IC=vk["IC"][:-1] + [[str(Q), "2", "1"]])):
+        assert batch_status(lib, vk_to_bytes(k, n_in), n_in, ib, pb, expect_rc=ERR_FORMAT) == [7, 7, 7]
+    # the input count cannot wrap the size check (the four values of test_verify.py::test_input_count_cannot_wrap_the_size_check)
+    vkb = bytes(512)
+    for n_inputs in (1 << 58, (1 << 58) - 1, (1 << 64) - 1, 2):
+        st = (C.c_uint8 * 1)(7)
+        rc = lib.c.wsnark_groth16_verify_batch(vkb, len(vkb), bytes(64), C.c_uint64(n_inputs), bytes(384), 1, st)
+        assert rc == ERR_SIZE and st[0] == 7, n_inputs
+    st = (C.c_uint8 * 1)(7)
+    assert lib.c.wsnark_groth16_verify_batch(vk_to_bytes(vk, n_in), 448 + 64 * (n_in + 1), ib, n_in, pb, (1 << 24) + 1, st) == ERR_SIZE and st[0] == 7
+    # count = 0 touches nothing (not even its pointers)
+    assert lib.c.wsnark_groth16_verify_batch(None, 0, None, 0, None, 0, None) == OK
+    assert bn.groth16VerifyBatch(vk, [], []) == []
+    # before wsnark_init: a fresh process that loads the library and never initialises it
+    code = ("import ctypes as C, sys\n"
+            "c = C.CDLL(sys.argv[1])\n"
+            "st = (C.c_uint8 * 1)(7)\n"
+            "rc = c.wsnark_groth16_verify_batch(bytes(512), C.c_size_t(512), None, C.c_uint64(0), bytes(384), C.c_uint64(1), st)\n"
+            "print(rc, st[0])\n")
+    out = subprocess.run([sys.executable, "-c", code, so_path], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.split() == [str(ERR_NOINIT), "7"], (out.stdout, out.stderr)
+
+
+def check_python_argument_errors(bn):
+    import pytest
+    vk, pub = _vk("t6")
+    good = load_golden("proofs.json")["t6"][0]["proof"]
+    with pytest.raises(ValueError):
+        bn.groth16VerifyBatch(vk, [pub, pub[:-1]], [good, good])            # input vectors of two lengths
+    with pytest.raises(ValueError):
+        bn.groth16VerifyBatch(vk, [pub], [good, good])
+    # an input outside [0, 2^256) makes that proof False without reaching the library; its neighbours are unaffected
+    assert bn.groth16VerifyBatch(vk, [pub, [str(1 << 256)] + pub[1:], ["-1"] + pub[1:], pub], [good] * 4) == [True, False, False, True]
+
+
+# ---- 6. forged proofs from known toxic waste ----
+class Forger:
+    """A synthetic setup with known toxic waste, its snarkjs verification key, and valid proofs for any public inputs."""
+
+    def __init__(self, bn, n_public, seed=3, log_domain=4):
+        from wasmsnark_amd import synth
+        self.bn, self.n_public = bn, n_public
+        circ = synth.make_circuit(log_domain, n_public=n_public, seed=seed)
+        self.S = S = synth.setup(circ, seed=seed + 100)
+        sec, (ic, gamma2) = synth.build_sections(circ, S, bn.mul_base)
+        self.vk = synth.vk_from_points(n_public, sec, ic, gamma2)
+        self.k = [(S.beta * S.a[s] + S.alpha * S.b[s] + S.c[s]) % R for s in range(n_public + 1)]
+        self.rnd = random.Random(seed + 1000)
+
+    def vk_bytes(self):
+        from wasmsnark_amd.bn128 import vk_to_bytes
+        return vk_to_bytes(self.vk, self.n_public)
+
+    def forge(self, n):
+        """n valid proofs with distinct random public inputs: (inputs bytes (n x n_public x 32), proofs bytes (n x 384))."""
+        rinv = pow(1 << 256, Q - 2, Q)
+        S, rnd = self.S, self.rnd
+        xs = [[rnd.randrange(R) for _ in range(self.n_public)] for _ in range(n)]
+        ab = [(rnd.randrange(1, R), rnd.randrange(1, R)) for _ in range(n)]
+        dinv = pow(S.delta, R - 2, R)
+        cs = [((a * b - S.alpha * S.beta - sum(x * k for x, k in zip([1] + x_, self.k))) * dinv) % R for (a, b), x_ in zip(ab, xs)]
+        le = lambda v: int(v).to_bytes(32, "little")
+        g1 = self.bn.mul_base(1, b"".join(le(a) for a, _ in ab) + b"".join(le(c) for c in cs))
+        g2 = self.bn.mul_base(2, b"".join(le(b) for _, b in ab))
+        plain = lambda bs: le(int.from_bytes(bs, "little") * rinv % Q)         # Montgomery affine bytes -> plain
+        one, zero = le(1), le(0)
+        proofs = bytearray()
+        for i in range(n):
+            A, Cp, B = g1[64 * i:64 * i + 64], g1[64 * (n + i):64 * (n + i) + 64], g2[128 * i:128 * i + 128]
+            proofs += plain(A[:32]) + plain(A[32:]) + one
+            proofs += b"".join(plain(B[32 * j:32 * j + 32]) for j in range(4)) + one + zero
+            proofs += plain(Cp[:32]) + plain(Cp[32:]) + one
+        return b"".join(le(v) for x_ in xs for v in x_), bytes(proofs)
+
+
+COORD_WORDS = (0, 1, 3, 4, 5, 6, 9, 10)      # the eight x / y coordinates of a 384-byte proof record (z words: 2, 7, 8, 11)
+
+
+def tamper(proofs_b, which, rnd):
+    """One random bit of one random x / y coordinate flipped in each proof of `which`; returns (bytes, {index: status by construction})."""
+    p = bytearray(proofs_b)
+    want = {}
+    for i in which:
+        w, bit = rnd.choice(COORD_WORDS), rnd.randrange(256)
+        off = 384 * i + 32 * w
+        v = int.from_bytes(p[off:off + 32], "little") ^ (1 << bit)
+        p[off:off + 32] = v.to_bytes(32, "little")
+        want[i] = 2 if v >= Q else 0          # a changed coordinate is another point, or none: never valid
+    return bytes(p), want
+
+
+def check_forged(bn, n_public, n, seed=3):
+    lib = bn.lib
+    F = Forger(bn, n_public, seed=seed)
+    vkb = F.vk_bytes()
+    ib, pb = F.forge(n)
+    # the forger itself, once against the pinned host verifier
+    assert host_status(lib, vkb, n_public, ib[:32 * n_public], pb[:384]) == 1
+    assert batch_status(lib, vkb, n_public, ib, pb) == [1] * n
+    rnd = random.Random(seed + 7)
+    which = sorted(rnd.sample(range(n), n // 3))
+    tp, want = tamper(pb, which, rnd)
+    got = batch_status(lib, vkb, n_public, ib, tp)
+    for i in range(n):
+        if i in want:
+            single = host_status(lib, vkb, n_public, ib[32 * n_public * i:32 * n_public * (i + 1)], tp[384 * i:384 * i + 384])
+            assert got[i] == single == want[i], (i, got[i], single, want[i])
+        else:
+            assert got[i] == 1, i

@@ -483,6 +483,14 @@ class Bn128:
         the reference does, :724-728); proof: {pi_a, pi_b, pi_c} of decimal strings.  Returns True / False."""
         return groth16_verify(self.lib, verificationKey, input, proof)
 
+    def groth16VerifyBatch(self, verificationKey, inputs, proofs, return_status=False):
+        """Many proofs against ONE verification key, on the GPU (wsnark_groth16_verify_batch; no reference counterpart).
+        inputs: one list of public signals per proof, all of one length (ValueError otherwise); proofs: a list of
+        {pi_a, pi_b, pi_c}.  Returns a list of bool, proof by proof what groth16Verify says (a proof with an unreduced
+        coordinate, which the single call raises on, reads as False), or with return_status the raw statuses
+        (1 valid, 0 invalid, 2 malformed)."""
+        return groth16_verify_batch(self.lib, verificationKey, inputs, proofs, return_status)
+
     def terminate(self):  # src/bn128.js:562-566
         self.lib.shutdown()
 
@@ -524,6 +532,32 @@ def groth16_verify(lib, verificationKey, input, proof):
     valid = C.c_int(0)
     lib.check(lib.c.wsnark_groth16_verify(vkb, len(vkb), inp if vals else None, len(vals), proof_to_bytes(proof), C.byref(valid)))
     return bool(valid.value)
+
+
+def groth16_verify_batch(lib, verificationKey, inputs, proofs, return_status=False):
+    """Bn128.groth16VerifyBatch over wsnark_groth16_verify_batch: needs an initialised library (a GPU)."""
+    inputs = [list(x) if isinstance(x, (list, tuple)) else ([] if x is None else [x]) for x in inputs]
+    proofs = list(proofs)
+    if len(inputs) != len(proofs):
+        raise ValueError("%d input vectors for %d proofs" % (len(inputs), len(proofs)))
+    if not proofs:
+        return []
+    n_in = len(inputs[0])
+    if any(len(x) != n_in for x in inputs):
+        raise ValueError("all proofs of a batch share the key, so every input vector must have %d entries" % n_in)
+    vkb = vk_to_bytes(verificationKey, n_in)
+    vals = [[int(v) for v in x] for x in inputs]
+    # an input outside [0, 2^256) makes that proof invalid without reaching the library, as in groth16_verify
+    keep = [i for i, x in enumerate(vals) if all(0 <= v < 1 << 256 for v in x)]
+    status = [0] * len(proofs)
+    if keep:
+        inp = b"".join(v.to_bytes(32, "little") for i in keep for v in vals[i])
+        prf = b"".join(proof_to_bytes(proofs[i]) for i in keep)
+        st = (C.c_uint8 * len(keep))()
+        lib.check(lib.c.wsnark_groth16_verify_batch(vkb, len(vkb), inp if n_in else None, n_in, prf, len(keep), st))
+        for i, v in zip(keep, st):
+            status[i] = int(v)
+    return status if return_status else [v == 1 for v in status]
 
 
 def build(lib=None, device=-1):

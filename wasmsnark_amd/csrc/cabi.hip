@@ -48,6 +48,7 @@ void points_info(const ResidentPoints* H, int* which, uint64_t* n, uint32_t* tab
 int points_msm(ResidentPoints* H, const void* scalars, bool on_device, uint64_t n, void* out, hipStream_t s);
 int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
 int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, uint8_t* out, uint64_t n);
+int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
 }  // namespace wsnark
 
 using namespace wsnark;
@@ -408,6 +409,17 @@ int wsnark_groth16_verify(const void* vk, size_t vk_len, const void* inputs, uin
     if (!vk || !proof384 || !valid || (n_inputs && !inputs)) return WSNARK_ERR_ARG;
     return groth16_verify((const uint8_t*)vk, vk_len, (const uint8_t*)inputs, n_inputs, (const uint8_t*)proof384, valid);
 }
+// batch verification on the device (pairing.hip); the key stays on the host in both variants
+int wsnark_groth16_verify_batch(const void* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proofs384, uint64_t count,
+                                uint8_t* status) {
+    REQUIRE_CTX();
+    return groth16_verify_batch((const uint8_t*)vk, vk_len, inputs, n_inputs, proofs384, count, status, false, nullptr);
+}
+int wsnark_groth16_verify_batch_dev(const void* vk, size_t vk_len, const void* d_inputs, uint64_t n_inputs, const void* d_proofs384,
+                                    uint64_t count, uint8_t* status_host, void* stream) {
+    REQUIRE_CTX();
+    return groth16_verify_batch((const uint8_t*)vk, vk_len, d_inputs, n_inputs, d_proofs384, count, status_host, true, (hipStream_t)stream);
+}
 int wsnark_last_blinding(void* r32, void* s32) {
     return last_blinding((uint8_t*)r32, (uint8_t*)s32) ? WSNARK_OK : WSNARK_ERR_ARG;
 }
@@ -438,6 +450,11 @@ int wsnark_selftest_curve(int g, int impl, int op, const void* p, const void* q,
     REQUIRE_CTX();
     if (n && (!p || !q || !out)) return WSNARK_ERR_ARG;
     return selftest_curve(g, impl, op, (const uint8_t*)p, (const uint8_t*)q, (uint8_t*)out, n);
+}
+int wsnark_selftest_fp12(int impl, int op, const void* a, const void* b, void* out, uint64_t n) {
+    REQUIRE_CTX();
+    if (n && (!a || !b || !out)) return WSNARK_ERR_ARG;
+    return selftest_fp12(impl, op, (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)out, n);
 }
 
 int wsnark_peak_probe(int probe, double* gops_per_s) {

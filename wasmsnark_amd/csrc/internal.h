@@ -83,6 +83,7 @@ struct Lane {
     DevBuf dist_buf[2];                         // distributed CALC_H: the rank's slices of (a, b, E), ping-pong (dist.hip)
     ScratchChain ntt_chain, calch_chain;        // who may touch ntt_scratch / calch_buf next (calls return before the GPU is done)
     DevBuf witness, h;                          // per-proof device buffers (grow-only)
+    DevBuf verify_ws;                           // batch verification (pairing.hip): key tables, per-proof points, Miller values (grow-only)
     hipEvent_t ev_start = nullptr, ev_tail = nullptr, ev_h = nullptr;   // cross-queue ordering of one proof
     hipEvent_t ev_plan = nullptr, ev_g2 = nullptr;                      // ... witness plan ready / G2 sum enqueued (third queue)
 };
@@ -277,6 +278,16 @@ int msm_g2_finish(Lane& L, int slot, XYZZ<Fq2>* out_host);
 void msm_abort_slots(Lane& L, const int* slots, int nslots, hipStream_t a, hipStream_t b);
 void msm_workspace_free(Lane& L);
 int msm_prepare_points(int which, void* d_points, uint64_t n, hipStream_t s);
+
+// ---- batch Groth16 verification (pairing.hip) ----
+struct PairConsts;    // fp12.h
+// the constants of the device pairing (Frobenius table, exponents, domain multipliers), computed from xi with the host field and
+// self-checked the first time they are asked for; WS_OK or WS_ERR_FORMAT if the self-check fails
+int pairing_consts(const PairConsts** out);
+// status[i] in {0, 1, 2} for count proofs against one key (include/wsnark.h: wsnark_groth16_verify_batch); inputs / proofs on the
+// host (staged through the ring) or on the device
+int groth16_verify_batch(const uint8_t* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proofs384, uint64_t count,
+                         uint8_t* status_host, bool on_device, hipStream_t s);
 
 // ---- CALC_H pieces (calch.hip) ----
 struct CsrMatrix {            // row-major transpose of the reference's column-major pols blob

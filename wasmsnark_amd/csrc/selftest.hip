@@ -14,6 +14,8 @@
 
 #include "../../include/wsnark.h"
 #include "internal.h"
+#include "fp12.h"
+#include "fp12_host.h"
 
 namespace wsnark {
 
@@ -414,6 +416,62 @@ int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, 
         if (impl == 4) return st_curve_pair_dev(op, p, q, out, n, s);
     }
     return WS_ERR_ARG;
+}
+
+// ---- Fp12 (fp12.h, the batch verifier's arithmetic): one lane per element, against the host verifier's Fp12 (fp12_host.h) ----
+// op 0 = a b, 1 = a^2, 2 = 1 / a, 3 = a^(p^2), 4 = final exponentiation (the shipped, split form), 5 = the same by the plain exponent
+__global__ __launch_bounds__(64) void st_fp12_kernel(int op, const Fe* __restrict__ a, const Fe* __restrict__ b, Fe* __restrict__ out,
+                                                       const PairConsts* __restrict__ K, uint64_t n, int* __restrict__ bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    F12d x, y, r;
+    f12d_load_plain(&x, a + 12 * i, K);
+    f12d_load_plain(&y, b + 12 * i, K);
+    switch (op) {
+        case 0: f12d_mul(&r, &x, &y); break;
+        case 1: f12d_sqr(&r, &x); break;
+        case 2: f12d_inv(&r, &x); break;
+        case 3: f12d_frob2(&r, &x, K); break;
+        case 4: f12d_final_exp(&r, &x, K, 0); break;
+        case 5: f12d_final_exp(&r, &x, K, 1); break;
+        default: r = x; *bad = 1; break;
+    }
+    f12d_store_plain(out + 12 * i, &r);
+}
+int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n) {
+    Context* X = ctx();
+    if (!X) return WS_ERR_NOINIT;
+    if (n == 0) return WS_OK;
+    if (!a || !b || !out || op < 0 || op > 5 || (impl != 0 && impl != 2)) return WS_ERR_ARG;
+    if (n > (1u << 16)) return WS_ERR_SIZE;
+    if (impl == 2) {
+        using namespace hostpair;
+        for (uint64_t i = 0; i < n; i++) {
+            const F12 x = f12_from_plain(a + i * 384), y = f12_from_plain(b + i * 384);
+            F12 r;
+            switch (op) {
+                case 0: r = f12_mul(x, y); break;
+                case 1: r = f12_mul(x, x); break;
+                case 2: r = f12_pow(x, kExpInv, kExpInvBits); break;        // Fermat: a^(p^12 - 2)
+                case 3: r = f12_pow(x, kExpP2, kExpP2Bits); break;
+                default: r = final_exponentiation(x); break;                // 4 and 5: the verifier's own plain exponentiation
+            }
+            f12_to_plain(r, out + i * 384);
+        }
+        return WS_OK;
+    }
+    const PairConsts* K = nullptr;
+    int rc = pairing_consts(&K);
+    if (rc) return rc;
+    hipStream_t s = X->stream;
+    StBufs B;
+    DevBuf dk;
+    if ((rc = B.up(a, b, n * 384, n * 384, s))) return rc;
+    WS_HIP_CHECK(dk.alloc(sizeof *K));
+    WS_HIP_CHECK(hipMemcpyAsync(dk.p, K, sizeof *K, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(st_fp12_kernel, dim3(ceil_div_u64(n, 64)), dim3(64), 0, s, op, B.a.as<Fe>(), B.b.as<Fe>(), B.out.as<Fe>(),
+                       (const PairConsts*)dk.p, n, B.bad.as<int>());
+    return B.down(out, n * 384, s);
 }
 
 // ---- peak probes (bench.py: the integer roofline's peak, re-measured on the box the run is on) ----

@@ -217,6 +217,29 @@ class Bn128 {
         const pf = le32cat([].concat(proof.pi_a, proof.pi_b[0], proof.pi_b[1], proof.pi_b[2], proof.pi_c));
         return addon.verify(vk, le32cat(vals), pf);
     }
+    /* Many proofs against ONE verification key, on the GPU (wsnark_groth16_verify_batch; no reference counterpart): inputs = one array
+     * of public signals per proof, all of one length; proofs = [{pi_a, pi_b, pi_c}, ...].  Resolves to boolean[], proof by proof
+     * what groth16Verify says (a proof with an unreduced coordinate, which the single call rejects with an error, reads false). */
+    async groth16VerifyBatch(verificationKey, inputs, proofs) {
+        if (!Array.isArray(inputs) || !Array.isArray(proofs) || inputs.length !== proofs.length) throw new TypeError("expected one input array per proof");
+        if (proofs.length === 0) return [];
+        const rows = inputs.map((x) => (x === undefined || x === null ? [] : Array.isArray(x) ? x : [x]).map((v) => BigInt(v)));
+        const nIn = rows[0].length;
+        if (rows.some((r) => r.length !== nIn)) throw new TypeError("all proofs of a batch share the key: every input array must have " + nIn + " entries");
+        const IC = verificationKey.IC;
+        if (!IC || IC.length < nIn + 1) throw new Error("verification key has fewer IC points than inputs + 1");
+        const g1 = (p) => [p[0], p[1]], g2 = (p) => [p[0][0], p[0][1], p[1][0], p[1][1]];
+        const vk = le32cat([].concat(g1(verificationKey.vk_alfa_1), g2(verificationKey.vk_beta_2), g2(verificationKey.vk_gamma_2),
+            g2(verificationKey.vk_delta_2), ...IC.slice(0, nIn + 1).map(g1)));
+        // an input outside [0, 2^256) makes that proof false without reaching the library, as in groth16Verify
+        const keep = rows.map((r, i) => i).filter((i) => !rows[i].some((v) => v < 0n || v >= (1n << 256n)));
+        const out = new Array(proofs.length).fill(false);
+        if (keep.length === 0) return out;
+        const pf = le32cat([].concat(...keep.map((i) => { const p = proofs[i]; return [].concat(p.pi_a, p.pi_b[0], p.pi_b[1], p.pi_b[2], p.pi_c); })));
+        const st = new Uint8Array(await addon.verifyBatch(vk, le32cat([].concat(...keep.map((i) => rows[i]))), pf, nIn));
+        keep.forEach((i, k) => { out[i] = st[k] === 1; });
+        return out;
+    }
     /* src/bn128.js:562-566.  The GPU context is process-wide (one per addon): it is shut down when the LAST live Bn128
      * object terminates, so one object's terminate() does not pull the device out from under another's proofs. */
     terminate() {
@@ -276,7 +299,16 @@ function groth16Verify(verificationKey, input, proof, cb) {   // main_bn128.js:4
     return p;
 }
 
+function groth16VerifyBatch(verificationKey, inputs, proofs, cb) {
+    const p = (async () => {
+        if (!singleton) singleton = await buildBn128();
+        return singleton.groth16VerifyBatch(verificationKey, inputs, proofs);
+    })();
+    if (cb) { p.then((ok) => cb(null, ok), (err) => cb(err)); return undefined; }
+    return p;
+}
+
 const formats = require("./formats.js");     // snarkjs JSON -> proving_key.bin / witness.bin (reference tools/build*.js)
-module.exports = { buildBn128, groth16GenProof, genZKSnarkProof: groth16GenProof, groth16Verify, terminate, Bn128, proofFromBytes,
+module.exports = { buildBn128, groth16GenProof, genZKSnarkProof: groth16GenProof, groth16Verify, groth16VerifyBatch, terminate, Bn128, proofFromBytes,
     pkeyJsonToBin: formats.pkeyJsonToBin, witnessJsonToBin: formats.witnessJsonToBin,
     pkeyBinSections: formats.pkeyBinSections, writeKeyContainer: formats.writeKeyContainer, pkeyBinToContainer: formats.pkeyBinToContainer };

@@ -39,6 +39,7 @@ static struct {
     int (*prove)(wsnark_pkey_t*, const void*, size_t, const void*, const void*, void*);
     int (*last_blinding)(void*, void*);
     int (*verify)(const void*, size_t, const void*, uint64_t, const void*, int*);
+    int (*verify_batch)(const void*, size_t, const void*, uint64_t, const void*, uint64_t, uint8_t*);
     int (*host_alloc)(size_t, void**);
     void (*host_free)(void*);
     int (*pkey_load_stats)(const wsnark_pkey_t*, double*);
@@ -93,6 +94,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(fr_ntt, "wsnark_fr_ntt") SYM(calc_h, "wsnark_calc_h") SYM(pkey_load, "wsnark_pkey_load")
     SYM(pkey_free, "wsnark_pkey_free") SYM(pkey_info, "wsnark_pkey_info") SYM(prove, "wsnark_groth16_prove")
     SYM(last_blinding, "wsnark_last_blinding") SYM(verify, "wsnark_groth16_verify")
+    SYM(verify_batch, "wsnark_groth16_verify_batch")
     SYM(host_alloc, "wsnark_host_alloc") SYM(host_free, "wsnark_host_free")
     SYM(pkey_load_stats, "wsnark_pkey_load_stats") SYM(pkey_wait_tables, "wsnark_pkey_wait_tables")
     SYM(points_load, "wsnark_points_load") SYM(points_free, "wsnark_points_free") SYM(points_info, "wsnark_points_info") SYM(points_msm, "wsnark_points_msm")
@@ -128,7 +130,7 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
-       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE };
+       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -267,6 +269,7 @@ static void job_execute(napi_env env, void* data) {
     case OP_LOADKEY_FILE: j->rc = L.pkey_load_file(j->path, 0, 1, 0, &j->key); break;
     case OP_GROUP_LOADKEY_FILE: j->rc = L.group_pkey_load_file(j->gr->g, j->path, &j->gk->k); break;
     case OP_VERIFY: j->rc = L.verify(j->a, j->na, j->b, j->nb / 32, j->c, &j->i0); break;
+    case OP_VERIFY_BATCH: j->rc = L.verify_batch(j->a, j->na, j->nb ? j->b : NULL, j->u0, j->c, j->nc / 384, j->out); break;
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
     case OP_GROUP_G1: j->rc = L.group_g1_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
     case OP_GROUP_G2: j->rc = L.group_g2_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
@@ -537,6 +540,24 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
         FAIL(env, j, "expected (vkBytes, inputBytes (n x 32), proof384)");
     keep(env, j, argv[0]); keep(env, j, argv[1]); keep(env, j, argv[2]);
     return start_job(env, j, "wsnark_groth16_verify");
+}
+
+/* verifyBatch(vkBytes, inputBytes (count x nInputs x 32), proofs (count x 384), nInputs) -> Promise<ArrayBuffer count>: one status
+ * byte per proof, 1 valid / 0 invalid / 2 malformed (include/wsnark.h, wsnark_groth16_verify_batch: on the GPU, needs init()) */
+static napi_value js_verify_batch(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_VERIFY_BATCH;
+    if (argc < 4 || !get_bytes(env, argv[0], &j->a, &j->na) || !get_bytes(env, argv[1], &j->b, &j->nb) ||
+        !get_bytes(env, argv[2], &j->c, &j->nc) || napi_get_value_uint32(env, argv[3], &j->u0) != napi_ok ||
+        j->nc == 0 || j->nc % 384 || j->nb != (j->nc / 384) * (size_t)j->u0 * 32)
+        FAIL(env, j, "expected (vkBytes, inputBytes (count x nInputs x 32), proofs (count x 384), nInputs)");
+    j->nout = j->nc / 384;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[0]); keep(env, j, argv[1]); keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_groth16_verify_batch");
 }
 
 /* allocPinned(bytes) -> ArrayBuffer over pinned host memory (wsnark_host_alloc): a witness written into it is DMA'd in place,
@@ -856,6 +877,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"prove", NULL, js_prove, NULL, NULL, NULL, napi_default, NULL},
         {"waitTables", NULL, js_wait_tables, NULL, NULL, NULL, napi_default, NULL},
         {"verify", NULL, js_verify, NULL, NULL, NULL, napi_default, NULL},
+        {"verifyBatch", NULL, js_verify_batch, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},
