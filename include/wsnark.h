@@ -202,6 +202,49 @@ int wsnark_pkey_load_shard(const wsnark_key_sections_t* sections, uint32_t rank,
 int wsnark_pkey_load_file(const char* path, uint32_t rank, uint32_t world, uint32_t h_interleave_log, wsnark_pkey_t** out_handle);
 /* header of a key file without loading it (no GPU needed).  format: 1 = proving_key.bin, 2 = WSNARK64.  Out pointers may be NULL. */
 int wsnark_pkey_file_info(const char* path, uint32_t* n_vars, uint32_t* n_public, uint32_t* domain, uint64_t* file_bytes, int* format);
+/* ---- the audit of a proving key (csrc/pkeycheck.hip; snarkjs users know the step as `zkey verify`) ----
+ * The loaders above never look at a point: a coordinate that is no field element, a point off its curve, a G2 point outside the
+ * order-r subgroup or a B2 section that does not match B1 all load, and every later proof is then rejected by every verifier.  These
+ * three calls take exactly what wsnark_pkey_load, _load_sections and _load_file take -- the key's BYTES, not a handle: after a load
+ * an unreduced coordinate can no longer be seen -- and look at the whole key on the device (no shard parameters).  Nothing calls them
+ * unless the host asks: they change no other call.
+ *   WSNARK_PKCHECK_POINTS     every point of A, B1, C, hExps (G1) and B2 (G2): x == 0 is infinity by the loaders' own rule (counted in
+ *                             infinity[], the rest of its bytes is not read); otherwise every coordinate < q, the curve equation
+ *                             (y^2 = x^3 + 3; on the twist x^3 + 3/(9+u)), and for B2 [r] Q == O.  G1 has cofactor 1: no subgroup
+ *                             test.  bad[], first_bad[], first_reason[] come from a reduction on the device and do not depend on
+ *                             how the sections are cut into chunks.  The five fixed points get the same tests on the host; there
+ *                             infinity (x == 0) is itself bad, reason 4, and as for every point it is decided first.
+ *   WSNARK_PKCHECK_RELATIONS  with the standard generators G1, G2:   bit 0  e(beta1, G2) = e(G1, beta2)
+ *                             bit 1  e(delta1, G2) = e(G1, delta2)    bit 2  e(sum rho_j B1_j, G2) = e(G1, sum rho_j B2_j)
+ *                             rho_j: 128 non-zero bits from seed32 and the index j (ChaCha20 block, key = seed, counter = j).  A
+ *                             relation is run only if every point it involves passed the point tests (or those were not asked
+ *                             for); one that was not run leaves its relations_run bit clear, and then ok = 0.
+ *                             seed32 == NULL: 32 bytes from the OS (getrandom), as the blinding values.  Bit 2 is sound with
+ *                             probability 1 - 2^-128 over a seed that whoever made the key did NOT know: a fixed or published seed
+ *                             gives no soundness.  What the audit cannot see: a permutation applied to B1 and B2 alike, and any
+ *                             relation to the circuit (A, C, hExps against the polynomials): that needs the toxic waste or a
+ *                             verification key.
+ * A bad key is a RESULT: WSNARK_OK with ok = 0.  What the loaders reject (a short section, a bad header, a file that cannot be
+ * opened) fails with the loader's code and writes nothing.  Needs wsnark_init (WSNARK_ERR_NOINIT); callable from any thread, each call
+ * takes a lane of the context.  Sections are streamed through the staging ring in chunks of WSNARK_PKCHECK_CHUNK points (default
+ * 2^18): device memory does not grow with the key, and the file variant hands every staged range back to the kernel. */
+enum { WSNARK_PK_A = 0, WSNARK_PK_B1 = 1, WSNARK_PK_B2 = 2, WSNARK_PK_C = 3, WSNARK_PK_H = 4 };      /* sections in report order */
+/* why a point is bad; when several apply, the smallest number is reported */
+enum { WSNARK_PK_UNREDUCED = 1, WSNARK_PK_OFF_CURVE = 2, WSNARK_PK_OUTSIDE_SUBGROUP = 3, WSNARK_PK_INFINITY = 4 /* fixed points only */ };
+#define WSNARK_PKCHECK_POINTS    1u
+#define WSNARK_PKCHECK_RELATIONS 2u      /* flags == 0 means both */
+typedef struct {
+    uint64_t points[5], infinity[5], bad[5];
+    uint64_t first_bad[5];               /* smallest index of a bad point, UINT64_MAX if none */
+    uint32_t first_reason[5];
+    uint32_t fixed_reason[5];            /* alfa1, beta1, delta1, beta2, delta2: 0 = good */
+    uint32_t relations_run, relations_bad;   /* bit 0: beta1 ~ beta2, bit 1: delta1 ~ delta2, bit 2: B1 ~ B2 */
+    uint32_t ok;                         /* 1 iff nothing is bad and every requested check was run */
+    double   ms[4];                      /* upload + point kernels, relation sums, host pairings, whole call */
+} wsnark_pkey_report_t;
+int wsnark_pkey_check(const void* pkey, size_t len, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out);
+int wsnark_pkey_check_sections(const wsnark_key_sections_t* sections, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out);
+int wsnark_pkey_check_file(const char* path, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out);
 /* which share a handle holds: (0, 1, 0, nVars, domain, 0) for a whole key.  Any out pointer may be NULL. */
 int wsnark_pkey_shard_info(const wsnark_pkey_t* handle, uint32_t* rank, uint32_t* world, uint64_t* first_signal,
                            uint64_t* n_signals, uint64_t* n_hexps, uint32_t* h_interleave_log);

@@ -59,6 +59,49 @@ class _KeySections(C.Structure):   # wsnark_key_sections_t
                 ("pointsH", C.c_void_p), ("pointsH_len", C.c_uint64)]
 
 
+class _KeyReport(C.Structure):     # wsnark_pkey_report_t
+    _fields_ = [("points", C.c_uint64 * 5), ("infinity", C.c_uint64 * 5), ("bad", C.c_uint64 * 5), ("first_bad", C.c_uint64 * 5),
+                ("first_reason", C.c_uint32 * 5), ("fixed_reason", C.c_uint32 * 5),
+                ("relations_run", C.c_uint32), ("relations_bad", C.c_uint32), ("ok", C.c_uint32), ("ms", C.c_double * 4)]
+
+
+KEY_SECTIONS = ("A", "B1", "B2", "C", "H")                                  # report order (WSNARK_PK_A ..)
+KEY_FIXED = ("alfa1", "beta1", "delta1", "beta2", "delta2")
+KEY_RELATIONS = ("beta1~beta2", "delta1~delta2", "B1~B2")                   # bits 0, 1, 2
+KEY_REASONS = {0: None, 1: "unreduced", 2: "off_curve", 3: "outside_subgroup", 4: "infinity"}
+
+
+def _report_dict(r):
+    """wsnark_pkey_report_t as a plain dict: per-section dicts keyed "A", "B1", "B2", "C", "H", then fixed, relations, ok, ms."""
+    out = {}
+    for k, name in enumerate(KEY_SECTIONS):
+        bad = int(r.bad[k])
+        out[name] = {"points": int(r.points[k]), "infinity": int(r.infinity[k]), "bad": bad,
+                     "first_bad": int(r.first_bad[k]) if bad else None, "first_reason": KEY_REASONS[r.first_reason[k]] if bad else None}
+    out["fixed"] = {name: KEY_REASONS[r.fixed_reason[k]] for k, name in enumerate(KEY_FIXED)}
+    out["relations"] = {name: (None if not (r.relations_run >> k) & 1 else not (r.relations_bad >> k) & 1)
+                        for k, name in enumerate(KEY_RELATIONS)}       # None: not run; True: holds; False: violated
+    out["relations_run"], out["relations_bad"] = int(r.relations_run), int(r.relations_bad)
+    out["ok"] = bool(r.ok)
+    out["ms"] = {"points": r.ms[0], "relation_sums": r.ms[1], "pairings": r.ms[2], "total": r.ms[3]}
+    return out
+
+
+def first_finding(report):
+    """One line naming the first thing check_key found in a key that is not ok (None for a good key)."""
+    for name in KEY_SECTIONS:
+        sec = report[name]
+        if sec["bad"]:
+            return "%d bad point(s) in section %s, the first at index %d: %s" % (sec["bad"], name, sec["first_bad"], sec["first_reason"])
+    for name, why in report["fixed"].items():
+        if why:
+            return "%s: %s" % (name, why)
+    for name, holds in report["relations"].items():
+        if holds is False:
+            return "relation %s does not hold" % name
+    return None if report["ok"] else "a requested relation could not be run"
+
+
 class ProvingKey:
     """Device-resident proving key (wsnark_pkey_load, or wsnark_pkey_load_sections for `sections`)."""
 
@@ -405,8 +448,44 @@ class Bn128:
         """Make a point set resident as fixed-base tables (no reference counterpart): see ResidentPoints."""
         return ResidentPoints(self.lib, g, points)
 
-    def load_key(self, pkey=None, sections=None, shard=None, h_interleave_log=0, wait_tables=True, path=None):
+    def load_key(self, pkey=None, sections=None, shard=None, h_interleave_log=0, wait_tables=True, path=None, check=False):
+        """check=True: audit the key first (check_key: every point, the relations, a fresh seed) and raise WsnarkError naming the
+        first finding instead of loading a bad key.  The key's bytes then cross the link twice, audit then load."""
+        if check:
+            rep = self.check_key(pkey=pkey, sections=sections, path=path)
+            if not rep["ok"]:
+                raise _lib.WsnarkError(2, "proving key failed its audit: " + first_finding(rep))
         return ProvingKey(self.lib, pkey, sections, shard, h_interleave_log, wait_tables, path)
+
+    def check_key(self, pkey=None, sections=None, path=None, points=True, relations=True, seed=None):
+        """The audit of a proving key's bytes on the GPU (wsnark_pkey_check / _check_sections / _check_file; no reference
+        counterpart -- snarkjs has `zkey verify`): every point of the five sections and the five fixed points is a reduced,
+        on-curve (B2: order-r) point; beta1 ~ beta2, delta1 ~ delta2 and B1 ~ B2 hold the same discrete logs.  Exactly one of
+        pkey (proving_key.bin bytes), sections (the dict of load_key) and path (a key file).  seed: 32 bytes for the random
+        combination of B1 ~ B2; None draws them from the OS, which is what makes that check sound -- a seed the key's maker
+        could know proves nothing.  Returns a dict: "A", "B1", "B2", "C", "H" -> {points, infinity, bad, first_bad,
+        first_reason}, fixed, relations (True holds / False violated / None not run), ok, ms.  A bad key is a result, not an
+        exception; what load_key rejects (truncated bytes, a bad header) raises WsnarkError as there.  The audit cannot see a
+        permutation applied to B1 and B2 alike, nor whether the points belong to the circuit."""
+        if (pkey is not None) + (sections is not None) + (path is not None) != 1:
+            raise ValueError("check_key: exactly one of pkey, sections, path")
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        flags = (1 if points else 0) | (2 if relations else 0)
+        if not flags:
+            raise ValueError("check_key: nothing to check")
+        sb = _ro(bytes(seed))[0] if seed is not None else None
+        rep = _KeyReport()
+        if path is not None:
+            rc = self.lib.c.wsnark_pkey_check_file(os.fsencode(path), flags, sb, C.byref(rep))
+        elif sections is not None:
+            ks, keep = _key_sections(sections)
+            rc = self.lib.c.wsnark_pkey_check_sections(C.byref(ks), flags, sb, C.byref(rep))
+        else:
+            b, n = _ro(pkey)
+            rc = self.lib.c.wsnark_pkey_check(b, n, flags, sb, C.byref(rep))
+        self.lib.check(rc)
+        return _report_dict(rep)
 
     def key_file_info(self, path):
         """Header of a key file (no GPU work): {n_vars, n_public, domain, file_bytes, format: 'proving_key.bin' | 'WSNARK64'}."""

@@ -49,6 +49,7 @@ int points_msm(ResidentPoints* H, const void* scalars, bool on_device, uint64_t 
 int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
 int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, uint8_t* out, uint64_t n);
 int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
+int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* seed32, wsnark_pkey_report_t* out);
 }  // namespace wsnark
 
 using namespace wsnark;
@@ -291,17 +292,22 @@ int wsnark_groth16_prove_dev(wsnark_pkey_t* h, const void* d_witness, size_t wit
                                      (const uint8_t*)r32, (const uint8_t*)s32, (uint8_t*)out384_host, (hipStream_t)stream);
 }
 
-static int load_sections_entry(const wsnark_key_sections_t* ks, KeyShard shard, wsnark_pkey_t** out_handle) {
-    if (!ks || !out_handle || !ks->alfa1 || !ks->beta1 || !ks->delta1 || !ks->beta2 || !ks->delta2 || !ks->polsA ||
+static int sections_from_abi(const wsnark_key_sections_t* ks, KeySections* S) {
+    if (!ks || !ks->alfa1 || !ks->beta1 || !ks->delta1 || !ks->beta2 || !ks->delta2 || !ks->polsA ||
         !ks->polsB || !ks->pointsA || !ks->pointsB1 || !ks->pointsB2 || !ks->pointsH ||
         (!ks->pointsC && (uint64_t)ks->n_vars > (uint64_t)ks->n_public + 1))
         return WSNARK_ERR_ARG;
-    KeySections S{ks->n_vars, ks->n_public, ks->domain, (const uint8_t*)ks->alfa1, (const uint8_t*)ks->beta1,
-                  (const uint8_t*)ks->delta1, (const uint8_t*)ks->beta2, (const uint8_t*)ks->delta2,
-                  (const uint8_t*)ks->polsA, ks->polsA_len, (const uint8_t*)ks->polsB, ks->polsB_len,
-                  (const uint8_t*)ks->pointsA, (const uint8_t*)ks->pointsB1, (const uint8_t*)ks->pointsB2,
-                  (const uint8_t*)ks->pointsC, (const uint8_t*)ks->pointsH,
-                  ks->pointsA_len, ks->pointsB1_len, ks->pointsB2_len, ks->pointsC_len, ks->pointsH_len};
+    *S = KeySections{ks->n_vars, ks->n_public, ks->domain, (const uint8_t*)ks->alfa1, (const uint8_t*)ks->beta1,
+                     (const uint8_t*)ks->delta1, (const uint8_t*)ks->beta2, (const uint8_t*)ks->delta2,
+                     (const uint8_t*)ks->polsA, ks->polsA_len, (const uint8_t*)ks->polsB, ks->polsB_len,
+                     (const uint8_t*)ks->pointsA, (const uint8_t*)ks->pointsB1, (const uint8_t*)ks->pointsB2,
+                     (const uint8_t*)ks->pointsC, (const uint8_t*)ks->pointsH,
+                     ks->pointsA_len, ks->pointsB1_len, ks->pointsB2_len, ks->pointsC_len, ks->pointsH_len};
+    return WSNARK_OK;
+}
+static int load_sections_entry(const wsnark_key_sections_t* ks, KeyShard shard, wsnark_pkey_t** out_handle) {
+    KeySections S;
+    if (!out_handle || sections_from_abi(ks, &S)) return WSNARK_ERR_ARG;
     ProvingKey* K = nullptr;
     int rc = pkey_load_sections(S, &K, shard);
     if (rc) return rc;
@@ -344,6 +350,30 @@ int wsnark_pkey_file_info(const char* path, uint32_t* n_vars, uint32_t* n_public
     if (file_bytes) *file_bytes = F.len;
     if (format) *format = F.format;
     return WSNARK_OK;
+}
+// ---- the audit of a key's bytes (pkeycheck.hip): what the three loaders take, no handle ----
+int wsnark_pkey_check(const void* pkey, size_t len, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out) {
+    REQUIRE_CTX();
+    if (!out) return WSNARK_ERR_ARG;
+    KeySections S;
+    int rc = pkey_parse((const uint8_t*)pkey, len, &S);
+    if (rc) return rc;
+    return pkey_check_sections(S, flags, (const uint8_t*)seed32, out);
+}
+int wsnark_pkey_check_sections(const wsnark_key_sections_t* ks, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out) {
+    REQUIRE_CTX();
+    KeySections S;
+    if (!out || sections_from_abi(ks, &S)) return WSNARK_ERR_ARG;
+    return pkey_check_sections(S, flags, (const uint8_t*)seed32, out);
+}
+int wsnark_pkey_check_file(const char* path, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out) {
+    REQUIRE_CTX();
+    if (!path || !out) return WSNARK_ERR_ARG;
+    KeyFile F;
+    KeySections S;
+    int rc = keyfile_open(path, &F, &S);      // (S.release: every staged range of the mapping goes back to the kernel)
+    if (rc) return rc;
+    return pkey_check_sections(S, flags, (const uint8_t*)seed32, out);
 }
 int wsnark_pkey_shard_info(const wsnark_pkey_t* h, uint32_t* rank, uint32_t* world, uint64_t* first_signal, uint64_t* n_signals,
                            uint64_t* n_hexps, uint32_t* h_interleave_log) {

@@ -425,7 +425,7 @@ void g2_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out192) { sum_jac<
 // The blinding values' entropy: the reference draws crypto.randomBytes(32) twice (src/bn128.js:642-661).  getrandom(2) -- no file
 // descriptor, works in a chroot without /dev, blocks only until the kernel's pool has been seeded once -- with an UNBUFFERED read
 // of /dev/urandom for kernels without the system call (round 5 pulled 4 KiB through stdio for 64 bytes).
-static int os_random(uint8_t* out, size_t n) {
+int os_random(uint8_t* out, size_t n) {
     size_t got = 0;
 #if defined(__linux__) && defined(SYS_getrandom)
     while (got < n) {

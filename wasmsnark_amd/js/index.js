@@ -60,6 +60,38 @@ function asBytes(x) {
     throw new TypeError("expected an ArrayBuffer, Buffer or TypedArray");
 }
 
+/* wsnark_pkey_report_t (include/wsnark.h, 248 bytes) -> the object checkKey() resolves to: per-section objects keyed A, B1, B2, C,
+ * H ({points, infinity, bad, firstBad, firstReason}), then fixed, relations (true holds / false violated / null not run), ok, ms.
+ * Counts are Numbers (a section has at most 2^27 points). */
+const KEY_SECTIONS = ["A", "B1", "B2", "C", "H"], KEY_FIXED = ["alfa1", "beta1", "delta1", "beta2", "delta2"];
+const KEY_RELATIONS = ["beta1~beta2", "delta1~delta2", "B1~B2"], KEY_REASONS = [null, "unreduced", "off_curve", "outside_subgroup", "infinity"];
+function keyReport(ab) {
+    const v = new DataView(ab);
+    const u64 = (o) => Number(v.getBigUint64(o, true));
+    const out = {};
+    KEY_SECTIONS.forEach((name, k) => {
+        const bad = u64(80 + 8 * k);
+        out[name] = { points: u64(8 * k), infinity: u64(40 + 8 * k), bad, firstBad: bad ? u64(120 + 8 * k) : null,
+                      firstReason: bad ? KEY_REASONS[v.getUint32(160 + 4 * k, true)] : null };
+    });
+    out.fixed = {};
+    KEY_FIXED.forEach((name, k) => { out.fixed[name] = KEY_REASONS[v.getUint32(180 + 4 * k, true)]; });
+    const run = v.getUint32(200, true), bad = v.getUint32(204, true);
+    out.relations = {};
+    KEY_RELATIONS.forEach((name, k) => { out.relations[name] = (run >> k) & 1 ? !((bad >> k) & 1) : null; });
+    out.relationsRun = run;
+    out.relationsBad = bad;
+    out.ok = v.getUint32(208, true) === 1;
+    out.ms = { points: v.getFloat64(216, true), relationSums: v.getFloat64(224, true), pairings: v.getFloat64(232, true), total: v.getFloat64(240, true) };
+    return out;
+}
+function firstFinding(rep) {
+    for (const name of KEY_SECTIONS) if (rep[name].bad) return `${rep[name].bad} bad point(s) in section ${name}, the first at index ${rep[name].firstBad}: ${rep[name].firstReason}`;
+    for (const name of KEY_FIXED) if (rep.fixed[name]) return `${name}: ${rep.fixed[name]}`;
+    for (const name of KEY_RELATIONS) if (rep.relations[name] === false) return `relation ${name} does not hold`;
+    return "a requested relation could not be run";
+}
+
 class Bn128 {
     constructor(deviceInfo, group, devices) {
         this.deviceInfo = deviceInfo;
@@ -102,6 +134,10 @@ class Bn128 {
      * the sampled fingerprint does.  Concurrent callers with the same key object share ONE load: the entry is in the map before it is awaited. */
     async loadKey(pkey, opts) {
         if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (opts && opts.check === true) {           // opt-in: audit the bytes first (they then cross the link twice); the Error carries .report
+            const report = await this.checkKey(pkey);
+            if (!report.ok) throw Object.assign(new Error("wsnark: proving key failed its audit: " + firstFinding(report)), { report });
+        }
         if (typeof pkey === "string") return this._loadKeyFile(pkey);
         if (pkey !== null && typeof pkey === "object" && !(pkey instanceof ArrayBuffer) && !ArrayBuffer.isView(pkey)) return pkey;   // already a handle
         const u8 = asBytes(pkey);
@@ -128,6 +164,22 @@ class Bn128 {
             if (this._keys.get(pkey) === entry) this._keys.delete(pkey);                // a key that failed to parse is not cached
             throw e;
         }
+    }
+    /* No counterpart in the reference (snarkjs: `zkey verify`): the audit of a proving key on the GPU -- every point of the five sections
+     * and the five fixed points is a reduced, on-curve (B2: order-r) point, and beta1 ~ beta2, delta1 ~ delta2, B1 ~ B2 hold the same
+     * discrete logs (include/wsnark.h: wsnark_pkey_check).  pkey: proving_key.bin bytes, or the path of a key file (either format).
+     * opts.points / opts.relations: false leaves that half out; opts.seed: 32 bytes for the random combination of B1 ~ B2 -- by default
+     * drawn from the OS, which is what makes that check sound (a seed the key's maker could know proves nothing).  Resolves to the
+     * report object (keyReport above); a bad key is a result ({ok: false}), not a rejection.  Single GPU only: an object built with
+     * {devices} audits with a one-GPU object first.  The audit cannot see a permutation applied to B1 and B2 alike, nor whether the
+     * points belong to the circuit. */
+    async checkKey(pkey, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: checkKey runs on a single GPU (build a Bn128 without {devices} for the audit)");
+        const flags = (!opts || opts.points !== false ? 1 : 0) | (!opts || opts.relations !== false ? 2 : 0);
+        if (!flags) throw new TypeError("checkKey: nothing to check");
+        if (typeof pkey !== "string") asBytes(pkey);
+        return keyReport(await addon.checkKey(pkey, flags, opts && opts.seed ? opts.seed : null));
     }
     /* A key FILE -- the reference's proving_key.bin or the WSNARK64 container for keys beyond its 4 GiB (js/formats.js:
      * writeKeyContainer; 2^24 constraints = 7.8 GB, more than one Buffer holds).  The library maps the file and reads only what it makes

@@ -63,6 +63,9 @@ static struct {
     int (*pkey_load_file)(const char*, uint32_t, uint32_t, uint32_t, wsnark_pkey_t**);
     int (*pkey_file_info)(const char*, uint32_t*, uint32_t*, uint32_t*, uint64_t*, int*);
     int (*group_pkey_load_file)(wsnark_group_t*, const char*, wsnark_group_pkey_t**);
+    /* the audit of a key's bytes or of a key file (include/wsnark.h: wsnark_pkey_check, wsnark_pkey_report_t) */
+    int (*pkey_check)(const void*, size_t, uint32_t, const void*, void*);
+    int (*pkey_check_file)(const char*, uint32_t, const void*, void*);
     char dir[4096];
 } L;
 
@@ -103,6 +106,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(group_pkey_wait_tables, "wsnark_group_pkey_wait_tables") SYM(group_prove, "wsnark_group_prove")
     SYM(group_last_blinding, "wsnark_group_last_blinding") SYM(group_g1_msm, "wsnark_group_g1_msm") SYM(group_g2_msm, "wsnark_group_g2_msm")
     SYM(pkey_load_file, "wsnark_pkey_load_file") SYM(pkey_file_info, "wsnark_pkey_file_info") SYM(group_pkey_load_file, "wsnark_group_pkey_load_file")
+    SYM(pkey_check, "wsnark_pkey_check") SYM(pkey_check_file, "wsnark_pkey_check_file")
 #undef SYM
     return 0;
 }
@@ -130,7 +134,7 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
-       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH };
+       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -270,6 +274,9 @@ static void job_execute(napi_env env, void* data) {
     case OP_GROUP_LOADKEY_FILE: j->rc = L.group_pkey_load_file(j->gr->g, j->path, &j->gk->k); break;
     case OP_VERIFY: j->rc = L.verify(j->a, j->na, j->b, j->nb / 32, j->c, &j->i0); break;
     case OP_VERIFY_BATCH: j->rc = L.verify_batch(j->a, j->na, j->nb ? j->b : NULL, j->u0, j->c, j->nc / 384, j->out); break;
+    case OP_CHECK_KEY:
+        j->rc = j->path ? L.pkey_check_file(j->path, j->u0, j->r32, j->out) : L.pkey_check(j->a, j->na, j->u0, j->r32, j->out);
+        break;
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
     case OP_GROUP_G1: j->rc = L.group_g1_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
     case OP_GROUP_G2: j->rc = L.group_g2_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
@@ -558,6 +565,27 @@ static napi_value js_verify_batch(napi_env env, napi_callback_info info) {
     if (!j->out) FAIL(env, j, "out of memory");
     keep(env, j, argv[0]); keep(env, j, argv[1]); keep(env, j, argv[2]);
     return start_job(env, j, "wsnark_groth16_verify_batch");
+}
+
+/* checkKey(pkeyBytes | path, flags, seed32 | null) -> Promise<ArrayBuffer 248>: the wsnark_pkey_report_t of the audit (include/wsnark.h:
+ * wsnark_pkey_check / wsnark_pkey_check_file; index.js turns it into an object).  flags: 1 points, 2 relations, 0 both. */
+#define PKEY_REPORT_BYTES 248
+static napi_value js_check_key(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CHECK_KEY;
+    if (argc < 2 || (!(j->path = get_path(env, argv[0])) && !get_bytes(env, argv[0], &j->a, &j->na)) ||
+        napi_get_value_uint32(env, argv[1], &j->u0) != napi_ok)
+        FAIL(env, j, "expected (proving_key.bin bytes | key file path, flags[, seed32])");
+    size_t ns = 0;
+    if (argc > 2 && get_bytes(env, argv[2], &j->r32, &ns) && ns != 32) FAIL(env, j, "the seed must be 32 bytes");
+    j->nout = PKEY_REPORT_BYTES;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    if (!j->path) keep(env, j, argv[0]);
+    if (j->r32) keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_pkey_check");
 }
 
 /* allocPinned(bytes) -> ArrayBuffer over pinned host memory (wsnark_host_alloc): a witness written into it is DMA'd in place,
@@ -878,6 +906,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"waitTables", NULL, js_wait_tables, NULL, NULL, NULL, napi_default, NULL},
         {"verify", NULL, js_verify, NULL, NULL, NULL, napi_default, NULL},
         {"verifyBatch", NULL, js_verify_batch, NULL, NULL, NULL, napi_default, NULL},
+        {"checkKey", NULL, js_check_key, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},
