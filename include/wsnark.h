@@ -245,6 +245,76 @@ typedef struct {
 int wsnark_pkey_check(const void* pkey, size_t len, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out);
 int wsnark_pkey_check_sections(const wsnark_key_sections_t* sections, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out);
 int wsnark_pkey_check_file(const char* path, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out);
+/* ---- the phase-2 contribution to a key's delta, and its check (csrc/pkeydelta.hip; snarkjs: `zkey contribute` / `zkey verify`) ----
+ * Nobody should deploy a key whose delta is known to whoever ran the setup.  A contribution by a secret d (non-zero mod r) turns a
+ * key with C_j = (.../delta) G1, hExps_i = (tau^i Z(tau)/delta) G1, delta1 = delta G1, delta2 = delta G2 into the same key under
+ * delta d:   delta1' = d delta1, delta2' = d delta2 (host)     C'_j = d^-1 C_j, hExps'_i = d^-1 hExps_i (device, one lane per point)
+ * and leaves everything else -- header, alfa1, beta1, beta2, polsA, polsB, A, B1, B2 -- byte for byte as it was.  A point with
+ * x == 0 is infinity by the loaders' rule and is copied through byte for byte.
+ *   wsnark_g{1,2}_scale_batch   out[i] = k * points[i]; affine Montgomery in and out, x == 0 is infinity (copied through); k: 32 bytes
+ *                             plain LE, reduced mod r; a result at infinity is written as zeros.  The counterpart of
+ *                             wsnark_g{1,2}_mul_base_batch (one base, many scalars): many bases, ONE scalar.  Every input gets the
+ *                             audit's two cheap tests (coordinates < q, the curve equation; NOT the G2 subgroup test): a bad point
+ *                             fails the call with WSNARK_ERR_FORMAT (wsnark_last_error names the first index), out is then unspecified.
+ *   d32                       32 bytes plain little-endian, reduced mod r; d = 0 mod r is WSNARK_ERR_ARG.  d32 == NULL draws the 32
+ *                             bytes from the OS (getrandom), as the blinding values: the production case.  The library never returns
+ *                             the secret and wipes d, d^-1 and the digit string of d^-1 (volatile stores) before it returns; the
+ *                             digits also cross to the device in the kernels' argument blocks, which the runtime owns.  With an
+ *                             explicit d32 the call is deterministic.
+ *   a bad input is a RESULT   as in the audit: WSNARK_OK with ok = 0 for a C or hExps point with a coordinate >= q or off the curve
+ *                             (bad[], first_bad[], first_reason[]: reduced on the device as the audit's, independent of the chunking)
+ *                             and for a delta1 or delta2 that fails the audit's fixed-point tests (then no section is looked at and
+ *                             the counts stay 0).  With ok = 0 the output buffers are unspecified; the file variant removes its output.
+ *   errors                    what the loaders reject (a short section, a bad header, a file that cannot be opened) fails with the
+ *                             loader's code before anything is written, as wsnark_pkey_check does; out_cap < len is WSNARK_ERR_SIZE;
+ *                             in_path and out_path naming one file is WSNARK_ERR_ARG; before wsnark_init WSNARK_ERR_NOINIT.  A report
+ *                             that was not produced is left untouched.
+ *   streaming                 C and hExps go through the staging ring in chunks of WSNARK_PKDELTA_CHUNK points (default 2^18, clamped
+ *                             to [64, 2^22] as WSNARK_PKCHECK_CHUNK): a chunk goes up, is scaled, and comes down, the next chunk's
+ *                             upload beside this chunk's kernel; device memory does not grow with the key.  The file variant maps
+ *                             the input read-only, writes the output in the input's format (proving_key.bin or WSNARK64, also above
+ *                             4 GiB) and hands every range it has read back to the kernel.  Each call takes a lane of the context;
+ *                             nothing else calls these functions and no other entry point changes.
+ *                             out_pkey may not overlap pkey unless it IS pkey (in place).
+ * wsnark_pkey_delta_verify*: what the next participant runs on (old key, new key).
+ *   bit 0  everything but C, hExps, delta1, delta2 is byte-identical: a host memcmp of nVars, nPublic, domainSize, alfa1, beta1,
+ *          beta2, both record streams, A, B1, B2.  If the counts or the streams' lengths differ the bit is bad and bits 2, 3 are not run.
+ *   bit 1  e(delta1', G2) = e(G1, delta2'); run only if both new points pass the audit's fixed-point tests.
+ *   bit 2  e(sum rho_j C'_j, delta2') = e(sum rho_j C_j, delta2)      bit 3  the same for hExps.  rho_j as in the audit (ChaCha20,
+ *          key = seed32, counter = the global index j), the SAME for the old and the new point j; the sums run chunk by chunk through
+ *          the ordinary G1 MSM, partial sums added on the host.  Run only if bit 1 ran and held -- that is what makes them mean
+ *          something: C' = c C and delta2' = c' delta2 pass iff c c' = 1.
+ *   bit 4  delta2' != delta2 (a contribution by 1 is none).
+ *   seed32 == NULL: 32 bytes from the OS.  As in the audit, bits 2 and 3 are sound with probability 1 - 2^-128 over a seed the
+ *   contributor did NOT know; a fixed or published seed gives no soundness.
+ *   The check does NOT test individual points -- that is wsnark_pkey_check's job: run the audit on the new key first.  Unreduced
+ *   or off-curve bytes do not fault it, they only make the sums meaningless, as in the prover.
+ * Out of scope: a transcript of contributions, the proof of knowledge of d that snarkjs stores with each of them, a random
+ * beacon, and anything that touches the circuit. */
+int wsnark_g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out_affine);
+int wsnark_g2_scale_batch(const void* points, uint64_t n, const void* k32, void* out_affine);
+typedef struct {
+    uint64_t points[2], infinity[2], bad[2];   /* [0] = C, [1] = hExps */
+    uint64_t first_bad[2];                      /* UINT64_MAX if none */
+    uint32_t first_reason[2];                   /* WSNARK_PK_UNREDUCED / WSNARK_PK_OFF_CURVE */
+    uint32_t ok;                                /* 1 iff no bad point and delta1, delta2 passed the audit's fixed-point tests */
+    double   ms[3];                             /* device (upload + kernels + download), host (delta1', delta2', copies), whole call */
+} wsnark_pkey_delta_report_t;
+int wsnark_pkey_contribute(const void* pkey, size_t len, const void* d32, void* out_pkey, size_t out_cap, wsnark_pkey_delta_report_t* rep);
+int wsnark_pkey_contribute_sections(const wsnark_key_sections_t* in, const void* d32,
+                                    void* out_pointsC, void* out_pointsH, void* out_delta1_64, void* out_delta2_128,
+                                    wsnark_pkey_delta_report_t* rep);
+int wsnark_pkey_contribute_file(const char* in_path, const char* out_path, const void* d32, wsnark_pkey_delta_report_t* rep);
+typedef struct {
+    uint32_t checks_run, checks_bad;   /* bits 0..4 as above */
+    uint32_t ok;                       /* 1 iff all five ran and none is bad */
+    double   ms[3];                    /* sums, pairings, whole call */
+} wsnark_pkey_delta_verdict_t;
+int wsnark_pkey_delta_verify(const void* old_pkey, size_t old_len, const void* new_pkey, size_t new_len, const void* seed32,
+                             wsnark_pkey_delta_verdict_t* out);
+int wsnark_pkey_delta_verify_sections(const wsnark_key_sections_t* old_key, const wsnark_key_sections_t* new_key, const void* seed32,
+                                      wsnark_pkey_delta_verdict_t* out);
+int wsnark_pkey_delta_verify_file(const char* old_path, const char* new_path, const void* seed32, wsnark_pkey_delta_verdict_t* out);
 /* which share a handle holds: (0, 1, 0, nVars, domain, 0) for a whole key.  Any out pointer may be NULL. */
 int wsnark_pkey_shard_info(const wsnark_pkey_t* handle, uint32_t* rank, uint32_t* world, uint64_t* first_signal,
                            uint64_t* n_signals, uint64_t* n_hexps, uint32_t* h_interleave_log);

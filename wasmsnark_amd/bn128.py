@@ -87,6 +87,36 @@ def _report_dict(r):
     return out
 
 
+class _DeltaReport(C.Structure):   # wsnark_pkey_delta_report_t
+    _fields_ = [("points", C.c_uint64 * 2), ("infinity", C.c_uint64 * 2), ("bad", C.c_uint64 * 2), ("first_bad", C.c_uint64 * 2),
+                ("first_reason", C.c_uint32 * 2), ("ok", C.c_uint32), ("ms", C.c_double * 3)]
+
+
+class _DeltaVerdict(C.Structure):  # wsnark_pkey_delta_verdict_t
+    _fields_ = [("checks_run", C.c_uint32), ("checks_bad", C.c_uint32), ("ok", C.c_uint32), ("ms", C.c_double * 3)]
+
+
+DELTA_CHECKS = ("unchanged", "delta1~delta2", "C", "H", "delta_changed")    # bits 0..4 of wsnark_pkey_delta_verdict_t
+
+
+def _delta_report_dict(r):
+    out = {}
+    for k, name in enumerate(("C", "H")):
+        bad = int(r.bad[k])
+        out[name] = {"points": int(r.points[k]), "infinity": int(r.infinity[k]), "bad": bad,
+                     "first_bad": int(r.first_bad[k]) if bad else None, "first_reason": KEY_REASONS[r.first_reason[k]] if bad else None}
+    out["ok"] = bool(r.ok)
+    out["ms"] = {"device": r.ms[0], "host": r.ms[1], "total": r.ms[2]}
+    return out
+
+
+def _delta_verdict_dict(v):
+    out = {"checks": {name: (None if not (v.checks_run >> k) & 1 else not (v.checks_bad >> k) & 1) for k, name in enumerate(DELTA_CHECKS)},
+           "checks_run": int(v.checks_run), "checks_bad": int(v.checks_bad), "ok": bool(v.ok),
+           "ms": {"sums": v.ms[0], "pairings": v.ms[1], "total": v.ms[2]}}
+    return out
+
+
 def first_finding(report):
     """One line naming the first thing check_key found in a key that is not ok (None for a good key)."""
     for name in KEY_SECTIONS:
@@ -486,6 +516,85 @@ class Bn128:
             rc = self.lib.c.wsnark_pkey_check(b, n, flags, sb, C.byref(rep))
         self.lib.check(rc)
         return _report_dict(rep)
+
+    # --- the phase-2 delta contribution (csrc/pkeydelta.hip; no reference counterpart -- snarkjs: zkey contribute / zkey verify) ---
+    def scale_points(self, g, points, k):
+        """k * P for every point of `points` (affine Montgomery, 64 bytes each for g = 1, 128 for g = 2; x == 0 is infinity and is
+        copied through) and ONE scalar k (an int, or 32 bytes plain LE; reduced mod r): wsnark_g{1,2}_scale_batch."""
+        p, nb = _ro(points)
+        sz = 64 if g == 1 else 128
+        if nb % sz:
+            raise ValueError("points: not a whole number of %d-byte points" % sz)
+        kb = int(k).to_bytes(32, "little") if isinstance(k, int) else bytes(k)
+        if len(kb) != 32:
+            raise ValueError("k must be 32 bytes")
+        out = (C.c_uint8 * max(nb, 1))()
+        fn = self.lib.c.wsnark_g1_scale_batch if g == 1 else self.lib.c.wsnark_g2_scale_batch
+        self.lib.check(fn(p, nb // sz, kb, out))
+        return bytes(out)[:nb]
+
+    def contribute_key(self, pkey=None, sections=None, path=None, out_path=None, d=None):
+        """One phase-2 contribution: the same key under delta * d.  Exactly one of pkey (proving_key.bin bytes), sections (the
+        dict of load_key) and path (a key file, with out_path: the new file, same format).  d: 32 bytes plain LE (or an int),
+        non-zero mod r -- for tests; None draws it from the OS inside the library, which never returns it and wipes it: the
+        production case.  Returns (new key in the form it was given -- bytes, a sections dict, or out_path --, report dict with
+        "C", "H" -> {points, infinity, bad, first_bad, first_reason}, ok, ms).  A bad input point, or a delta1 / delta2 that fails
+        the audit's fixed-point tests, is a result: ok is False and the returned key is None."""
+        if (pkey is not None) + (sections is not None) + (path is not None) != 1:
+            raise ValueError("contribute_key: exactly one of pkey, sections, path")
+        if (path is not None) != (out_path is not None):
+            raise ValueError("contribute_key: out_path goes with path")
+        db = None
+        if d is not None:
+            db = int(d).to_bytes(32, "little") if isinstance(d, int) else bytes(d)
+            if len(db) != 32:
+                raise ValueError("d must be 32 bytes")
+        rep = _DeltaReport()
+        if path is not None:
+            self.lib.check(self.lib.c.wsnark_pkey_contribute_file(os.fsencode(path), os.fsencode(out_path), db, C.byref(rep)))
+            new = out_path
+        elif sections is not None:
+            ks, keep = _key_sections(sections)
+            nC = max(sections["n_vars"] - sections["n_public"] - 1, 0)
+            oc, oh = (C.c_uint8 * max(nC * 64, 1))(), (C.c_uint8 * (sections["domain"] * 64))()
+            d1, d2 = (C.c_uint8 * 64)(), (C.c_uint8 * 128)()
+            self.lib.check(self.lib.c.wsnark_pkey_contribute_sections(C.byref(ks), db, oc, oh, d1, d2, C.byref(rep)))
+            new = dict(sections, pointsC=bytes(oc)[:nC * 64], pointsH=bytes(oh), delta1=bytes(d1), delta2=bytes(d2))
+        else:
+            b, n = _ro(pkey)
+            out = (C.c_uint8 * max(n, 1))()
+            self.lib.check(self.lib.c.wsnark_pkey_contribute(b, n, db, out, n, C.byref(rep)))
+            new = bytes(out)[:n]
+        report = _delta_report_dict(rep)
+        return (new if report["ok"] else None), report
+
+    def verify_contribution(self, old, new, seed=None, check=True):
+        """Is `new` exactly `old` under another delta?  (wsnark_pkey_delta_verify*.)  old, new: both proving_key.bin bytes, both
+        sections dicts, or both paths of key files.  seed: as check_key's -- None draws it from the OS, which is what makes the two
+        random combinations sound.  check=True first audits the new key (check_key) and raises WsnarkError with the audit's message
+        if that fails: the relation check itself looks at no single point.  Returns {checks: {unchanged, delta1~delta2, C, H,
+        delta_changed -> True holds / False violated / None not run}, checks_run, checks_bad, ok, ms}."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        kind = lambda k: "sections" if isinstance(k, dict) else "path" if isinstance(k, (str, os.PathLike)) else "pkey"
+        if kind(old) != kind(new):
+            raise ValueError("verify_contribution: old and new must be given in the same form")
+        if check:
+            rep = self.check_key(**{kind(new): new})
+            if not rep["ok"]:
+                raise _lib.WsnarkError(2, "proving key failed its audit: " + first_finding(rep))
+        sb = _ro(bytes(seed))[0] if seed is not None else None
+        v = _DeltaVerdict()
+        if kind(old) == "path":
+            rc = self.lib.c.wsnark_pkey_delta_verify_file(os.fsencode(old), os.fsencode(new), sb, C.byref(v))
+        elif kind(old) == "sections":
+            (ko, keep_o), (kn, keep_n) = _key_sections(old), _key_sections(new)
+            rc = self.lib.c.wsnark_pkey_delta_verify_sections(C.byref(ko), C.byref(kn), sb, C.byref(v))
+        else:
+            (bo, no), (bn_, nn) = _ro(old), _ro(new)
+            rc = self.lib.c.wsnark_pkey_delta_verify(bo, no, bn_, nn, sb, C.byref(v))
+        self.lib.check(rc)
+        return _delta_verdict_dict(v)
 
     def key_file_info(self, path):
         """Header of a key file (no GPU work): {n_vars, n_public, domain, file_bytes, format: 'proving_key.bin' | 'WSNARK64'}."""

@@ -50,6 +50,13 @@ int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t*
 int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, uint8_t* out, uint64_t n);
 int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
 int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* seed32, wsnark_pkey_report_t* out);
+int g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
+int g2_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
+int pkey_contribute_sections(const KeySections& S, const uint8_t* d32, uint8_t* out_pointsC, uint8_t* out_pointsH, uint8_t* out_delta1,
+                             uint8_t* out_delta2, wsnark_pkey_delta_report_t* rep);
+int pkey_contribute_bytes(const uint8_t* pkey, size_t len, const uint8_t* d32, uint8_t* out, size_t out_cap, wsnark_pkey_delta_report_t* rep);
+int pkey_contribute_file(const char* in_path, const char* out_path, const uint8_t* d32, wsnark_pkey_delta_report_t* rep);
+int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const uint8_t* seed32, wsnark_pkey_delta_verdict_t* out);
 }  // namespace wsnark
 
 using namespace wsnark;
@@ -58,6 +65,7 @@ static_assert(sizeof(Fe) == 32, "field element must be 32 bytes");
 static_assert(sizeof(Affine<Fq>) == 64 && sizeof(Affine<Fq2>) == 128, "affine layouts");
 static_assert(sizeof(Jac<Fq>) == 96 && sizeof(Jac<Fq2>) == 192, "jacobian layouts");
 static_assert(sizeof(XYZZ<Fq>) == 128 && sizeof(XYZZ<Fq2>) == 256, "xyzz layouts");
+static_assert(sizeof(wsnark_pkey_delta_report_t) == 104 && sizeof(wsnark_pkey_delta_verdict_t) == 40, "the bindings read these by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
 // addon runs on the libuv pool): select the context's device first.
@@ -374,6 +382,58 @@ int wsnark_pkey_check_file(const char* path, uint32_t flags, const void* seed32,
     int rc = keyfile_open(path, &F, &S);      // (S.release: every staged range of the mapping goes back to the kernel)
     if (rc) return rc;
     return pkey_check_sections(S, flags, (const uint8_t*)seed32, out);
+}
+// ---- the phase-2 delta contribution and its check (pkeydelta.hip) ----
+int wsnark_g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out_affine) {
+    REQUIRE_CTX();
+    return g1_scale_batch(points, n, k32, out_affine);
+}
+int wsnark_g2_scale_batch(const void* points, uint64_t n, const void* k32, void* out_affine) {
+    REQUIRE_CTX();
+    return g2_scale_batch(points, n, k32, out_affine);
+}
+int wsnark_pkey_contribute(const void* pkey, size_t len, const void* d32, void* out_pkey, size_t out_cap, wsnark_pkey_delta_report_t* rep) {
+    REQUIRE_CTX();
+    return pkey_contribute_bytes((const uint8_t*)pkey, len, (const uint8_t*)d32, (uint8_t*)out_pkey, out_cap, rep);
+}
+int wsnark_pkey_contribute_sections(const wsnark_key_sections_t* in, const void* d32, void* out_pointsC, void* out_pointsH,
+                                    void* out_delta1_64, void* out_delta2_128, wsnark_pkey_delta_report_t* rep) {
+    REQUIRE_CTX();
+    KeySections S;
+    if (!rep || sections_from_abi(in, &S)) return WSNARK_ERR_ARG;
+    return pkey_contribute_sections(S, (const uint8_t*)d32, (uint8_t*)out_pointsC, (uint8_t*)out_pointsH, (uint8_t*)out_delta1_64,
+                                    (uint8_t*)out_delta2_128, rep);
+}
+int wsnark_pkey_contribute_file(const char* in_path, const char* out_path, const void* d32, wsnark_pkey_delta_report_t* rep) {
+    REQUIRE_CTX();
+    return pkey_contribute_file(in_path, out_path, (const uint8_t*)d32, rep);
+}
+int wsnark_pkey_delta_verify(const void* old_pkey, size_t old_len, const void* new_pkey, size_t new_len, const void* seed32,
+                             wsnark_pkey_delta_verdict_t* out) {
+    REQUIRE_CTX();
+    if (!out) return WSNARK_ERR_ARG;
+    KeySections O, N;
+    int rc = pkey_parse((const uint8_t*)old_pkey, old_len, &O);
+    if (!rc) rc = pkey_parse((const uint8_t*)new_pkey, new_len, &N);
+    if (rc) return rc;
+    return pkey_delta_verify_sections(O, N, (const uint8_t*)seed32, out);
+}
+int wsnark_pkey_delta_verify_sections(const wsnark_key_sections_t* old_key, const wsnark_key_sections_t* new_key, const void* seed32,
+                                      wsnark_pkey_delta_verdict_t* out) {
+    REQUIRE_CTX();
+    KeySections O, N;
+    if (!out || sections_from_abi(old_key, &O) || sections_from_abi(new_key, &N)) return WSNARK_ERR_ARG;
+    return pkey_delta_verify_sections(O, N, (const uint8_t*)seed32, out);
+}
+int wsnark_pkey_delta_verify_file(const char* old_path, const char* new_path, const void* seed32, wsnark_pkey_delta_verdict_t* out) {
+    REQUIRE_CTX();
+    if (!old_path || !new_path || !out) return WSNARK_ERR_ARG;
+    KeyFile FO, FN;
+    KeySections O, N;
+    int rc = keyfile_open(old_path, &FO, &O);
+    if (!rc) rc = keyfile_open(new_path, &FN, &N);
+    if (rc) return rc;
+    return pkey_delta_verify_sections(O, N, (const uint8_t*)seed32, out);
 }
 int wsnark_pkey_shard_info(const wsnark_pkey_t* h, uint32_t* rank, uint32_t* world, uint64_t* first_signal, uint64_t* n_signals,
                            uint64_t* n_hexps, uint32_t* h_interleave_log) {

@@ -48,9 +48,11 @@ static int mul_base_host(const void* base, const void* scalars, uint64_t n, void
     WS_HIP_CHECK(ds.alloc(n * 32));
     WS_HIP_CHECK(dout.alloc(n * sizeof(typename C::Aff)));
     WS_HIP_CHECK(hipMemcpyAsync(ds.p, scalars, n * 32, hipMemcpyHostToDevice, X->stream));
+    X->timer.begin(sizeof(typename C::Aff) == 64 ? "mul_base_g1" : "mul_base_g2", X->stream);      // (a no-op unless timing is on)
     hipLaunchKernelGGL(mul_base_kernel<C>, dim3(ceil_div_u64(n, 256)), dim3(256), 0, X->stream, b, ds.as<Fe>(), n,
                        dout.as<typename C::Aff>());
     WS_HIP_CHECK(hipGetLastError());
+    X->timer.end(X->stream);
     WS_HIP_CHECK(hipMemcpyAsync(out, dout.p, n * sizeof(typename C::Aff), hipMemcpyDeviceToHost, X->stream));
     WS_HIP_CHECK(hipStreamSynchronize(X->stream));
     return WS_OK;

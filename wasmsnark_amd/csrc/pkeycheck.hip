@@ -33,6 +33,7 @@
 #include "internal.h"
 #include "fp12.h"
 #include "fp12_host.h"
+#include "pkeycheck.h"
 
 namespace wsnark {
 
@@ -44,31 +45,6 @@ int os_random(uint8_t* out, size_t n);      // prove.hip: getrandom(2), else /de
 
 // ---- device ----
 typedef G2R29 G2c;                          // Curve<Fp2T<Fq29>>: products as calls, as in pairing.hip (the chain is ~12 000 of them)
-
-// one section's running result; `first` holds ~(index << 3 | reason) of the smallest bad index (0 = none) so that atomicMax finds
-// the minimum
-struct PkAcc { unsigned long long inf, bad, first; };
-
-struct PkSeed { uint32_t w[8]; };
-
-__device__ inline bool pk_ge(const Fe& x, const uint64_t* m) {        // x >= m
-    for (int i = 3; i >= 0; i--) {
-        if (x.l[i] > m[i]) return true;
-        if (x.l[i] < m[i]) return false;
-    }
-    return true;
-}
-__device__ inline bool pk_zero(const Fe& x) { return (x.l[0] | x.l[1] | x.l[2] | x.l[3]) == 0; }
-
-// st: 0 good, 1..3 the reason, 4 infinity.  Every lane of the wavefront arrives here (lanes past the end with st = 0).
-__device__ inline void pk_reduce(int st, uint64_t index, PkAcc* __restrict__ acc) {
-    const unsigned long long m_inf = __ballot(st == 4), m_bad = __ballot(st >= 1 && st <= 3);
-    if ((threadIdx.x & 63) == 0) {
-        if (m_inf) atomicAdd(&acc->inf, (unsigned long long)__popcll(m_inf));
-        if (m_bad) atomicAdd(&acc->bad, (unsigned long long)__popcll(m_bad));
-    }
-    if (st >= 1 && st <= 3) atomicMax(&acc->first, ~(((unsigned long long)index << 3) | (unsigned long long)st));
-}
 
 __global__ __launch_bounds__(256) void pkcheck_g1_kernel(const Fe* __restrict__ pts, uint64_t n, uint64_t base,
                                                            const PairConsts* __restrict__ K, PkAcc* __restrict__ acc) {
@@ -169,6 +145,13 @@ __global__ __launch_bounds__(256) void pkcheck_rho_kernel(Fe* __restrict__ out, 
     out[i] = Fe{{lo, hi, 0, 0}};
 }
 #undef PK_QR
+int pkcheck_rho_dev(Fe* d_out, uint64_t n, uint64_t base, const uint8_t* seed32, hipStream_t s) {
+    PkSeed sd;
+    memcpy(sd.w, seed32, 32);
+    hipLaunchKernelGGL(pkcheck_rho_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_out, n, base, sd);
+    WS_HIP_CHECK(hipGetLastError());
+    return WS_OK;
+}
 
 // ---- host: the five fixed points and the pairings ----
 namespace {
@@ -184,6 +167,7 @@ bool h_reduced(const Fe& x) {
     }
     return false;
 }
+}  // namespace
 // reference-format bytes -> the host pairing's point; the reason it is bad (0 = good).  check = false: only the infinity rule
 uint32_t fixed_g1(const uint8_t* p, bool check, G1A* out) {
     memcpy(&out->x, p, 32);
@@ -223,7 +207,6 @@ bool same_log(const G1A& P, const G2A& Q) {
     if (!miller_ate(gen2(), P, &m1) || !miller_ate(Q, ng, &m2)) return false;      // (a degenerate step: Q is not of order r)
     return f12_is_one(final_exponentiation(f12_mul(m1, m2)));
 }
-}  // namespace
 
 int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* seed32, wsnark_pkey_report_t* out) {
     Context* X = ctx();

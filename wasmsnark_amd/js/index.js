@@ -85,6 +85,29 @@ function keyReport(ab) {
     out.ms = { points: v.getFloat64(216, true), relationSums: v.getFloat64(224, true), pairings: v.getFloat64(232, true), total: v.getFloat64(240, true) };
     return out;
 }
+/* wsnark_pkey_delta_report_t (104 bytes) and wsnark_pkey_delta_verdict_t (40 bytes) -> the objects of contributeKey() / verifyContribution() */
+const DELTA_CHECKS = ["unchanged", "delta1~delta2", "C", "H", "delta_changed"];
+function deltaReport(ab) {
+    const v = new DataView(ab, 0, 104);
+    const u64 = (o) => Number(v.getBigUint64(o, true));
+    const out = {};
+    ["C", "H"].forEach((name, k) => {
+        const bad = u64(32 + 8 * k);
+        out[name] = { points: u64(8 * k), infinity: u64(16 + 8 * k), bad, firstBad: bad ? u64(48 + 8 * k) : null,
+                      firstReason: bad ? KEY_REASONS[v.getUint32(64 + 4 * k, true)] : null };
+    });
+    out.ok = v.getUint32(72, true) === 1;
+    out.ms = { device: v.getFloat64(80, true), host: v.getFloat64(88, true), total: v.getFloat64(96, true) };
+    return out;
+}
+function deltaVerdict(ab) {
+    const v = new DataView(ab);
+    const run = v.getUint32(0, true), bad = v.getUint32(4, true);
+    const out = { checks: {}, checksRun: run, checksBad: bad, ok: v.getUint32(8, true) === 1,
+                  ms: { sums: v.getFloat64(16, true), pairings: v.getFloat64(24, true), total: v.getFloat64(32, true) } };
+    DELTA_CHECKS.forEach((name, k) => { out.checks[name] = (run >> k) & 1 ? !((bad >> k) & 1) : null; });
+    return out;
+}
 function firstFinding(rep) {
     for (const name of KEY_SECTIONS) if (rep[name].bad) return `${rep[name].bad} bad point(s) in section ${name}, the first at index ${rep[name].firstBad}: ${rep[name].firstReason}`;
     for (const name of KEY_FIXED) if (rep.fixed[name]) return `${name}: ${rep.fixed[name]}`;
@@ -180,6 +203,37 @@ class Bn128 {
         if (!flags) throw new TypeError("checkKey: nothing to check");
         if (typeof pkey !== "string") asBytes(pkey);
         return keyReport(await addon.checkKey(pkey, flags, opts && opts.seed ? opts.seed : null));
+    }
+    /* No counterpart in the reference (snarkjs: `zkey contribute`): one phase-2 contribution -- the same key under delta * d, with
+     * C and hExps scaled by 1/d on the GPU (include/wsnark.h: wsnark_pkey_contribute).  key: proving_key.bin bytes, or the path of a key
+     * file (either format) together with opts.outPath, the new file.  opts.entropy: 32 bytes plain LE used as d (tests); by default the
+     * library draws d from the OS, never returns it and wipes it.  Resolves to {key: the new key's ArrayBuffer, or outPath; report}; a bad
+     * input point is a result ({key: null, report: {ok: false, ...}}), not a rejection. */
+    async contributeKey(key, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: contributeKey runs on a single GPU (build a Bn128 without {devices})");
+        const isPath = typeof key === "string";
+        if (!isPath) asBytes(key);
+        if (isPath !== !!(opts && opts.outPath)) throw new TypeError("contributeKey: outPath goes with a key file path");
+        const ab = await addon.contributeKey(key, isPath ? opts.outPath : null, opts && opts.entropy ? opts.entropy : null);
+        const report = deltaReport(ab);
+        return { key: !report.ok ? null : isPath ? opts.outPath : ab.slice(104), report };
+    }
+    /* What the next participant runs: is newKey exactly oldKey under another delta (include/wsnark.h: wsnark_pkey_delta_verify)?  Both
+     * keys as bytes, or both as file paths.  opts.seed: 32 bytes for the two random combinations, by default from the OS (a seed the
+     * contributor could know proves nothing); opts.check !== false audits the new key first (checkKey) and rejects with the audit's
+     * message and .report if that fails -- the relation check itself looks at no single point.  Resolves to {checks: {unchanged,
+     * "delta1~delta2", C, H, delta_changed: true holds / false violated / null not run}, checksRun, checksBad, ok, ms}. */
+    async verifyContribution(oldKey, newKey, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: verifyContribution runs on a single GPU (build a Bn128 without {devices})");
+        if ((typeof oldKey === "string") !== (typeof newKey === "string")) throw new TypeError("verifyContribution: both keys as bytes, or both as paths");
+        if (typeof oldKey !== "string") { asBytes(oldKey); asBytes(newKey); }
+        if (!opts || opts.check !== false) {
+            const report = await this.checkKey(newKey);
+            if (!report.ok) throw Object.assign(new Error("wsnark: proving key failed its audit: " + firstFinding(report)), { report });
+        }
+        return deltaVerdict(await addon.deltaVerify(oldKey, newKey, opts && opts.seed ? opts.seed : null));
     }
     /* A key FILE -- the reference's proving_key.bin or the WSNARK64 container for keys beyond its 4 GiB (js/formats.js:
      * writeKeyContainer; 2^24 constraints = 7.8 GB, more than one Buffer holds).  The library maps the file and reads only what it makes

@@ -66,6 +66,11 @@ static struct {
     /* the audit of a key's bytes or of a key file (include/wsnark.h: wsnark_pkey_check, wsnark_pkey_report_t) */
     int (*pkey_check)(const void*, size_t, uint32_t, const void*, void*);
     int (*pkey_check_file)(const char*, uint32_t, const void*, void*);
+    /* the phase-2 delta contribution and its check (include/wsnark.h: wsnark_pkey_contribute*, wsnark_pkey_delta_verify*) */
+    int (*pkey_contribute)(const void*, size_t, const void*, void*, size_t, void*);
+    int (*pkey_contribute_file)(const char*, const char*, const void*, void*);
+    int (*pkey_delta_verify)(const void*, size_t, const void*, size_t, const void*, void*);
+    int (*pkey_delta_verify_file)(const char*, const char*, const void*, void*);
     char dir[4096];
 } L;
 
@@ -107,6 +112,8 @@ static int load_lib(char* err, size_t errlen) {
     SYM(group_last_blinding, "wsnark_group_last_blinding") SYM(group_g1_msm, "wsnark_group_g1_msm") SYM(group_g2_msm, "wsnark_group_g2_msm")
     SYM(pkey_load_file, "wsnark_pkey_load_file") SYM(pkey_file_info, "wsnark_pkey_file_info") SYM(group_pkey_load_file, "wsnark_group_pkey_load_file")
     SYM(pkey_check, "wsnark_pkey_check") SYM(pkey_check_file, "wsnark_pkey_check_file")
+    SYM(pkey_contribute, "wsnark_pkey_contribute") SYM(pkey_contribute_file, "wsnark_pkey_contribute_file")
+    SYM(pkey_delta_verify, "wsnark_pkey_delta_verify") SYM(pkey_delta_verify_file, "wsnark_pkey_delta_verify_file")
 #undef SYM
     return 0;
 }
@@ -134,7 +141,7 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
-       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY };
+       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -187,6 +194,7 @@ typedef struct {
     uint8_t* out;
     size_t nout;
     char* path;                 /* key file (OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE): owned by the job */
+    char* path2;                /* the second file of OP_CONTRIBUTE (output) / OP_DELTA_VERIFY (new key): owned by the job */
     char err[512];
 } job_t;
 
@@ -252,6 +260,8 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
     return 0;
 }
 
+#define PKEY_DELTA_REPORT_BYTES 104      /* sizeof(wsnark_pkey_delta_report_t) */
+#define PKEY_DELTA_VERDICT_BYTES 40      /* sizeof(wsnark_pkey_delta_verdict_t) */
 static void job_execute(napi_env env, void* data) {
     (void)env;
     job_t* j = (job_t*)data;
@@ -276,6 +286,13 @@ static void job_execute(napi_env env, void* data) {
     case OP_VERIFY_BATCH: j->rc = L.verify_batch(j->a, j->na, j->nb ? j->b : NULL, j->u0, j->c, j->nc / 384, j->out); break;
     case OP_CHECK_KEY:
         j->rc = j->path ? L.pkey_check_file(j->path, j->u0, j->r32, j->out) : L.pkey_check(j->a, j->na, j->u0, j->r32, j->out);
+        break;
+    case OP_CONTRIBUTE:      /* out = the report (104 B), then -- for key bytes -- the new key */
+        j->rc = j->path ? L.pkey_contribute_file(j->path, j->path2, j->r32, j->out)
+                        : L.pkey_contribute(j->a, j->na, j->r32, j->out + PKEY_DELTA_REPORT_BYTES, j->na, j->out);
+        break;
+    case OP_DELTA_VERIFY:
+        j->rc = j->path ? L.pkey_delta_verify_file(j->path, j->path2, j->r32, j->out) : L.pkey_delta_verify(j->a, j->na, j->b, j->nb, j->r32, j->out);
         break;
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
     case OP_GROUP_G1: j->rc = L.group_g1_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
@@ -368,19 +385,19 @@ static void job_complete(napi_env env, napi_status status, void* data) {
     for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
     napi_delete_async_work(env, j->work);
     job_done_with_group(j);
-    free(j->path);
+    free(j->path); free(j->path2);
     free(j->out);
     free(j);
 }
 
 static napi_value start_job(napi_env env, job_t* j, const char* name) {
     napi_value promise, rname;
-    if (!L.h) { job_done_with_group(j); free(j->path); free(j->out); free(j); napi_throw_error(env, NULL, "wsnark_napi: init() has not been called (use buildBn128())"); return NULL; }
+    if (!L.h) { job_done_with_group(j); free(j->path); free(j->path2); free(j->out); free(j); napi_throw_error(env, NULL, "wsnark_napi: init() has not been called (use buildBn128())"); return NULL; }
     if (napi_create_promise(env, &j->deferred, &promise) != napi_ok || napi_create_string_utf8(env, name, NAPI_AUTO_LENGTH, &rname) != napi_ok ||
         napi_create_async_work(env, NULL, rname, job_execute, job_complete, j, &j->work) != napi_ok || napi_queue_async_work(env, j->work) != napi_ok) {
         for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
         job_done_with_group(j);           /* (never queued: nothing will complete it) */
-        free(j->path); free(j->out); free(j);
+        free(j->path); free(j->path2); free(j->out); free(j);
         napi_throw_error(env, NULL, "wsnark_napi: cannot queue the call");
         return NULL;
     }
@@ -389,7 +406,7 @@ static napi_value start_job(napi_env env, job_t* j, const char* name) {
 static int keep(napi_env env, job_t* j, napi_value v) {   /* inputs stay referenced until completion */
     return napi_create_reference(env, v, 1, &j->refs[j->nrefs++]) == napi_ok;
 }
-#define FAIL(env, j, msg) do { free((j)->path); free((j)->out); free(j); napi_throw_type_error((env), NULL, (msg)); return NULL; } while (0)
+#define FAIL(env, j, msg) do { free((j)->path); free((j)->path2); free((j)->out); free(j); napi_throw_type_error((env), NULL, (msg)); return NULL; } while (0)
 static char* get_path(napi_env env, napi_value v) {        /* a JS string -> malloc'ed UTF-8 (NULL if it is not a string) */
     size_t n = 0;
     napi_valuetype t;
@@ -586,6 +603,45 @@ static napi_value js_check_key(napi_env env, napi_callback_info info) {
     if (!j->path) keep(env, j, argv[0]);
     if (j->r32) keep(env, j, argv[2]);
     return start_job(env, j, "wsnark_pkey_check");
+}
+
+/* contributeKey(pkeyBytes | inPath, outPath | null, d32 | null) -> Promise<ArrayBuffer>: the wsnark_pkey_delta_report_t (104 bytes) and,
+ * for key bytes, the new key behind it (wsnark_pkey_contribute / _contribute_file).  d32 == null: the library draws d and wipes it. */
+static napi_value js_contribute_key(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CONTRIBUTE;
+    if (argc < 1 || (!(j->path = get_path(env, argv[0])) && !get_bytes(env, argv[0], &j->a, &j->na)))
+        FAIL(env, j, "expected (proving_key.bin bytes | key file path, outPath | null[, d32])");
+    if (j->path && (argc < 2 || !(j->path2 = get_path(env, argv[1])))) FAIL(env, j, "a key file needs the path of the new file");
+    size_t ns = 0;
+    if (argc > 2 && get_bytes(env, argv[2], &j->r32, &ns) && ns != 32) FAIL(env, j, "the entropy must be 32 bytes");
+    j->nout = PKEY_DELTA_REPORT_BYTES + (j->path ? 0 : j->na);
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    if (!j->path) keep(env, j, argv[0]);
+    if (j->r32) keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_pkey_contribute");
+}
+/* deltaVerify(oldBytes | oldPath, newBytes | newPath, seed32 | null) -> Promise<ArrayBuffer 40>: the wsnark_pkey_delta_verdict_t */
+static napi_value js_delta_verify(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_DELTA_VERIFY;
+    if (argc < 2) FAIL(env, j, "expected (old key, new key[, seed32])");
+    j->path = get_path(env, argv[0]);
+    if (j->path ? !(j->path2 = get_path(env, argv[1])) : (!get_bytes(env, argv[0], &j->a, &j->na) || !get_bytes(env, argv[1], &j->b, &j->nb)))
+        FAIL(env, j, "expected two key byte buffers or two key file paths");
+    size_t ns = 0;
+    if (argc > 2 && get_bytes(env, argv[2], &j->r32, &ns) && ns != 32) FAIL(env, j, "the seed must be 32 bytes");
+    j->nout = PKEY_DELTA_VERDICT_BYTES;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    if (!j->path) { keep(env, j, argv[0]); keep(env, j, argv[1]); }
+    if (j->r32) keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_pkey_delta_verify");
 }
 
 /* allocPinned(bytes) -> ArrayBuffer over pinned host memory (wsnark_host_alloc): a witness written into it is DMA'd in place,
@@ -907,6 +963,8 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"verify", NULL, js_verify, NULL, NULL, NULL, napi_default, NULL},
         {"verifyBatch", NULL, js_verify_batch, NULL, NULL, NULL, napi_default, NULL},
         {"checkKey", NULL, js_check_key, NULL, NULL, NULL, napi_default, NULL},
+        {"contributeKey", NULL, js_contribute_key, NULL, NULL, NULL, napi_default, NULL},
+        {"deltaVerify", NULL, js_delta_verify, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},

@@ -409,6 +409,16 @@ def vk_from_points(npub, sec, ic, gamma2):
             "vk_gamma_2": dec2(gamma2), "vk_delta_2": dec2(sec["delta2"]), "IC": [dec1(p) for p in ic]}
 
 
+def vk_with_delta2(vk, new_key):
+    """The verification key that goes with a key after a phase-2 contribution (Bn128.contribute_key): vk with vk_delta_2 replaced
+    by the new key's delta2.  new_key: a sections dict, proving_key.bin bytes, or the 128 bytes of delta2 themselves."""
+    d2 = new_key["delta2"] if isinstance(new_key, dict) else bytes(new_key)
+    if len(d2) != 128:
+        d2 = d2[360:488]      # proving_key.bin: 40-byte header, alfa1, beta1, delta1, beta2, then delta2
+    d2 = bytes(d2)
+    return dict(vk, vk_delta_2=[[_dec_q(d2[0:32]), _dec_q(d2[32:64])], [_dec_q(d2[64:96]), _dec_q(d2[96:128])], ["1", "0"]])
+
+
 def proof_from_points(g1, g2):
     """{pi_a, pi_c} = the two 64-byte affine Montgomery points of g1, pi_b = the 128-byte point g2, as the proof object."""
     p1 = lambda p: ["0", "1", "0"] if p[:32] == b"\0" * 32 else [_dec_q(p[:32]), _dec_q(p[32:64]), "1"]
