@@ -11,12 +11,8 @@ import random
 import subprocess
 import sys
 
-from verify_batch_common import _f2_mul, twist_point_outside_g2
+from bn128_ref import Q, R, RINV, g1_on_curve, g2_on_twist, g2_times_r_is_infinity, le, mont, twist_point_outside_g2
 
-Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
-R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-MONT = 1 << 256
-RINV = pow(MONT, Q - 2, Q)
 OK, ERR_SIZE, ERR_FORMAT, ERR_ARG, ERR_NOINIT = 0, 1, 2, 4, 5
 SECTIONS = ("A", "B1", "B2", "C", "H")
 SEC_KEY = {"A": "pointsA", "B1": "pointsB1", "B2": "pointsB2", "C": "pointsC", "H": "pointsH"}
@@ -25,48 +21,7 @@ FIXED = ("alfa1", "beta1", "delta1", "beta2", "delta2")
 UNREDUCED, OFF_CURVE, OUTSIDE, INFINITY = "unreduced", "off_curve", "outside_subgroup", "infinity"
 
 
-# ---- the yardstick ----
-def _f2_inv(a):
-    n = pow((a[0] * a[0] + a[1] * a[1]) % Q, -1, Q)
-    return (a[0] * n % Q, (-a[1]) * n % Q)
-
-
-B2_TWIST = _f2_mul((3, 0), _f2_inv((9, 1)))
-
-
-def _f2_add(a, b):
-    return ((a[0] + b[0]) % Q, (a[1] + b[1]) % Q)
-
-
-def _f2_sub(a, b):
-    return ((a[0] - b[0]) % Q, (a[1] - b[1]) % Q)
-
-
-def _g2_add(p, q):
-    """Affine addition on the twist with every case; None is the point at infinity."""
-    if p is None:
-        return q
-    if q is None:
-        return p
-    if p[0] == q[0]:
-        if _f2_add(p[1], q[1]) == (0, 0):
-            return None
-        lam = _f2_mul(_f2_mul((3, 0), _f2_mul(p[0], p[0])), _f2_inv(_f2_mul((2, 0), p[1])))
-    else:
-        lam = _f2_mul(_f2_sub(q[1], p[1]), _f2_inv(_f2_sub(q[0], p[0])))
-    x = _f2_sub(_f2_sub(_f2_mul(lam, lam), p[0]), q[0])
-    return (x, _f2_sub(_f2_mul(lam, _f2_sub(p[0], x)), p[1]))
-
-
-def g2_times_r_is_infinity(pt):
-    acc = None
-    for bit in bin(R)[2:]:
-        acc = _g2_add(acc, acc)
-        if bit == "1":
-            acc = _g2_add(acc, pt)
-    return acc is None
-
-
+# ---- the yardstick (the arithmetic: bn128_ref.py) ----
 _memo = {}
 
 
@@ -84,10 +39,10 @@ def classify(pt):
     else:
         v = [x * RINV % Q for x in w]
         if nx == 1:
-            res = None if v[1] * v[1] % Q == (v[0] ** 3 + 3) % Q else OFF_CURVE
+            res = None if g1_on_curve(v[0], v[1]) else OFF_CURVE
         else:
             x, y = (v[0], v[1]), (v[2], v[3])
-            if _f2_mul(y, y) != _f2_add(_f2_mul(_f2_mul(x, x), x), B2_TWIST):
+            if not g2_on_twist(x, y):
                 res = OFF_CURVE
             else:
                 res = None if g2_times_r_is_infinity((x, y)) else OUTSIDE
@@ -141,17 +96,9 @@ def no_ms(rep):
     return {k: v for k, v in rep.items() if k != "ms"}
 
 
-def le(v):
-    return int(v).to_bytes(32, "little")
-
-
-def mont(v):
-    return le(int(v) * MONT % Q)
-
-
 def rogue_g2_bytes():
-    p = twist_point_outside_g2()
-    return mont(p[0][0]) + mont(p[0][1]) + mont(p[1][0]) + mont(p[1][1])
+    x, y = twist_point_outside_g2()
+    return mont(x[0]) + mont(x[1]) + mont(y[0]) + mont(y[1])
 
 
 def plant(sec, name, index, what):

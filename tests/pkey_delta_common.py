@@ -3,7 +3,7 @@ csrc/pkeydelta.hip), run by tests/test_emul_pkey_delta.py on the thread-emulator
 tests/test_gpu_pkey_delta.py on the device.
 
 The yardstick is never the code under test.  scale_batch is compared with affine double-and-add in plain Python integers
-(`g1_mul` / `g2_mul` below).  A re-keyed key is compared byte for byte with the closed form: the SAME synthetic key built from
+(`g1_mul` / `g2_mul` of bn128_ref.py).  A re-keyed key is compared byte for byte with the closed form: the SAME synthetic key built from
 toxic waste whose delta is delta * d, every point a fixed-base multiple of a known logarithm through mul_base -- an independent
 kernel that the parity tests pin.  Bad input points are counted by the audit's pure-Python classifier (pkey_check_common)."""
 import ctypes as C
@@ -12,63 +12,27 @@ import subprocess
 import sys
 
 import pkey_check_common as pk
-from pkey_check_common import ERR_ARG, ERR_FORMAT, ERR_NOINIT, ERR_SIZE, MONT, Q, R, RINV, _g2_add, le
+from bn128_ref import Q, R, from_mont, g1_mul, g2_mul, le, mont
+from pkey_check_common import ERR_ARG, ERR_FORMAT, ERR_NOINIT, ERR_SIZE
 
 D_FIXED = 0x1D2C3B4A5968778695A4B3C2D1E0F00112233445566778899AABBCCDDEEFF01 % R
 BIT = {"unchanged": 1, "delta1~delta2": 2, "C": 4, "H": 8, "delta_changed": 16}
 
 
-# ---- the yardstick: affine double-and-add, Python integers ----
-def _g1_add(p, q):
-    """Affine addition on y^2 = x^3 + 3 with every case; None is the point at infinity."""
-    if p is None:
-        return q
-    if q is None:
-        return p
-    if p[0] == q[0]:
-        if (p[1] + q[1]) % Q == 0:
-            return None
-        lam = 3 * p[0] * p[0] * pow(2 * p[1], -1, Q) % Q
-    else:
-        lam = (q[1] - p[1]) * pow(q[0] - p[0], -1, Q) % Q
-    x = (lam * lam - p[0] - q[0]) % Q
-    return (x, (lam * (p[0] - x) - p[1]) % Q)
-
-
-def _times(add, pt, k):
-    acc = None
-    for bit in bin(k)[2:] if k else "":
-        acc = add(acc, acc)
-        if bit == "1":
-            acc = add(acc, pt)
-    return acc
-
-
-def g1_mul(pt, k):
-    return _times(_g1_add, pt, k)
-
-
-def g2_mul(pt, k):
-    return _times(_g2_add, pt, k)
-
-
-def _dec(b):
-    return int.from_bytes(b, "little") * RINV % Q
-
-
+# ---- the yardstick: affine double-and-add in Python integers (bn128_ref.g1_mul / g2_mul) ----
 def point_from_bytes(g, b):
     """64 / 128 bytes affine Montgomery -> integers; x == 0 (the loaders' rule) -> None"""
     if g == 1:
-        return None if not any(b[:32]) else (_dec(b[:32]), _dec(b[32:64]))
-    return None if not any(b[:64]) else ((_dec(b[:32]), _dec(b[32:64])), (_dec(b[64:96]), _dec(b[96:128])))
+        return None if not any(b[:32]) else (from_mont(b[:32]), from_mont(b[32:64]))
+    return None if not any(b[:64]) else ((from_mont(b[:32]), from_mont(b[32:64])), (from_mont(b[64:96]), from_mont(b[96:128])))
 
 
 def point_to_bytes(g, p):
     if p is None:
         return bytes(64 if g == 1 else 128)
     if g == 1:
-        return pk.mont(p[0]) + pk.mont(p[1])
-    return pk.mont(p[0][0]) + pk.mont(p[0][1]) + pk.mont(p[1][0]) + pk.mont(p[1][1])
+        return mont(p[0]) + mont(p[1])
+    return mont(p[0][0]) + mont(p[0][1]) + mont(p[1][0]) + mont(p[1][1])
 
 
 _mul_memo = {}

@@ -13,10 +13,9 @@ import random
 import subprocess
 import sys
 
+from bn128_ref import Q, R, twist_point_outside_g2
 from conftest import GOLDEN, ROOT, load_golden
 
-Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
-R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 OK, ERR_SIZE, ERR_FORMAT, ERR_NOINIT = 0, 1, 2, 5
 
 
@@ -134,45 +133,10 @@ def check_golden_proofs(bn, name):
 
 
 # ---- 4. malformed points between valid neighbours ----
-def _f2_mul(a, b):
-    return ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
-
-
-def _f2_inv(a):
-    n = pow((a[0] * a[0] + a[1] * a[1]) % Q, Q - 2, Q)
-    return (a[0] * n % Q, (-a[1]) * n % Q)
-
-
-def _f2_sqrt(a):
-    """sqrt in Fq[u]/(u^2 + 1), q = 3 mod 4 (complex method); None if a is not a square."""
-    if a == (0, 0):
-        return (0, 0)
-    norm = (a[0] * a[0] + a[1] * a[1]) % Q
-    s = pow(norm, (Q + 1) // 4, Q)
-    if s * s % Q != norm:
-        return None
-    half = pow(2, Q - 2, Q)
-    for sign in (1, -1):
-        t = (a[0] + sign * s) * half % Q
-        x0 = pow(t, (Q + 1) // 4, Q)
-        if x0 * x0 % Q == t and x0:
-            x1 = a[1] * pow(2 * x0 % Q, Q - 2, Q) % Q
-            if _f2_mul((x0, x1), (x0, x1)) == (a[0] % Q, a[1] % Q):
-                return (x0, x1)
-    return None
-
-
-def twist_point_outside_g2():
-    """A point on the twist y^2 = x^3 + 3/(9 + u), almost surely not in the order-r subgroup (the cofactor is ~2^254)."""
-    b2 = _f2_mul((3, 0), _f2_inv((9, 1)))
-    k = 1
-    while True:
-        x = (k, 7 * k + 1)
-        x3 = _f2_mul(_f2_mul(x, x), x)
-        y = _f2_sqrt(((x3[0] + b2[0]) % Q, (x3[1] + b2[1]) % Q))
-        if y is not None:
-            return [[str(x[0]), str(x[1])], [str(y[0]), str(y[1])], ["1", "0"]]
-        k += 1
+def rogue_g2_json():
+    """bn128_ref's twist point outside the order-r subgroup, as the coordinates of a proof or key JSON."""
+    x, y = twist_point_outside_g2()
+    return [[str(x[0]), str(x[1])], [str(y[0]), str(y[1])], ["1", "0"]]
 
 
 def malformed_cases(good, good2, pub):
@@ -185,7 +149,7 @@ def malformed_cases(good, good2, pub):
         ("pi_a off the curve", pub, dict(good, pi_a=bump(good["pi_a"]))),
         ("pi_c off the curve", pub, dict(good, pi_c=bump(good["pi_c"]))),
         ("pi_b off the twist", pub, dict(good, pi_b=[b[0], [b[1][0], str((int(b[1][1]) + 1) % Q)], b[2]])),
-        ("pi_b outside the subgroup", pub, dict(good, pi_b=twist_point_outside_g2())),
+        ("pi_b outside the subgroup", pub, dict(good, pi_b=rogue_g2_json())),
         ("z coordinates 0 and 5", pub, dict(good, pi_a=[good["pi_a"][0], good["pi_a"][1], "0"], pi_c=good["pi_c"][:2] + ["5"])),
         ("proof at infinity", pub, {"pi_a": ["0", "1", "0"], "pi_b": [["0", "0"], ["1", "0"], ["0", "0"]], "pi_c": ["0", "1", "0"]}),
         ("an input >= r", [str(R + 1)] + pub[1:], good),
@@ -235,7 +199,7 @@ def check_key_level(bn, so_path):
     ib, pb = _inputs_bytes(pub) * 3, b"".join(proof_to_bytes(p) for p in good)
     assert batch_status(lib, vk_to_bytes(vk, n_in), n_in, ib, pb) == [1, 1, 1]
     bump = lambda p: [p[0], str((int(p[1]) + 1) % Q), p[2]]
-    rogue = twist_point_outside_g2()
+    rogue = rogue_g2_json()
     bad_keys = [dict(vk, vk_alfa_1=bump(vk["vk_alfa_1"])), dict(vk, vk_gamma_2=rogue), dict(vk, vk_delta_2=rogue),
                 dict(vk, IC=[bump(vk["IC"][0])] + vk["IC"][1:]), dict(vk, IC=vk["IC"][:-1] + [bump(vk["IC"][-1])])]
     for k in bad_keys:

@@ -4,60 +4,7 @@
 
 #include "../../include/wsnark.h"
 #include "internal.h"
-
-namespace wsnark {
-int context_init(int device);
-void context_shutdown();
-const std::string& get_last_error();
-const std::string& device_info();
-struct ProvingKey;
-int pkey_load(const uint8_t* buf, size_t len, ProvingKey** out);
-void pkey_free(ProvingKey* K);
-void pkey_info(const ProvingKey* K, uint32_t* nv, uint32_t* np, uint32_t* dom);
-void pkey_table_info(const ProvingKey* K, uint32_t* cw, uint32_t* rw, uint32_t* ch, uint32_t* rh, uint64_t* bytes);
-int groth16_prove_host_witness(ProvingKey* K, const uint8_t* witness, size_t witness_len, const uint8_t* r32,
-                               const uint8_t* s32, uint8_t* out384);
-int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard);
-void pkey_shard_info(const ProvingKey* K, uint32_t* rank, uint32_t* world, uint64_t* lo, uint64_t* n_local, uint64_t* h_local, uint32_t* h_log_m);
-void pkey_load_stats(const ProvingKey* K, double* out5);
-int pkey_wait_tables(ProvingKey* K);
-Context* pkey_context(const ProvingKey* K);
-int groth16_prove_dist(ProvingKey* K, const Fe* d_witness, size_t witness_len, const DistComm& cm, const uint8_t* r32, const uint8_t* s32,
-                       uint8_t* out384, hipStream_t s);
-int pkey_h_msm_dev(ProvingKey* K, const Fe* d_h_local, uint64_t n, uint8_t* out96, hipStream_t s);
-int groth16_prove_partial(ProvingKey* K, const uint8_t* witness, size_t witness_len, WindowShard sh, uint8_t* out576, bool skip_h);
-int groth16_prove_partial_dev(ProvingKey* K, const Fe* d_witness, size_t witness_len, WindowShard sh, uint8_t* out576, hipStream_t s, bool skip_h);
-int pkey_eval_ab_dev(ProvingKey* K, const Fe* d_witness, size_t witness_len, Fe* d_a, Fe* d_b, hipStream_t s);
-int groth16_prove_finish(ProvingKey* K, const uint8_t* partials, uint64_t n_ranks, const uint8_t* r32,
-                         const uint8_t* s32, uint8_t* out384);
-int groth16_prove_dev_witness(ProvingKey* K, const Fe* d_witness, size_t witness_len, const uint8_t* r32,
-                              const uint8_t* s32, uint8_t* out384, hipStream_t s);
-bool last_blinding(uint8_t* r32, uint8_t* s32);
-int groth16_verify(const uint8_t* vk, size_t vk_len, const uint8_t* inputs, uint64_t n_inputs, const uint8_t* proof384, int* valid);
-int dist_scale_dev(Fe* d_data, uint64_t stack, uint64_t rows, uint64_t cols, uint64_t row0, uint32_t log_n1, uint32_t log_n, int mode, int inverse, hipStream_t s);
-void g1_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out96);
-void g2_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out192);
-int g1_mul_base_batch(const void* base, const void* scalars, uint64_t n, void* out);
-int g2_mul_base_batch(const void* base, const void* scalars, uint64_t n, void* out);
-int peak_probe(int probe, double* gops);
-struct ResidentPoints;
-Context* points_context(const ResidentPoints* H);
-int points_load(int which, const void* h_points, uint64_t n, ResidentPoints** out);
-void points_free(ResidentPoints* H);
-void points_info(const ResidentPoints* H, int* which, uint64_t* n, uint32_t* table_c, uint32_t* rows, uint64_t* bytes);
-int points_msm(ResidentPoints* H, const void* scalars, bool on_device, uint64_t n, void* out, hipStream_t s);
-int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
-int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, uint8_t* out, uint64_t n);
-int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
-int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* seed32, wsnark_pkey_report_t* out);
-int g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
-int g2_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
-int pkey_contribute_sections(const KeySections& S, const uint8_t* d32, uint8_t* out_pointsC, uint8_t* out_pointsH, uint8_t* out_delta1,
-                             uint8_t* out_delta2, wsnark_pkey_delta_report_t* rep);
-int pkey_contribute_bytes(const uint8_t* pkey, size_t len, const uint8_t* d32, uint8_t* out, size_t out_cap, wsnark_pkey_delta_report_t* rep);
-int pkey_contribute_file(const char* in_path, const char* out_path, const uint8_t* d32, wsnark_pkey_delta_report_t* rep);
-int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const uint8_t* seed32, wsnark_pkey_delta_verdict_t* out);
-}  // namespace wsnark
+#include "keybytes.h"
 
 using namespace wsnark;
 
@@ -93,6 +40,34 @@ static int msm_entry(Context* C, bool host, const void* scalars, const void* poi
     int rc = run(*L, WindowShard{rank, world}, &r);
     if (rc) return rc;
     memcpy(out, &r, sizeof r);
+    return WSNARK_OK;
+}
+
+// ---- a key's bytes as the entry points below receive them: an image in memory, separate sections, or a file ----
+struct KeyInput {
+    KeySections S;
+    KeyFile file;      // the third case: the mapping S points into (S.release hands every range the callee has read back to the kernel)
+    int open(const void* pkey, size_t len) { return pkey_parse((const uint8_t*)pkey, len, &S); }
+    int open(const wsnark_key_sections_t* ks) {
+        if (!ks || !ks->alfa1 || !ks->beta1 || !ks->delta1 || !ks->beta2 || !ks->delta2 || !ks->polsA ||
+            !ks->polsB || !ks->pointsA || !ks->pointsB1 || !ks->pointsB2 || !ks->pointsH ||
+            (!ks->pointsC && (uint64_t)ks->n_vars > (uint64_t)ks->n_public + 1))
+            return WSNARK_ERR_ARG;
+        S = KeySections{ks->n_vars, ks->n_public, ks->domain, (const uint8_t*)ks->alfa1, (const uint8_t*)ks->beta1,
+                        (const uint8_t*)ks->delta1, (const uint8_t*)ks->beta2, (const uint8_t*)ks->delta2,
+                        (const uint8_t*)ks->polsA, ks->polsA_len, (const uint8_t*)ks->polsB, ks->polsB_len,
+                        (const uint8_t*)ks->pointsA, (const uint8_t*)ks->pointsB1, (const uint8_t*)ks->pointsB2,
+                        (const uint8_t*)ks->pointsC, (const uint8_t*)ks->pointsH,
+                        ks->pointsA_len, ks->pointsB1_len, ks->pointsB2_len, ks->pointsC_len, ks->pointsH_len};
+        return WSNARK_OK;
+    }
+    int open(const char* path) { return keyfile_open(path, &file, &S); }
+};
+static int load_entry(const KeySections& S, KeyShard shard, wsnark_pkey_t** out_handle) {
+    ProvingKey* K = nullptr;
+    int rc = pkey_load_sections(S, &K, shard);      // (returns with every byte it needs copied: a mapped file may go)
+    if (rc) return rc;
+    *out_handle = reinterpret_cast<wsnark_pkey_t*>(K);
     return WSNARK_OK;
 }
 
@@ -264,11 +239,9 @@ int wsnark_calc_h(const void* signals, const void* polsA, size_t lenA, const voi
 int wsnark_pkey_load(const void* pkey, size_t len, wsnark_pkey_t** out_handle) {
     REQUIRE_CTX();
     if (!out_handle) return WSNARK_ERR_ARG;
-    ProvingKey* K = nullptr;
-    int rc = pkey_load((const uint8_t*)pkey, len, &K);
-    if (rc) return rc;
-    *out_handle = reinterpret_cast<wsnark_pkey_t*>(K);
-    return WSNARK_OK;
+    KeyInput in;
+    int rc = in.open(pkey, len);
+    return rc ? rc : load_entry(in.S, KeyShard{}, out_handle);
 }
 void wsnark_pkey_free(wsnark_pkey_t* h) {
     if (!h) return;
@@ -300,88 +273,59 @@ int wsnark_groth16_prove_dev(wsnark_pkey_t* h, const void* d_witness, size_t wit
                                      (const uint8_t*)r32, (const uint8_t*)s32, (uint8_t*)out384_host, (hipStream_t)stream);
 }
 
-static int sections_from_abi(const wsnark_key_sections_t* ks, KeySections* S) {
-    if (!ks || !ks->alfa1 || !ks->beta1 || !ks->delta1 || !ks->beta2 || !ks->delta2 || !ks->polsA ||
-        !ks->polsB || !ks->pointsA || !ks->pointsB1 || !ks->pointsB2 || !ks->pointsH ||
-        (!ks->pointsC && (uint64_t)ks->n_vars > (uint64_t)ks->n_public + 1))
-        return WSNARK_ERR_ARG;
-    *S = KeySections{ks->n_vars, ks->n_public, ks->domain, (const uint8_t*)ks->alfa1, (const uint8_t*)ks->beta1,
-                     (const uint8_t*)ks->delta1, (const uint8_t*)ks->beta2, (const uint8_t*)ks->delta2,
-                     (const uint8_t*)ks->polsA, ks->polsA_len, (const uint8_t*)ks->polsB, ks->polsB_len,
-                     (const uint8_t*)ks->pointsA, (const uint8_t*)ks->pointsB1, (const uint8_t*)ks->pointsB2,
-                     (const uint8_t*)ks->pointsC, (const uint8_t*)ks->pointsH,
-                     ks->pointsA_len, ks->pointsB1_len, ks->pointsB2_len, ks->pointsC_len, ks->pointsH_len};
-    return WSNARK_OK;
-}
-static int load_sections_entry(const wsnark_key_sections_t* ks, KeyShard shard, wsnark_pkey_t** out_handle) {
-    KeySections S;
-    if (!out_handle || sections_from_abi(ks, &S)) return WSNARK_ERR_ARG;
-    ProvingKey* K = nullptr;
-    int rc = pkey_load_sections(S, &K, shard);
-    if (rc) return rc;
-    *out_handle = reinterpret_cast<wsnark_pkey_t*>(K);
-    return WSNARK_OK;
-}
 int wsnark_pkey_load_sections(const wsnark_key_sections_t* ks, wsnark_pkey_t** out_handle) {
     REQUIRE_CTX();
-    return load_sections_entry(ks, KeyShard{}, out_handle);
+    KeyInput in;
+    if (!out_handle || in.open(ks)) return WSNARK_ERR_ARG;
+    return load_entry(in.S, KeyShard{}, out_handle);
 }
 int wsnark_pkey_load_shard(const wsnark_key_sections_t* ks, uint32_t rank, uint32_t world, uint32_t h_interleave_log,
                            wsnark_pkey_t** out_handle) {
     REQUIRE_CTX();
-    if (!shard_ok(rank, world)) return WSNARK_ERR_ARG;
-    return load_sections_entry(ks, KeyShard{rank, world, h_interleave_log}, out_handle);
+    KeyInput in;
+    if (!shard_ok(rank, world) || !out_handle || in.open(ks)) return WSNARK_ERR_ARG;
+    return load_entry(in.S, KeyShard{rank, world, h_interleave_log}, out_handle);
 }
 // a key FILE: proving_key.bin or the WSNARK64 container (keyfile.hip); rank / world / h_interleave_log as wsnark_pkey_load_shard
 int wsnark_pkey_load_file(const char* path, uint32_t rank, uint32_t world, uint32_t h_interleave_log, wsnark_pkey_t** out_handle) {
     REQUIRE_CTX();
     if (!path || !out_handle || !shard_ok(rank, world)) return WSNARK_ERR_ARG;
-    KeyFile F;
-    KeySections S;
-    int rc = keyfile_open(path, &F, &S);
-    if (rc) return rc;
-    ProvingKey* K = nullptr;
-    rc = pkey_load_sections(S, &K, KeyShard{rank, world, h_interleave_log});      // (returns with every byte it needs copied: F may go)
-    if (rc) return rc;
-    *out_handle = reinterpret_cast<wsnark_pkey_t*>(K);
-    return WSNARK_OK;
+    KeyInput in;
+    int rc = in.open(path);
+    return rc ? rc : load_entry(in.S, KeyShard{rank, world, h_interleave_log}, out_handle);
 }
 int wsnark_pkey_file_info(const char* path, uint32_t* n_vars, uint32_t* n_public, uint32_t* domain, uint64_t* file_bytes, int* format) {
     if (!path) return WSNARK_ERR_ARG;
-    KeyFile F;
-    KeySections S;
-    int rc = keyfile_open(path, &F, &S);
+    KeyInput in;
+    int rc = in.open(path);
     if (rc) return rc;
-    if (n_vars) *n_vars = S.n_vars;
-    if (n_public) *n_public = S.n_public;
-    if (domain) *domain = S.domain;
-    if (file_bytes) *file_bytes = F.len;
-    if (format) *format = F.format;
+    if (n_vars) *n_vars = in.S.n_vars;
+    if (n_public) *n_public = in.S.n_public;
+    if (domain) *domain = in.S.domain;
+    if (file_bytes) *file_bytes = in.file.len;
+    if (format) *format = in.file.format;
     return WSNARK_OK;
 }
 // ---- the audit of a key's bytes (pkeycheck.hip): what the three loaders take, no handle ----
 int wsnark_pkey_check(const void* pkey, size_t len, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out) {
     REQUIRE_CTX();
     if (!out) return WSNARK_ERR_ARG;
-    KeySections S;
-    int rc = pkey_parse((const uint8_t*)pkey, len, &S);
-    if (rc) return rc;
-    return pkey_check_sections(S, flags, (const uint8_t*)seed32, out);
+    KeyInput in;
+    int rc = in.open(pkey, len);
+    return rc ? rc : pkey_check_sections(in.S, flags, (const uint8_t*)seed32, out);
 }
 int wsnark_pkey_check_sections(const wsnark_key_sections_t* ks, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out) {
     REQUIRE_CTX();
-    KeySections S;
-    if (!out || sections_from_abi(ks, &S)) return WSNARK_ERR_ARG;
-    return pkey_check_sections(S, flags, (const uint8_t*)seed32, out);
+    KeyInput in;
+    if (!out || in.open(ks)) return WSNARK_ERR_ARG;
+    return pkey_check_sections(in.S, flags, (const uint8_t*)seed32, out);
 }
 int wsnark_pkey_check_file(const char* path, uint32_t flags, const void* seed32, wsnark_pkey_report_t* out) {
     REQUIRE_CTX();
     if (!path || !out) return WSNARK_ERR_ARG;
-    KeyFile F;
-    KeySections S;
-    int rc = keyfile_open(path, &F, &S);      // (S.release: every staged range of the mapping goes back to the kernel)
-    if (rc) return rc;
-    return pkey_check_sections(S, flags, (const uint8_t*)seed32, out);
+    KeyInput in;
+    int rc = in.open(path);
+    return rc ? rc : pkey_check_sections(in.S, flags, (const uint8_t*)seed32, out);
 }
 // ---- the phase-2 delta contribution and its check (pkeydelta.hip) ----
 int wsnark_g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out_affine) {
@@ -394,46 +338,49 @@ int wsnark_g2_scale_batch(const void* points, uint64_t n, const void* k32, void*
 }
 int wsnark_pkey_contribute(const void* pkey, size_t len, const void* d32, void* out_pkey, size_t out_cap, wsnark_pkey_delta_report_t* rep) {
     REQUIRE_CTX();
-    return pkey_contribute_bytes((const uint8_t*)pkey, len, (const uint8_t*)d32, (uint8_t*)out_pkey, out_cap, rep);
+    if (!rep || !out_pkey) return WSNARK_ERR_ARG;
+    KeyInput in;
+    int rc = in.open(pkey, len);
+    return rc ? rc : pkey_contribute_bytes(in.S, (const uint8_t*)pkey, len, (const uint8_t*)d32, (uint8_t*)out_pkey, out_cap, rep);
 }
-int wsnark_pkey_contribute_sections(const wsnark_key_sections_t* in, const void* d32, void* out_pointsC, void* out_pointsH,
+int wsnark_pkey_contribute_sections(const wsnark_key_sections_t* ks, const void* d32, void* out_pointsC, void* out_pointsH,
                                     void* out_delta1_64, void* out_delta2_128, wsnark_pkey_delta_report_t* rep) {
     REQUIRE_CTX();
-    KeySections S;
-    if (!rep || sections_from_abi(in, &S)) return WSNARK_ERR_ARG;
-    return pkey_contribute_sections(S, (const uint8_t*)d32, (uint8_t*)out_pointsC, (uint8_t*)out_pointsH, (uint8_t*)out_delta1_64,
+    KeyInput in;
+    if (!rep || in.open(ks)) return WSNARK_ERR_ARG;
+    return pkey_contribute_sections(in.S, (const uint8_t*)d32, (uint8_t*)out_pointsC, (uint8_t*)out_pointsH, (uint8_t*)out_delta1_64,
                                     (uint8_t*)out_delta2_128, rep);
 }
 int wsnark_pkey_contribute_file(const char* in_path, const char* out_path, const void* d32, wsnark_pkey_delta_report_t* rep) {
     REQUIRE_CTX();
-    return pkey_contribute_file(in_path, out_path, (const uint8_t*)d32, rep);
+    if (!in_path || !out_path || !rep) return WSNARK_ERR_ARG;
+    KeyInput in;
+    int rc = in.open(in_path);
+    return rc ? rc : pkey_contribute_file(in.S, in.file, in_path, out_path, (const uint8_t*)d32, rep);
 }
 int wsnark_pkey_delta_verify(const void* old_pkey, size_t old_len, const void* new_pkey, size_t new_len, const void* seed32,
                              wsnark_pkey_delta_verdict_t* out) {
     REQUIRE_CTX();
     if (!out) return WSNARK_ERR_ARG;
-    KeySections O, N;
-    int rc = pkey_parse((const uint8_t*)old_pkey, old_len, &O);
-    if (!rc) rc = pkey_parse((const uint8_t*)new_pkey, new_len, &N);
-    if (rc) return rc;
-    return pkey_delta_verify_sections(O, N, (const uint8_t*)seed32, out);
+    KeyInput o, n;
+    int rc = o.open(old_pkey, old_len);
+    if (!rc) rc = n.open(new_pkey, new_len);
+    return rc ? rc : pkey_delta_verify_sections(o.S, n.S, (const uint8_t*)seed32, out);
 }
 int wsnark_pkey_delta_verify_sections(const wsnark_key_sections_t* old_key, const wsnark_key_sections_t* new_key, const void* seed32,
                                       wsnark_pkey_delta_verdict_t* out) {
     REQUIRE_CTX();
-    KeySections O, N;
-    if (!out || sections_from_abi(old_key, &O) || sections_from_abi(new_key, &N)) return WSNARK_ERR_ARG;
-    return pkey_delta_verify_sections(O, N, (const uint8_t*)seed32, out);
+    KeyInput o, n;
+    if (!out || o.open(old_key) || n.open(new_key)) return WSNARK_ERR_ARG;
+    return pkey_delta_verify_sections(o.S, n.S, (const uint8_t*)seed32, out);
 }
 int wsnark_pkey_delta_verify_file(const char* old_path, const char* new_path, const void* seed32, wsnark_pkey_delta_verdict_t* out) {
     REQUIRE_CTX();
     if (!old_path || !new_path || !out) return WSNARK_ERR_ARG;
-    KeyFile FO, FN;
-    KeySections O, N;
-    int rc = keyfile_open(old_path, &FO, &O);
-    if (!rc) rc = keyfile_open(new_path, &FN, &N);
-    if (rc) return rc;
-    return pkey_delta_verify_sections(O, N, (const uint8_t*)seed32, out);
+    KeyInput o, n;
+    int rc = o.open(old_path);
+    if (!rc) rc = n.open(new_path);
+    return rc ? rc : pkey_delta_verify_sections(o.S, n.S, (const uint8_t*)seed32, out);
 }
 int wsnark_pkey_shard_info(const wsnark_pkey_t* h, uint32_t* rank, uint32_t* world, uint64_t* first_signal, uint64_t* n_signals,
                            uint64_t* n_hexps, uint32_t* h_interleave_log) {

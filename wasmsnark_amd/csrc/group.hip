@@ -31,8 +31,6 @@
 
 namespace wsnark {
 
-const std::string& get_last_error();
-
 // all ranks arrive, all leave: spins briefly (the exchanges of a proof are microseconds apart), then yields
 struct SpinBarrier {
     std::atomic<uint32_t> count{0}, generation{0};
@@ -164,14 +162,6 @@ struct GroupKey {
     bool dist = false;                            // CALC_H on the distributed transform (else: complete on every device)
     uint32_t h_log_m = 0;
 };
-
-int groth16_prove_dist(ProvingKey* K, const Fe* d_witness, size_t witness_len, const DistComm& cm, const uint8_t* r32, const uint8_t* s32,
-                       uint8_t* out384, hipStream_t s);
-int groth16_prove_partial(ProvingKey* K, const uint8_t* witness, size_t witness_len, WindowShard sh, uint8_t* out576, bool skip_h);
-int groth16_prove_finish(ProvingKey* K, const uint8_t* partials, uint64_t n_ranks, const uint8_t* r32, const uint8_t* s32, uint8_t* out384);
-bool last_blinding(uint8_t* r32, uint8_t* s32);
-void g1_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out96);
-void g2_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out192);
 
 }  // namespace wsnark
 

@@ -151,6 +151,10 @@ struct DeviceRestore {
     DeviceRestore(const DeviceRestore&) = delete;
     DeviceRestore& operator=(const DeviceRestore&) = delete;
 };
+int context_init(int device);                  // the default context (wsnark_init / wsnark_shutdown)
+void context_shutdown();
+const std::string& get_last_error();           // the calling thread's (rt.h: set_last_error)
+const std::string& device_info();              // of the calling thread's context
 int context_create(int device, Context** out, bool wrap = false);  // a context of its own on that device (wsnark_group_create)
 void context_destroy(Context* C);
 // One no-op kernel per translation unit: the runtime loads a TU's code object when the first of its kernels is launched (7-12 ms for
@@ -279,7 +283,8 @@ void msm_abort_slots(Lane& L, const int* slots, int nslots, hipStream_t a, hipSt
 void msm_workspace_free(Lane& L);
 int msm_prepare_points(int which, void* d_points, uint64_t n, hipStream_t s);
 
-// ---- batch Groth16 verification (pairing.hip) ----
+// ---- Groth16 verification: one proof on the host (verify.hip), a batch on the device (pairing.hip) ----
+int groth16_verify(const uint8_t* vk, size_t vk_len, const uint8_t* inputs, uint64_t n_inputs, const uint8_t* proof384, int* valid);
 struct PairConsts;    // fp12.h
 // the constants of the device pairing (Frobenius table, exponents, domain multipliers), computed from xi with the host field and
 // self-checked the first time they are asked for; WS_OK or WS_ERR_FORMAT if the self-check fails
@@ -345,6 +350,38 @@ void pkey_free(ProvingKey* K);
 int pkey_wait_tables(ProvingKey* K);
 Context* pkey_context(const ProvingKey* K);
 void pkey_info(const ProvingKey* K, uint32_t* nv, uint32_t* np, uint32_t* dom);
+void pkey_table_info(const ProvingKey* K, uint32_t* cw, uint32_t* rw, uint32_t* ch, uint32_t* rh, uint64_t* bytes);
+void pkey_shard_info(const ProvingKey* K, uint32_t* rank, uint32_t* world, uint64_t* lo, uint64_t* n_local, uint64_t* h_local, uint32_t* h_log_m);
+void pkey_load_stats(const ProvingKey* K, double* out5);
+int groth16_prove_host_witness(ProvingKey* K, const uint8_t* witness, size_t witness_len, const uint8_t* r32, const uint8_t* s32, uint8_t* out384);
+int groth16_prove_dev_witness(ProvingKey* K, const Fe* d_witness, size_t witness_len, const uint8_t* r32, const uint8_t* s32, uint8_t* out384,
+                              hipStream_t s);
+int groth16_prove_partial(ProvingKey* K, const uint8_t* witness, size_t witness_len, WindowShard sh, uint8_t* out576, bool skip_h);
+int groth16_prove_partial_dev(ProvingKey* K, const Fe* d_witness, size_t witness_len, WindowShard sh, uint8_t* out576, hipStream_t s, bool skip_h);
+int groth16_prove_finish(ProvingKey* K, const uint8_t* partials, uint64_t n_ranks, const uint8_t* r32, const uint8_t* s32, uint8_t* out384);
+int pkey_h_msm_dev(ProvingKey* K, const Fe* d_h_local, uint64_t n, uint8_t* out96, hipStream_t s);
+int pkey_eval_ab_dev(ProvingKey* K, const Fe* d_witness, size_t witness_len, Fe* d_a, Fe* d_b, hipStream_t s);
+bool last_blinding(uint8_t* r32, uint8_t* s32);
+// serial host sum of Jacobian-Montgomery partials (the reference's gather loop), affine-normalised
+void g1_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out96);
+void g2_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out192);
+int os_random(uint8_t* out, size_t n);      // getrandom(2), else /dev/urandom; 0 = all n bytes drawn
+
+// ---- resident bases and fixed-base multiples (fixedbase.hip) ----
+struct ResidentPoints;
+Context* points_context(const ResidentPoints* H);
+int points_load(int which, const void* h_points, uint64_t n, ResidentPoints** out);
+void points_free(ResidentPoints* H);
+void points_info(const ResidentPoints* H, int* which, uint64_t* n, uint32_t* table_c, uint32_t* rows, uint64_t* bytes);
+int points_msm(ResidentPoints* H, const void* scalars, bool on_device, uint64_t n, void* out, hipStream_t s);
+int g1_mul_base_batch(const void* base, const void* scalars, uint64_t n, void* out);
+int g2_mul_base_batch(const void* base, const void* scalars, uint64_t n, void* out);
+
+// ---- device self-tests and peak probes (selftest.hip) ----
+int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
+int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, uint8_t* out, uint64_t n);
+int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
+int peak_probe(int probe, double* gops);
 
 // ---- one proof over the ranks of a node (dist.hip) ----
 // The host's transport (include/wsnark.h: wsnark_comm_t): exchange buffers it owns and two callbacks.
@@ -357,6 +394,8 @@ struct DistComm {
     int (*all_gather)(void* user, const void* send, void* recv, uint64_t bytes) = nullptr;
     void* user = nullptr;
 };
+int groth16_prove_dist(ProvingKey* K, const Fe* d_witness, size_t witness_len, const DistComm& cm, const uint8_t* r32, const uint8_t* s32,
+                       uint8_t* out384, hipStream_t s);
 // the rank's slice of h (plain form, 2^l2-interleaved rows of the rank), three exchanges
 // *exchanges (optional): how many of the three all-to-alls this rank has posted when the call returns
 int calc_h_dist(Lane& L, const DistComm& cm, const Fe* d_signals_plain, uint32_t n_signals, const CsrMatrix& A, const CsrMatrix& B,

@@ -1,0 +1,169 @@
+// keybytes.h -- the parts shared by everything that walks the BYTES of a proving key: the loaders (prove.hip, keyfile.hip), the audit
+// (pkeycheck.hip) and the phase-2 contribution with its check (pkeydelta.hip).  One copy each of: the header conditions a key must
+// meet and its five section counts; the per-point classifier on the device and its reduction; the decoding of that reduction on
+// the host; the fixed-point tests and the pairing relation; the seed draw; the chunked staging; the random-combination sums.
+#pragma once
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "../../include/wsnark.h"
+#include "internal.h"
+#include "fp12_host.h"
+
+namespace wsnark {
+
+// ---- a key's shape ----
+// the first header condition alone (nPublic + 1 <= nVars): the parsers need nVars - nPublic - 1 before they can bound a section
+int key_vars_check(uint32_t n_vars, uint32_t n_public);
+// what every consumer of a key's bytes rejects, with the loaders' codes and messages, in this order: too few variables for the inputs
+// (WS_ERR_FORMAT), domainSize not a power of two in [2, 2^27] (WS_ERR_SIZE), a point section shorter than the header implies
+// (WS_ERR_FORMAT)
+int key_shape_check(const KeySections& S);
+// points per section, indexed by WSNARK_PK_A .. WSNARK_PK_H (a key that passed key_shape_check)
+struct KeyCounts {
+    uint64_t n[5];
+    uint64_t operator[](int k) const { return n[k]; }
+};
+inline KeyCounts key_counts(const KeySections& S) {
+    const uint64_t nv = S.n_vars;
+    return KeyCounts{{nv, nv, nv, nv - S.n_public - 1, S.domain}};
+}
+
+// ---- the per-point tests (device) ----
+// one section's running result; `first` holds ~(index << 3 | reason) of the smallest bad index (0 = none) so that atomicMax finds
+// the minimum
+struct PkAcc { unsigned long long inf, bad, first; };
+
+__device__ inline bool pk_ge(const Fe& x, const uint64_t* m) {        // x >= m
+    for (int i = 3; i >= 0; i--) {
+        if (x.l[i] > m[i]) return true;
+        if (x.l[i] < m[i]) return false;
+    }
+    return true;
+}
+__device__ inline bool pk_zero(const Fe& x) { return (x.l[0] | x.l[1] | x.l[2] | x.l[3]) == 0; }
+
+// One point of a key in reference format (canonical Montgomery words) -> pk_reduce's state: 4 infinity by the loaders' rule (every
+// word of x zero; y is never read), 1 a coordinate word string >= q, 2 off the curve sqr(Y) == X^3 + b, 0 good -- and then *P is
+// the point in the field's internal form.  curve_b: 3 on G1, 3 / (9 + u) on the twist, internal form (pk_curve_b).
+template <class C>
+__device__ inline int pk_classify(const typename C::AffP& p, const typename C::El& curve_b, typename C::Aff* P) {
+    typedef typename C::Field F;
+    constexpr int NW = (int)(sizeof(typename C::AffP) / 32);      // 32-byte words of a point: 2 (G1), 4 (G2); the first half is x
+    const uint64_t q[4] = {FqParams::P0, FqParams::P1, FqParams::P2, FqParams::P3};
+    const Fe* w = reinterpret_cast<const Fe*>(&p);
+    typename C::AffP v;                                            // every word is loaded once, the y half only behind a finite x
+    Fe* vw = reinterpret_cast<Fe*>(&v);
+    bool inf = true, big = false;
+    for (int k = 0; k < NW / 2; k++) { vw[k] = w[k]; inf = inf && pk_zero(vw[k]); }
+    if (inf) return 4;
+    for (int k = NW / 2; k < NW; k++) vw[k] = w[k];
+    for (int k = 0; k < NW; k++) big = big || pk_ge(vw[k], q);
+    if (big) return 1;
+    *P = C::aff_to_internal(v);
+    if (!F::eq(F::sqr(P->y), F::add(F::mul(F::sqr(P->x), P->x), curve_b))) return 2;
+    return 0;
+}
+
+// st: 0 good, 1..3 the reason, 4 infinity.  Every lane of the wavefront arrives here (lanes past the end with st = 0).
+__device__ inline void pk_reduce(int st, uint64_t index, PkAcc* __restrict__ acc) {
+    const unsigned long long m_inf = __ballot(st == 4), m_bad = __ballot(st >= 1 && st <= 3);
+    if ((threadIdx.x & 63) == 0) {
+        if (m_inf) atomicAdd(&acc->inf, (unsigned long long)__popcll(m_inf));
+        if (m_bad) atomicAdd(&acc->bad, (unsigned long long)__popcll(m_bad));
+    }
+    if (st >= 1 && st <= 3) atomicMax(&acc->first, ~(((unsigned long long)index << 3) | (unsigned long long)st));
+}
+
+// ---- host ----
+// a section's result as the reports hold it: *first_bad = UINT64_MAX and *first_reason = 0 without a bad point
+inline void pk_decode(const PkAcc& a, uint64_t* inf, uint64_t* bad, uint64_t* first_bad, uint32_t* first_reason) {
+    const unsigned long long key = ~a.first;
+    *inf = a.inf;
+    *bad = a.bad;
+    *first_bad = a.first ? key >> 3 : UINT64_MAX;
+    *first_reason = a.first ? (uint32_t)(key & 7) : 0;
+}
+// pk_classify's curve_b for the two device curves (either may be nullptr); the twist's comes from pairing_consts
+int pk_curve_b(G1R29::El* b1, G2R29::El* b2);
+
+// reference-format bytes -> the host pairing's point; the reason it is bad (0 = good).  check = false: only the infinity rule
+uint32_t fixed_g1(const uint8_t* p, bool check, hostpair::G1A* out);
+uint32_t fixed_g2(const uint8_t* p, bool check, hostpair::G2A* out);
+hostpair::G1A gen1();
+hostpair::G2A gen2();
+// e(P1, Q1) == e(P2, Q2): two Miller values, one with a negated argument, one final exponentiation
+bool same_pairing(const hostpair::G1A& P1, const hostpair::G2A& Q1, const hostpair::G1A& P2, const hostpair::G2A& Q2);
+// e(P, G2) == e(G1, Q): P and Q hold the same logarithm
+inline bool same_log(const hostpair::G1A& P, const hostpair::G2A& Q) { return same_pairing(P, gen2(), gen1(), Q); }
+
+// out = the caller's 32 bytes, else the system's (os_random); WS_ERR_ARG with the entropy message if that fails
+int draw_seed(const uint8_t* caller32, uint8_t out[32]);
+
+typedef std::chrono::steady_clock Clock;
+inline double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
+
+// points per chunk of a streamed section: the switch `name` (PKCHECK_CHUNK, PKDELTA_CHUNK; default 2^18) within [64, 2^22]
+inline uint64_t key_chunk(const char* name) {
+    return std::min<uint64_t>(std::max<uint64_t>((uint64_t)tuning_get(name, 1 << 18), 64), (uint64_t)1 << 22);
+}
+// ... and the points the device buffers must hold for sections of at most `most` points
+inline uint64_t key_chunk_cap(uint64_t chunk, uint64_t most) { return std::min(chunk, std::max<uint64_t>(most, 1)); }
+// one range of a section to the device through the staging ring; a mapped key file gets the range back (KeySections::release)
+inline int stage_chunk(void* d_dst, const uint8_t* src, size_t bytes, hipStream_t s, void (*release)(const void*, size_t)) {
+    const int rc = upload_staged(d_dst, src, bytes, s);
+    if (!rc && release) release(src, bytes);
+    return rc;
+}
+
+// d_out[i] = rho_(base + i), i < n: 128 non-zero bits of the ChaCha20 block under key = seed32, counter = the global index
+int pkcheck_rho_dev(Fe* d_out, uint64_t n, uint64_t base, const uint8_t* seed32, hipStream_t s);
+
+// sum_j rho_j P_j over a section that goes through the device chunk by chunk: each resident chunk is summed by the ordinary MSM on
+// the caller's lane and queue, the partial sums are added on the host.  F = Fq: G1, Fq2: G2.
+inline int rho_msm(Lane& L, const Fe* d_rho, const Affine<Fq>* d_pts, uint64_t n, Jac<Fq>* out, hipStream_t s) {
+    return msm_g1_dev(L, d_rho, d_pts, n, WindowShard{}, out, s);
+}
+inline int rho_msm(Lane& L, const Fe* d_rho, const Affine<Fq2>* d_pts, uint64_t n, Jac<Fq2>* out, hipStream_t s) {
+    return msm_g2_dev(L, d_rho, d_pts, n, WindowShard{}, out, s);
+}
+inline hostpair::G1A rho_total(const std::vector<Jac<Fq>>& part) {
+    Jac<Fq> t;
+    g1_sum_host(reinterpret_cast<const uint8_t*>(part.data()), part.size(), reinterpret_cast<uint8_t*>(&t));
+    return hostpair::G1A{t.x, t.y, Fq::is_zero(t.z)};
+}
+inline hostpair::G2A rho_total(const std::vector<Jac<Fq2>>& part) {
+    Jac<Fq2> t;
+    g2_sum_host(reinterpret_cast<const uint8_t*>(part.data()), part.size(), reinterpret_cast<uint8_t*>(&t));
+    return hostpair::G2A{t.x, t.y, Fq2::is_zero(t.z)};
+}
+template <class F>
+struct RhoSum {
+    std::vector<Jac<F>> part;
+    int add(Lane& L, const Fe* d_rho, const Affine<F>* d_pts, uint64_t n, hipStream_t s) {
+        Jac<F> p;
+        const int rc = rho_msm(L, d_rho, d_pts, n, &p, s);
+        if (!rc) part.push_back(p);
+        return rc;
+    }
+    auto finish() const { return rho_total(part); }      // the host pairing's affine point
+};
+
+// ---- the workers behind the C ABI (cabi.hip opens the bytes, the sections or the file) ----
+int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* seed32, wsnark_pkey_report_t* out);
+int g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
+int g2_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
+int pkey_contribute_sections(const KeySections& S, const uint8_t* d32, uint8_t* out_pointsC, uint8_t* out_pointsH, uint8_t* out_delta1,
+                             uint8_t* out_delta2, wsnark_pkey_delta_report_t* rep);
+// S: the sections of the image pkey[0 .. len) (pkey_parse)
+int pkey_contribute_bytes(const KeySections& S, const uint8_t* pkey, size_t len, const uint8_t* d32, uint8_t* out, size_t out_cap,
+                          wsnark_pkey_delta_report_t* rep);
+// S: the sections of the mapped file F (keyfile_open of in_path)
+int pkey_contribute_file(const KeySections& S, const KeyFile& F, const char* in_path, const char* out_path, const uint8_t* d32,
+                         wsnark_pkey_delta_report_t* rep);
+int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const uint8_t* seed32, wsnark_pkey_delta_verdict_t* out);
+
+}  // namespace wsnark

@@ -28,6 +28,7 @@
 #include <unistd.h>
 
 #include "internal.h"
+#include "keybytes.h"
 
 namespace wsnark {
 
@@ -55,7 +56,7 @@ static int parse_container(const uint8_t* b, size_t len, KeySections* S) {
     memcpy(q, b + 32, 80);
     const uint64_t pA_ = q[0], lA = q[1], pB_ = q[2], lB = q[3], pA = q[4], pB1 = q[5], pB2 = q[6], pC = q[7], pH = q[8], flen = q[9];
     if (flen != len) { set_last_error("key container: the file is not as long as its header says (truncated?)"); return WS_ERR_FORMAT; }
-    if (nv == 0 || (uint64_t)np + 1 > nv) { set_last_error("proving key: nPublic + 1 > nVars"); return WS_ERR_FORMAT; }
+    if (int bad = key_vars_check(nv, np)) return bad;
     const uint64_t nC = (uint64_t)nv - np - 1;
     if (pA_ < w[1] || !range_ok(pA_, lA, len) || !range_ok(pB_, lB, len) || !range_ok(pA, (uint64_t)nv * 64, len) ||
         !range_ok(pB1, (uint64_t)nv * 64, len) || !range_ok(pB2, (uint64_t)nv * 128, len) || !range_ok(pC, nC * 64, len) ||

@@ -4,7 +4,8 @@
 // on the key's BYTES (reference format: canonical Montgomery words) -- after a load the points are in the device field's domain
 // and an unreduced coordinate can no longer be told from a reduced one.
 //
-//   per point (one lane each, kernels pkcheck_g1 / pkcheck_g2):
+//   per point (one lane each, kernels pkcheck_g1 / pkcheck_g2; the first three tests are keybytes.h: pk_classify, which the
+//   contribution's kernel applies too):
 //     x == 0 (all words of x)            infinity by the loader's own rule (msm_points_mask_kernel, Curve::aff_is_inf): counted,
 //                                        the rest of its bytes is not read -- the prover never reads them either
 //     a coordinate word string >= q      WSNARK_PK_UNREDUCED
@@ -20,50 +21,27 @@
 //   relations (host pairings, fp12_host.h):  e(beta1, G2) = e(G1, beta2),  e(delta1, G2) = e(G1, delta2),  and
 //     e(sum rho_j B1_j, G2) = e(G1, sum rho_j B2_j)  with rho_j = the first 128 bits of the ChaCha20 block (key = the seed,
 //     counter = the GLOBAL index j), made non-zero.  B1 and B2 go up chunk by chunk side by side, each pair of chunks is summed by
-//     the ordinary MSMs (msm_g1_dev / msm_g2_dev) over the chunk's rho, the partial sums are added on the host.
+//     the ordinary MSMs (msm_g1_dev / msm_g2_dev) over the chunk's rho, the partial sums are added on the host (keybytes.h: RhoSum).
 //     If B1_j = b_j G1 and B2_j = b'_j G2 the check passes with b != b' only if sum rho_j (b_j - b'_j) = 0 mod r: probability
 //     2^-128 over a seed the key's maker did not know.  A seed known in advance gives no soundness at all.
 #include <string.h>
 
-#include <algorithm>
-#include <chrono>
-#include <vector>
-
-#include "../../include/wsnark.h"
-#include "internal.h"
 #include "fp12.h"
-#include "fp12_host.h"
-#include "pkeycheck.h"
+#include "keybytes.h"
 
 namespace wsnark {
 
 using namespace hostpair;
 
-void g1_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out96);
-void g2_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out192);
-int os_random(uint8_t* out, size_t n);      // prove.hip: getrandom(2), else /dev/urandom
-
 // ---- device ----
+typedef Curve<Fq29> G1c;                    // products as calls: the kernel is bound by its loads, not by issue
 typedef G2R29 G2c;                          // Curve<Fp2T<Fq29>>: products as calls, as in pairing.hip (the chain is ~12 000 of them)
 
-__global__ __launch_bounds__(256) void pkcheck_g1_kernel(const Fe* __restrict__ pts, uint64_t n, uint64_t base,
-                                                           const PairConsts* __restrict__ K, PkAcc* __restrict__ acc) {
-    typedef Fq29 F;
+__global__ __launch_bounds__(256) void pkcheck_g1_kernel(const G1c::AffP* __restrict__ pts, uint64_t n, uint64_t base, G1c::El curve_b,
+                                                           PkAcc* __restrict__ acc) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int st = 0;
-    if (i < n) {
-        const Fe x = pts[2 * i];
-        if (pk_zero(x)) st = 4;
-        else {
-            const Fe y = pts[2 * i + 1];
-            if (pk_ge(x, K->q) || pk_ge(y, K->q)) st = 1;
-            else {
-                const F29 X = F::to_internal(x), Y = F::to_internal(y);
-                const F29 three = F::add(F::dbl(F::one()), F::one());
-                if (!F::eq(F::sqr(Y), F::add(F::mul(F::sqr(X), X), three))) st = 2;
-            }
-        }
-    }
+    G1c::Aff P;
+    const int st = i < n ? pk_classify<G1c>(pts[i], curve_b, &P) : 0;
     pk_reduce(st, base + i, acc);
 }
 
@@ -71,49 +49,37 @@ __global__ __launch_bounds__(256) void pkcheck_g1_kernel(const Fe* __restrict__ 
 // g = xi^((p - 1) / 6) (PairConsts::gamma1), and 6 x^2 = p - r = the Miller loop's T (PairConsts::ate, bit 126 leading)
 // (one wavefront per workgroup: the chain takes all 256 registers of a lane, so a SIMD holds one wavefront whatever the group size;
 // measured the same as 256-lane groups -- a 2^16 key's 65 537 finite points are 1025 wavefronts, two rounds on 1024 SIMDs either way)
-__global__ __launch_bounds__(64) void pkcheck_g2_kernel(const Fe* __restrict__ pts, uint64_t n, uint64_t base,
+__global__ __launch_bounds__(64) void pkcheck_g2_kernel(const G2c::AffP* __restrict__ pts, uint64_t n, uint64_t base, G2c::El curve_b,
                                                            const PairConsts* __restrict__ K, int mode, PkAcc* __restrict__ acc) {
     typedef Fq2d F;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int st = 0;
-    if (i < n) {
-        const Fe* p = pts + 4 * i;
-        const Fe x0 = p[0], x1 = p[1];
-        if (pk_zero(x0) && pk_zero(x1)) st = 4;
-        else {
-            const Fe y0 = p[2], y1 = p[3];
-            if (pk_ge(x0, K->q) || pk_ge(x1, K->q) || pk_ge(y0, K->q) || pk_ge(y1, K->q)) st = 1;
-            else {
-                const F2d X = F2d{Fq29::to_internal(x0), Fq29::to_internal(x1)}, Y = F2d{Fq29::to_internal(y0), Fq29::to_internal(y1)};
-                const F2d b2 = F2d{K->b2[0], K->b2[1]};
-                if (!F::eq(F::sqr(Y), F::add(F::mul(F::sqr(X), X), b2))) st = 2;
-                else {
-                    const G2c::Aff Q = G2c::Aff{X, Y};
-                    G2c::Pt a = G2c::infinity();
-                    if (mode == 0) {
+    G2c::Aff Q;
+    int st = i < n ? pk_classify<G2c>(pts[i], curve_b, &Q) : 0;
+    if (i < n && st == 0) {
+        const F2d X = Q.x, Y = Q.y;
+        G2c::Pt a = G2c::infinity();
+        if (mode == 0) {
 #pragma unroll 1
-                        for (int bit = 253; bit >= 0; bit--) {
-                            a = G2c::dbl(a);
-                            if ((K->r[bit >> 6] >> (bit & 63)) & 1) G2c::madd(a, Q, false);
-                        }
-                        if (!G2c::is_inf(a)) st = 3;
-                    } else {
-#pragma unroll 1
-                        for (int bit = 126; bit >= 0; bit--) {
-                            a = G2c::dbl(a);
-                            if ((K->ate[bit >> 6] >> (bit & 63)) & 1) G2c::madd(a, Q, false);
-                        }
-                        const F2d px = F::mul(F2d{X.c0, Fq29::neg(X.c1)}, F2d{K->gamma1[1][0], K->gamma1[1][1]});
-                        const F2d py = F::mul(F2d{Y.c0, Fq29::neg(Y.c1)}, F2d{K->gamma1[2][0], K->gamma1[2][1]});
-                        if (G2c::is_inf(a) || !F::eq(F::mul(px, a.zz), a.x) || !F::eq(F::mul(py, a.zzz), a.y)) st = 3;
-                    }
-                }
+            for (int bit = 253; bit >= 0; bit--) {
+                a = G2c::dbl(a);
+                if ((K->r[bit >> 6] >> (bit & 63)) & 1) G2c::madd(a, Q, false);
             }
+            if (!G2c::is_inf(a)) st = 3;
+        } else {
+#pragma unroll 1
+            for (int bit = 126; bit >= 0; bit--) {
+                a = G2c::dbl(a);
+                if ((K->ate[bit >> 6] >> (bit & 63)) & 1) G2c::madd(a, Q, false);
+            }
+            const F2d px = F::mul(F2d{X.c0, Fq29::neg(X.c1)}, F2d{K->gamma1[1][0], K->gamma1[1][1]});
+            const F2d py = F::mul(F2d{Y.c0, Fq29::neg(Y.c1)}, F2d{K->gamma1[2][0], K->gamma1[2][1]});
+            if (G2c::is_inf(a) || !F::eq(F::mul(px, a.zz), a.x) || !F::eq(F::mul(py, a.zzz), a.y)) st = 3;
         }
     }
     pk_reduce(st, base + i, acc);
 }
 
+struct PkSeed { uint32_t w[8]; };
 // rho_j for j = base .. base + n: words 0..3 of the ChaCha20 block (RFC 8439 state layout) under key = seed, 64-bit counter = j
 __device__ inline uint32_t pk_rotl(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
 #define PK_QR(a, b, c, d)                          \
@@ -153,11 +119,39 @@ int pkcheck_rho_dev(Fe* d_out, uint64_t n, uint64_t base, const uint8_t* seed32,
     return WS_OK;
 }
 
+// ---- host: a key's shape, the seed ----
+int key_vars_check(uint32_t nv, uint32_t np) {
+    if (nv == 0 || (uint64_t)np + 1 > nv) { set_last_error("proving key: nPublic + 1 > nVars"); return WS_ERR_FORMAT; }
+    return WS_OK;
+}
+int key_shape_check(const KeySections& S) {
+    const uint32_t dom = S.domain;
+    if (int rc = key_vars_check(S.n_vars, S.n_public)) return rc;
+    if (dom < 2 || (dom & (dom - 1)) || dom > (1u << 27)) { set_last_error("proving key: domainSize must be a power of two in [2, 2^27]"); return WS_ERR_SIZE; }
+    const KeyCounts c = key_counts(S);
+    if (S.lenPA < c[0] * 64 || S.lenPB1 < c[1] * 64 || S.lenPB2 < c[2] * 128 || S.lenPC < c[3] * 64 || S.lenPH < c[4] * 64) {
+        set_last_error("proving key: a point section is shorter than its header-implied size");
+        return WS_ERR_FORMAT;
+    }
+    return WS_OK;
+}
+int draw_seed(const uint8_t* caller32, uint8_t out[32]) {
+    if (caller32) memcpy(out, caller32, 32);
+    else if (os_random(out, 32)) { set_last_error("no entropy: getrandom(2) and /dev/urandom both failed"); return WS_ERR_ARG; }
+    return WS_OK;
+}
+int pk_curve_b(G1R29::El* b1, G2R29::El* b2) {
+    if (b1) *b1 = Fq29::to_internal(Fq::to_mont(Fe{{3, 0, 0, 0}}));
+    if (b2) {
+        const PairConsts* K = nullptr;
+        if (int rc = pairing_consts(&K)) return rc;
+        *b2 = G2R29::El{K->b2[0], K->b2[1]};
+    }
+    return WS_OK;
+}
+
 // ---- host: the five fixed points and the pairings ----
 namespace {
-typedef std::chrono::steady_clock Clock;
-double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
-
 bool h_zero(const Fe& x) { return (x.l[0] | x.l[1] | x.l[2] | x.l[3]) == 0; }
 bool h_reduced(const Fe& x) {
     const Fe q = Fq::modulus();
@@ -199,12 +193,12 @@ G2A gen2() {
                   Fq::to_mont(Fe{{0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull}})},
                false};
 }
-// e(P, G2) == e(G1, Q): two Miller values, one with a negated argument, one final exponentiation
-bool same_log(const G1A& P, const G2A& Q) {
-    G1A ng = gen1();
-    ng.y = Fq::neg(ng.y);
+// e(P1, Q1) == e(P2, Q2): two Miller values, one with a negated argument, one final exponentiation
+bool same_pairing(const G1A& P1, const G2A& Q1, const G1A& P2, const G2A& Q2) {
+    G1A n2 = P2;
+    n2.y = Fq::neg(n2.y);
     F12 m1, m2;
-    if (!miller_ate(gen2(), P, &m1) || !miller_ate(Q, ng, &m2)) return false;      // (a degenerate step: Q is not of order r)
+    if (!miller_ate(Q1, P1, &m1) || !miller_ate(Q2, n2, &m2)) return false;      // (a degenerate step: a Q not of order r)
     return f12_is_one(final_exponentiation(f12_mul(m1, m2)));
 }
 
@@ -214,28 +208,18 @@ int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* see
     if (!out || (flags & ~(uint32_t)(WSNARK_PKCHECK_POINTS | WSNARK_PKCHECK_RELATIONS))) return WS_ERR_ARG;
     if (!flags) flags = WSNARK_PKCHECK_POINTS | WSNARK_PKCHECK_RELATIONS;
     const bool do_points = (flags & WSNARK_PKCHECK_POINTS) != 0, do_rel = (flags & WSNARK_PKCHECK_RELATIONS) != 0;
-    // what the loaders reject (prove.hip: pkey_load_sections), with their codes
-    const uint32_t nv = S.n_vars, np = S.n_public, dom = S.domain;
-    if (nv == 0 || (uint64_t)np + 1 > nv) { set_last_error("proving key: nPublic + 1 > nVars"); return WS_ERR_FORMAT; }
-    if (dom < 2 || (dom & (dom - 1)) || dom > (1u << 27)) { set_last_error("proving key: domainSize must be a power of two in [2, 2^27]"); return WS_ERR_SIZE; }
-    const uint64_t nC = (uint64_t)nv - np - 1;
-    if (S.lenPA < (uint64_t)nv * 64 || S.lenPB1 < (uint64_t)nv * 64 || S.lenPB2 < (uint64_t)nv * 128 || S.lenPC < nC * 64 ||
-        S.lenPH < (uint64_t)dom * 64) {
-        set_last_error("proving key: a point section is shorter than its header-implied size");
-        return WS_ERR_FORMAT;
-    }
-    const PairConsts* K = nullptr;
-    int rc = pairing_consts(&K);
+    int rc = key_shape_check(S);      // what the loaders reject, with their codes
     if (rc) return rc;
+    const PairConsts* K = nullptr;
+    G1c::El b1;
+    G2c::El b2;
+    if ((rc = pairing_consts(&K)) || (rc = pk_curve_b(&b1, &b2))) return rc;
     uint8_t seed[32];
-    if (do_rel) {
-        if (seed32) memcpy(seed, seed32, 32);
-        else if (os_random(seed, 32)) { set_last_error("no entropy: getrandom(2) and /dev/urandom both failed"); return WS_ERR_ARG; }
-    }
+    if (do_rel && (rc = draw_seed(seed32, seed))) return rc;
     const auto t_begin = Clock::now();
     wsnark_pkey_report_t R;
     memset(&R, 0, sizeof R);
-    const uint64_t counts[5] = {nv, nv, nv, nC, dom};
+    const KeyCounts counts = key_counts(S);
     for (int k = 0; k < 5; k++) { R.points[k] = counts[k]; R.first_bad[k] = UINT64_MAX; }
 
     G1A alfa1, beta1, delta1;
@@ -246,16 +230,15 @@ int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* see
     R.fixed_reason[3] = fixed_g2(S.beta2, do_points, &beta2);
     R.fixed_reason[4] = fixed_g2(S.delta2, do_points, &delta2);
 
-    uint64_t chunk = (uint64_t)tuning_get("PKCHECK_CHUNK", 1 << 18);
-    chunk = chunk < 64 ? 64 : chunk > ((uint64_t)1 << 22) ? (uint64_t)1 << 22 : chunk;
+    const uint64_t chunk = key_chunk("PKCHECK_CHUNK");
     const int sub_mode = tuning_get("PKCHECK_SUBGROUP", 0) == 1 ? 1 : 0;
-    const uint64_t cap = std::min<uint64_t>(chunk, std::max<uint64_t>(std::max<uint64_t>(nv, dom), 1));
+    const uint64_t cap = key_chunk_cap(chunk, std::max(counts[WSNARK_PK_A], counts[WSNARK_PK_H]));
 
     PkAcc h_acc[5];
     memset(h_acc, 0, sizeof h_acc);
     double ms_points = 0, ms_sums = 0;
-    std::vector<Jac<Fq>> part1;
-    std::vector<Jac<Fq2>> part2;
+    RhoSum<Fq> sum1;
+    RhoSum<Fq2> sum2;
     bool sums_on = do_rel;          // off from the first chunk on in which B1 or B2 has a bad point
     {
         LaneLock L = acquire_lane(X);   // (released before the pairings: they need no lane)
@@ -270,17 +253,11 @@ int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* see
         WS_HIP_CHECK(hipMemsetAsync(d_small.as<uint8_t>() + o_acc, 0, 5 * sizeof(PkAcc), s));
         const PairConsts* d_K = d_small.as<PairConsts>();
         PkAcc* d_acc = reinterpret_cast<PkAcc*>(d_small.as<uint8_t>() + o_acc);
-        PkSeed sd;
-        if (do_rel) memcpy(sd.w, seed, 32);
 
-        auto stage = [&](void* dst, const uint8_t* src, size_t bytes) -> int {
-            const int r = upload_staged(dst, src, bytes, s);
-            if (!r && S.release) S.release(src, bytes);
-            return r;
-        };
+        auto stage = [&](void* dst, const uint8_t* src, size_t bytes) { return stage_chunk(dst, src, bytes, s, S.release); };
         auto run_g1 = [&](int sec, uint64_t lo, uint64_t n) -> int {
             X->timer.begin("pkcheck_g1", s);
-            hipLaunchKernelGGL(pkcheck_g1_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_g1.as<Fe>(), n, lo, d_K, d_acc + sec);
+            hipLaunchKernelGGL(pkcheck_g1_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_g1.as<G1c::AffP>(), n, lo, b1, d_acc + sec);
             WS_HIP_CHECK(hipGetLastError());
             X->timer.end(s);
             return WS_OK;
@@ -299,7 +276,7 @@ int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* see
                     if ((rc = stage(d_g2.p, S.B2 + lo * 128, (size_t)n * 128))) return rc;
                     if (do_points) {
                         X->timer.begin(sub_mode ? "pkcheck_g2_psi" : "pkcheck_g2", s);
-                        hipLaunchKernelGGL(pkcheck_g2_kernel, dim3(ceil_div_u64(n, 64)), dim3(64), 0, s, d_g2.as<Fe>(), n, lo, d_K, sub_mode,
+                        hipLaunchKernelGGL(pkcheck_g2_kernel, dim3(ceil_div_u64(n, 64)), dim3(64), 0, s, d_g2.as<G2c::AffP>(), n, lo, b2, d_K, sub_mode,
                                            d_acc + WSNARK_PK_B2);
                         WS_HIP_CHECK(hipGetLastError());
                         X->timer.end(s);
@@ -314,14 +291,9 @@ int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* see
                     WS_HIP_CHECK(hipStreamSynchronize(s));
                     ms_points += ms_since(t0);
                     t0 = Clock::now();
-                    hipLaunchKernelGGL(pkcheck_rho_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_rho.as<Fe>(), n, lo, sd);
-                    WS_HIP_CHECK(hipGetLastError());
-                    Jac<Fq> p1;
-                    Jac<Fq2> p2;
-                    if ((rc = msm_g1_dev(*L, d_rho.as<Fe>(), d_g1.as<Affine<Fq>>(), n, WindowShard{}, &p1, s))) return rc;
-                    if ((rc = msm_g2_dev(*L, d_rho.as<Fe>(), d_g2.as<Affine<Fq2>>(), n, WindowShard{}, &p2, s))) return rc;
-                    part1.push_back(p1);
-                    part2.push_back(p2);
+                    if ((rc = pkcheck_rho_dev(d_rho.as<Fe>(), n, lo, seed, s))) return rc;
+                    if ((rc = sum1.add(*L, d_rho.as<Fe>(), d_g1.as<Affine<Fq>>(), n, s))) return rc;
+                    if ((rc = sum2.add(*L, d_rho.as<Fe>(), d_g2.as<Affine<Fq2>>(), n, s))) return rc;
                     ms_sums += ms_since(t0);
                 } else {
                     ms_points += ms_since(t0);      // (the kernels of this chunk are still running: the next lap, or the drain below, has them)
@@ -335,15 +307,7 @@ int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* see
             ms_points += ms_since(t0);
         }
     }
-    for (int k = 0; k < 5; k++) {
-        R.infinity[k] = h_acc[k].inf;
-        R.bad[k] = h_acc[k].bad;
-        if (h_acc[k].first) {
-            const unsigned long long key = ~h_acc[k].first;
-            R.first_bad[k] = key >> 3;
-            R.first_reason[k] = (uint32_t)(key & 7);
-        }
-    }
+    for (int k = 0; k < 5; k++) pk_decode(h_acc[k], &R.infinity[k], &R.bad[k], &R.first_bad[k], &R.first_reason[k]);
 
     const auto t_pair = Clock::now();
     if (do_rel) {
@@ -356,12 +320,8 @@ int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* see
             if (!same_log(delta1, delta2)) R.relations_bad |= 2;
         }
         if (sums_on && !R.bad[WSNARK_PK_B1] && !R.bad[WSNARK_PK_B2]) {
-            Jac<Fq> s1;
-            Jac<Fq2> s2;
-            g1_sum_host(reinterpret_cast<const uint8_t*>(part1.data()), part1.size(), reinterpret_cast<uint8_t*>(&s1));
-            g2_sum_host(reinterpret_cast<const uint8_t*>(part2.data()), part2.size(), reinterpret_cast<uint8_t*>(&s2));
             R.relations_run |= 4;
-            if (!same_log(G1A{s1.x, s1.y, Fq::is_zero(s1.z)}, G2A{s2.x, s2.y, Fq2::is_zero(s2.z)})) R.relations_bad |= 4;
+            if (!same_log(sum1.finish(), sum2.finish())) R.relations_bad |= 4;
         }
     }
     R.ms[0] = ms_points;

@@ -11,8 +11,9 @@
 //     it once into non-adjacent form (digits -1, 0, 1; on average 1/3 of them non-zero: ~85 additions behind the 253 doublings
 //     instead of ~127) and passes the two digit masks in the argument block, so the loop's branches are scalar branches and no
 //     wavefront diverges on them.  A negative digit is madd's negate flag.
-//     Before the chain each lane applies the audit's two G1 tests (every coordinate < q, the curve equation); counts and the first
-//     bad index are reduced exactly as the audit does (pk_reduce).  x == 0 is infinity by the loaders' rule: copied through.
+//     Before the chain each lane classifies its point with the audit's own code (keybytes.h: pk_classify -- infinity by the loaders'
+//     rule, every coordinate < q, the curve equation); counts and the first bad index are reduced by the audit's pk_reduce and read
+//     by its pk_decode.  An infinity point is copied through.
 //     Products per finite point on G1 (counted from curve.h's formulas, squarings as products, the fused Y3 as two): input tests
 //     2 + 3, chain 253 x 9 (dbl) + ~85 x 11 (madd), normalisation 363 (Fermat) + 5, output 2: ~3600, the inversion ~10 % of it.
 //   normalisation (PKDELTA_NORM): 0 = one Fermat inversion per lane; 1 = ONE inversion per workgroup: a product tree over the
@@ -27,7 +28,7 @@
 //   wsnark_pkey_delta_verify: what the NEXT participant checks -- the new key is the old one under a new delta.  bit 0: a memcmp of
 //     everything a contribution must not touch; bit 1: e(delta1', G2) = e(G1, delta2'); bits 2, 3: with rho_j the audit's (ChaCha20,
 //     the global index) e(sum rho_j C'_j, delta2') = e(sum rho_j C_j, delta2), and the same for hExps, by the ordinary MSMs chunk by
-//     chunk and two host Miller loops each; bit 4: delta2' != delta2.
+//     chunk (keybytes.h: RhoSum) and two host Miller loops each (same_pairing); bit 4: delta2' != delta2.
 #include <errno.h>
 #include <fcntl.h>
 #include <string.h>
@@ -35,22 +36,11 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <algorithm>
-#include <chrono>
-#include <vector>
-
-#include "../../include/wsnark.h"
-#include "internal.h"
-#include "fp12.h"
-#include "fp12_host.h"
-#include "pkeycheck.h"
+#include "keybytes.h"
 
 namespace wsnark {
 
 using namespace hostpair;
-
-void g1_sum_host(const uint8_t* pts, uint64_t count, uint8_t* out96);
-int os_random(uint8_t* out, size_t n);      // prove.hip
 
 // ---- device ----
 // the scalar in non-adjacent form: digit i is non-zero iff bit i of nz, negative iff bit i of neg; top = index of the leading digit
@@ -63,26 +53,13 @@ __global__ __launch_bounds__(256) void scale_points_kernel(const typename C::Aff
                                                              PkAcc* __restrict__ acc) {
     typedef typename C::Field F;
     typedef typename C::El El;
-    constexpr int NW = (int)(sizeof(typename C::AffP) / 32);      // 32-byte words of a point: 2 (G1), 4 (G2); the first half is x
-    const uint64_t q[4] = {FqParams::P0, FqParams::P1, FqParams::P2, FqParams::P3};
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int st = 0;               // pk_reduce's states: 0 good, 1 unreduced, 2 off the curve, 4 infinity
     bool live = false;        // a good finite point and a non-zero scalar: this lane runs the chain
     typename C::Aff P = typename C::Aff{F::zero(), F::zero()};
     if (i < n) {
-        const Fe* w = reinterpret_cast<const Fe*>(pts + i);
-        bool inf = true, big = false;
-        for (int k = 0; k < NW / 2; k++) inf = inf && pk_zero(w[k]);
-        if (inf) st = 4;
-        else {
-            for (int k = 0; k < NW; k++) big = big || pk_ge(w[k], q);
-            if (big) st = 1;
-            else {
-                P = C::aff_to_internal(pts[i]);
-                if (!F::eq(F::sqr(P.y), F::add(F::mul(F::sqr(P.x), P.x), curve_b))) st = 2;
-                else live = D.top >= 0;
-            }
-        }
+        st = pk_classify<C>(pts[i], curve_b, &P);
+        live = st == 0 && D.top >= 0;
     }
     pk_reduce(st, base + i, acc);
 
@@ -154,9 +131,6 @@ __global__ __launch_bounds__(256) void scale_points_kernel(const typename C::Aff
 
 // ---- host ----
 namespace {
-typedef std::chrono::steady_clock Clock;
-double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
-
 // a wipe the compiler cannot drop: the stores are volatile
 void wipe(void* p, size_t n) {
     volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
@@ -185,26 +159,13 @@ void recode_naf(const Fe& k, ScaleDigits* D) {
     wipe(w, sizeof w);
 }
 
-template <class C> struct ScaleCurve;
-template <> struct ScaleCurve<G1R29> {
-    static int b(G1R29::El* out) { *out = Fq29::to_internal(Fq::to_mont(Fe{{3, 0, 0, 0}})); return WS_OK; }
-    static const char* name(int norm) { return norm ? "scale_points_g1_shared_inv" : "scale_points_g1"; }
-};
-template <> struct ScaleCurve<G2R29> {
-    static int b(G2R29::El* out) {
-        const PairConsts* K = nullptr;
-        const int rc = pairing_consts(&K);
-        if (rc) return rc;
-        *out = G2R29::El{K->b2[0], K->b2[1]};
-        return WS_OK;
-    }
-    static const char* name(int norm) { return norm ? "scale_points_g2_shared_inv" : "scale_points_g2"; }
-};
-
-uint64_t delta_chunk() {
-    const uint64_t c = (uint64_t)tuning_get("PKDELTA_CHUNK", 1 << 18);
-    return c < 64 ? 64 : c > ((uint64_t)1 << 22) ? (uint64_t)1 << 22 : c;
+inline int curve_b(G1R29::El* out) { return pk_curve_b(out, nullptr); }
+inline int curve_b(G2R29::El* out) { return pk_curve_b(nullptr, out); }
+template <class C> const char* scale_name(int norm) {
+    constexpr bool g1 = sizeof(typename C::AffP) == 64;
+    return g1 ? (norm ? "scale_points_g1_shared_inv" : "scale_points_g1") : (norm ? "scale_points_g2_shared_inv" : "scale_points_g2");
 }
+
 // the shipped normalisation: DESIGN.md section "Phase-2 contribution" has both measured
 int delta_norm() { return tuning_get("PKDELTA_NORM", 1) == 0 ? 0 : 1; }
 
@@ -277,11 +238,10 @@ int scale_stream(Context* X, ScaleRing& R, const uint8_t* src, uint64_t n, uint6
         const int b = (int)(R.k++ & 1);
         // buffers b were last used by the chunk before the previous one: its download has been waited for (drain below, one lap ago),
         // so its kernel has read d_in[b], the copy has read d_out[b], and the host has emptied pin[b]
-        if ((rc = upload_staged(R.d_in[b].p, src + lo * psz, (size_t)m * psz, R.sc))) return rc;
-        if (release) release(src + lo * psz, (size_t)m * psz);
+        if ((rc = stage_chunk(R.d_in[b].p, src + lo * psz, (size_t)m * psz, R.sc, release))) return rc;
         WS_HIP_CHECK(hipEventRecord(R.ev_up[b], R.sc));
         WS_HIP_CHECK(hipStreamWaitEvent(R.s, R.ev_up[b], 0));
-        X->timer.begin(ScaleCurve<C>::name(norm), R.s);
+        X->timer.begin(scale_name<C>(norm), R.s);
         hipLaunchKernelGGL(scale_points_kernel<C>, dim3(ceil_div_u64(m, 256)), dim3(256), 0, R.s, R.d_in[b].as<AffP>(), m, lo, D, cb, norm,
                            R.d_out[b].as<AffP>(), d_acc);
         WS_HIP_CHECK(hipGetLastError());
@@ -309,11 +269,11 @@ int scale_batch(const void* points, uint64_t n, const void* k32, void* out) {
     if (!points || !k32 || !out) return WS_ERR_ARG;
     if (n > ((uint64_t)1 << 28)) return WS_ERR_SIZE;
     typename C::El cb;
-    int rc = ScaleCurve<C>::b(&cb);
+    int rc = curve_b(&cb);
     if (rc) return rc;
     ScaleDigits D;
     recode_naf(load_scalar((const uint8_t*)k32), &D);
-    const uint64_t chunk = delta_chunk();
+    const uint64_t chunk = key_chunk("PKDELTA_CHUNK");
     PkAcc h_acc;
     {
         LaneLock L = acquire_lane(X);
@@ -329,24 +289,11 @@ int scale_batch(const void* points, uint64_t n, const void* k32, void* out) {
         WS_HIP_CHECK(hipMemcpyAsync(&h_acc, d_acc.p, sizeof h_acc, hipMemcpyDeviceToHost, L->stream));
         WS_HIP_CHECK(hipStreamSynchronize(L->stream));
     }
-    if (h_acc.bad) {
-        const unsigned long long key = ~h_acc.first;
-        set_last_error("scale_batch: " + std::to_string(h_acc.bad) + " point(s) unreduced or off the curve, the first at index " +
-                       std::to_string(key >> 3));
-        return WS_ERR_FORMAT;
-    }
-    return WS_OK;
-}
-
-// what the loaders reject, with their codes (prove.hip: pkey_load_sections; pkeycheck.hip does the same)
-int loader_checks(const KeySections& S) {
-    const uint32_t nv = S.n_vars, np = S.n_public, dom = S.domain;
-    if (nv == 0 || (uint64_t)np + 1 > nv) { set_last_error("proving key: nPublic + 1 > nVars"); return WS_ERR_FORMAT; }
-    if (dom < 2 || (dom & (dom - 1)) || dom > (1u << 27)) { set_last_error("proving key: domainSize must be a power of two in [2, 2^27]"); return WS_ERR_SIZE; }
-    const uint64_t nC = (uint64_t)nv - np - 1;
-    if (S.lenPA < (uint64_t)nv * 64 || S.lenPB1 < (uint64_t)nv * 64 || S.lenPB2 < (uint64_t)nv * 128 || S.lenPC < nC * 64 ||
-        S.lenPH < (uint64_t)dom * 64) {
-        set_last_error("proving key: a point section is shorter than its header-implied size");
+    uint64_t inf, bad, first;
+    uint32_t reason;
+    pk_decode(h_acc, &inf, &bad, &first, &reason);
+    if (bad) {
+        set_last_error("scale_batch: " + std::to_string(bad) + " point(s) unreduced or off the curve, the first at index " + std::to_string(first));
         return WS_ERR_FORMAT;
     }
     return WS_OK;
@@ -361,11 +308,10 @@ struct Secret {
 // everything that can fail before a byte is written
 int contribute_prepare(const KeySections& S, const uint8_t* d32, Secret* K) {
     if (!ctx()) return WS_ERR_NOINIT;
-    int rc = loader_checks(S);
+    int rc = key_shape_check(S);
     if (rc) return rc;
     uint8_t raw[32];
-    if (d32) memcpy(raw, d32, 32);
-    else if (os_random(raw, 32)) { set_last_error("no entropy: getrandom(2) and /dev/urandom both failed"); return WS_ERR_ARG; }
+    if ((rc = draw_seed(d32, raw))) return rc;
     K->d = load_scalar(raw);
     wipe(raw, sizeof raw);
     if (Fr::is_zero(K->d)) { set_last_error("contribution: d = 0 mod r"); return WS_ERR_ARG; }
@@ -381,7 +327,8 @@ int contribute_run(const KeySections& S, const Secret& K, const Sink& outC, cons
     const auto t_begin = Clock::now();
     wsnark_pkey_delta_report_t R;
     memset(&R, 0, sizeof R);
-    const uint64_t counts[2] = {(uint64_t)S.n_vars - S.n_public - 1, S.domain};
+    const KeyCounts all = key_counts(S);
+    const uint64_t counts[2] = {all[WSNARK_PK_C], all[WSNARK_PK_H]};
     for (int k = 0; k < 2; k++) { R.points[k] = counts[k]; R.first_bad[k] = UINT64_MAX; }
 
     // delta1' = d delta1, delta2' = d delta2: the host curve of proof assembly
@@ -406,15 +353,15 @@ int contribute_run(const KeySections& S, const Secret& K, const Sink& outC, cons
     if (fixed_ok) {
         t0 = Clock::now();
         G1R29::El cb;
-        int rc = ScaleCurve<G1R29>::b(&cb);
+        int rc = curve_b(&cb);
         if (rc) return rc;
-        const uint64_t chunk = delta_chunk();
+        const uint64_t chunk = key_chunk("PKDELTA_CHUNK");
         LaneLock L = acquire_lane(X);
         DevBuf d_acc;
         WS_HIP_CHECK(d_acc.alloc(sizeof h_acc));
         WS_HIP_CHECK(hipMemsetAsync(d_acc.p, 0, sizeof h_acc, L->stream));
         ScaleRing ring;
-        const uint64_t cap = std::min<uint64_t>(chunk, std::max<uint64_t>(std::max(counts[0], counts[1]), 1));
+        const uint64_t cap = key_chunk_cap(chunk, std::max(counts[0], counts[1]));
         if ((rc = ring.init(L->stream, L->stream_copy, (size_t)cap * 64))) return rc;
         const int norm = delta_norm();
         if ((rc = scale_stream<G1R29>(X, ring, S.Cpts, counts[0], chunk, K.inv_digits, cb, norm, outC, d_acc.as<PkAcc>(), S.release))) return rc;
@@ -426,13 +373,7 @@ int contribute_run(const KeySections& S, const Secret& K, const Sink& outC, cons
     }
     bool ok = fixed_ok;
     for (int k = 0; k < 2; k++) {
-        R.infinity[k] = h_acc[k].inf;
-        R.bad[k] = h_acc[k].bad;
-        if (h_acc[k].first) {
-            const unsigned long long key = ~h_acc[k].first;
-            R.first_bad[k] = key >> 3;
-            R.first_reason[k] = (uint32_t)(key & 7);
-        }
+        pk_decode(h_acc[k], &R.infinity[k], &R.bad[k], &R.first_bad[k], &R.first_reason[k]);
         ok = ok && R.bad[k] == 0;
     }
     R.ok = ok ? 1 : 0;
@@ -441,15 +382,6 @@ int contribute_run(const KeySections& S, const Secret& K, const Sink& outC, cons
     R.ms[2] = ms_since(t_begin);
     *rep = R;
     return WS_OK;
-}
-
-// e(P1, Q1) == e(P2, Q2): two Miller values, one with a negated argument, one final exponentiation
-bool same_pairing(const G1A& P1, const G2A& Q1, const G1A& P2, const G2A& Q2) {
-    G1A n2 = P2;
-    n2.y = Fq::neg(n2.y);
-    F12 m1, m2;
-    if (!miller_ate(Q1, P1, &m1) || !miller_ate(Q2, n2, &m2)) return false;
-    return f12_is_one(final_exponentiation(f12_mul(m1, m2)));
 }
 }  // namespace
 
@@ -469,12 +401,9 @@ int pkey_contribute_sections(const KeySections& S, const uint8_t* d32, uint8_t* 
 }
 
 // the key's image: a copy of the input with the four parts overwritten
-int pkey_contribute_bytes(const uint8_t* pkey, size_t len, const uint8_t* d32, uint8_t* out, size_t out_cap, wsnark_pkey_delta_report_t* rep) {
-    if (!ctx()) return WS_ERR_NOINIT;
-    if (!rep || !out) return WS_ERR_ARG;
-    KeySections S;
-    int rc = pkey_parse(pkey, len, &S);
-    if (rc) return rc;
+int pkey_contribute_bytes(const KeySections& S, const uint8_t* pkey, size_t len, const uint8_t* d32, uint8_t* out, size_t out_cap,
+                          wsnark_pkey_delta_report_t* rep) {
+    int rc;
     if (out_cap < len) { set_last_error("contribution: the output buffer is smaller than the key"); return WS_ERR_SIZE; }
     Secret K;
     if ((rc = contribute_prepare(S, d32, &K))) return rc;
@@ -491,13 +420,9 @@ int pkey_contribute_bytes(const uint8_t* pkey, size_t len, const uint8_t* d32, u
     return rc;
 }
 
-int pkey_contribute_file(const char* in_path, const char* out_path, const uint8_t* d32, wsnark_pkey_delta_report_t* rep) {
-    if (!ctx()) return WS_ERR_NOINIT;
-    if (!in_path || !out_path || !rep) return WS_ERR_ARG;
-    KeyFile F;
-    KeySections S;
-    int rc = keyfile_open(in_path, &F, &S);
-    if (rc) return rc;
+int pkey_contribute_file(const KeySections& S, const KeyFile& F, const char* in_path, const char* out_path, const uint8_t* d32,
+                         wsnark_pkey_delta_report_t* rep) {
+    int rc;
     struct stat si, so;
     if (strcmp(in_path, out_path) == 0 ||
         (fstat(F.fd, &si) == 0 && stat(out_path, &so) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)) {
@@ -513,8 +438,8 @@ int pkey_contribute_file(const char* in_path, const char* out_path, const uint8_
         ~Closer() { close(fd); if (!keep) unlink(path); }
     } closer{fd, out_path, false};
     // everything but C and hExps as it is, in pieces that go back to the kernel as soon as they are written
-    const uint64_t nC = (uint64_t)S.n_vars - S.n_public - 1;
-    uint64_t skip[2][2] = {{(uint64_t)(S.Cpts - F.base), nC * 64}, {(uint64_t)(S.H - F.base), (uint64_t)S.domain * 64}};
+    const KeyCounts counts = key_counts(S);
+    uint64_t skip[2][2] = {{(uint64_t)(S.Cpts - F.base), counts[WSNARK_PK_C] * 64}, {(uint64_t)(S.H - F.base), counts[WSNARK_PK_H] * 64}};
     if (skip[1][0] < skip[0][0]) std::swap(skip[0], skip[1]);
     Sink whole;
     whole.fd = fd;
@@ -554,10 +479,9 @@ int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const
     if (!X) return WS_ERR_NOINIT;
     if (!out) return WS_ERR_ARG;
     int rc;
-    if ((rc = loader_checks(O)) || (rc = loader_checks(N))) return rc;
+    if ((rc = key_shape_check(O)) || (rc = key_shape_check(N))) return rc;
     uint8_t seed[32];
-    if (seed32) memcpy(seed, seed32, 32);
-    else if (os_random(seed, 32)) { set_last_error("no entropy: getrandom(2) and /dev/urandom both failed"); return WS_ERR_ARG; }
+    if ((rc = draw_seed(seed32, seed))) return rc;
     const auto t_begin = Clock::now();
     wsnark_pkey_delta_verdict_t V;
     memset(&V, 0, sizeof V);
@@ -601,43 +525,37 @@ int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const
     if (same_shape && (V.checks_run & 2) && !(V.checks_bad & 2)) {
         const auto t0 = Clock::now();
         fixed_g2(O.delta2, false, &o2);
-        const uint64_t counts[2] = {(uint64_t)O.n_vars - O.n_public - 1, O.domain};
+        const KeyCounts all = key_counts(O);
+        const uint64_t counts[2] = {all[WSNARK_PK_C], all[WSNARK_PK_H]};
         const uint8_t* src[2][2] = {{O.Cpts, N.Cpts}, {O.H, N.H}};
-        Jac<Fq> sums[2][2];
+        G1A sums[2][2];
         {
-            const uint64_t chunk = delta_chunk();
-            const uint64_t cap = std::min<uint64_t>(chunk, std::max<uint64_t>(std::max(counts[0], counts[1]), 1));
+            const uint64_t chunk = key_chunk("PKDELTA_CHUNK");
+            const uint64_t cap = key_chunk_cap(chunk, std::max(counts[0], counts[1]));
             LaneLock L = acquire_lane(X);
             hipStream_t s = L->stream;
             DevBuf d_pts, d_rho;
             WS_HIP_CHECK(d_pts.alloc((size_t)cap * 64));
             WS_HIP_CHECK(d_rho.alloc((size_t)cap * 32));
             for (int sec = 0; sec < 2; sec++) {
-                std::vector<Jac<Fq>> part[2];
+                RhoSum<Fq> part[2];
                 for (uint64_t lo = 0; lo < counts[sec]; lo += chunk) {
                     const uint64_t n = std::min<uint64_t>(chunk, counts[sec] - lo);
                     if ((rc = pkcheck_rho_dev(d_rho.as<Fe>(), n, lo, seed, s))) return rc;      // the SAME rho_j for the old and the new point j
                     for (int which = 0; which < 2; which++) {
-                        const KeySections& Sx = which ? N : O;
-                        if ((rc = upload_staged(d_pts.p, src[sec][which] + lo * 64, (size_t)n * 64, s))) return rc;
-                        if (Sx.release) Sx.release(src[sec][which] + lo * 64, (size_t)n * 64);
-                        Jac<Fq> p;
-                        if ((rc = msm_g1_dev(*L, d_rho.as<Fe>(), d_pts.as<Affine<Fq>>(), n, WindowShard{}, &p, s))) return rc;
-                        part[which].push_back(p);
+                        if ((rc = stage_chunk(d_pts.p, src[sec][which] + lo * 64, (size_t)n * 64, s, (which ? N : O).release))) return rc;
+                        if ((rc = part[which].add(*L, d_rho.as<Fe>(), d_pts.as<Affine<Fq>>(), n, s))) return rc;
                     }
                 }
                 WS_HIP_CHECK(hipStreamSynchronize(s));
-                for (int which = 0; which < 2; which++)
-                    g1_sum_host(reinterpret_cast<const uint8_t*>(part[which].data()), part[which].size(), reinterpret_cast<uint8_t*>(&sums[sec][which]));
+                for (int which = 0; which < 2; which++) sums[sec][which] = part[which].finish();
             }
         }
         ms_sums = ms_since(t0);
         const auto t1 = Clock::now();
         for (int sec = 0; sec < 2; sec++) {
-            const G1A so = G1A{sums[sec][0].x, sums[sec][0].y, Fq::is_zero(sums[sec][0].z)};
-            const G1A sn = G1A{sums[sec][1].x, sums[sec][1].y, Fq::is_zero(sums[sec][1].z)};
             V.checks_run |= 4u << sec;
-            if (!same_pairing(sn, n2, so, o2)) V.checks_bad |= 4u << sec;
+            if (!same_pairing(sums[sec][1], n2, sums[sec][0], o2)) V.checks_bad |= 4u << sec;      // (the new sum, the old sum)
         }
         ms_pair += ms_since(t1);
     }

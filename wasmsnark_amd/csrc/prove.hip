@@ -20,6 +20,7 @@
 #include <thread>
 
 #include "internal.h"
+#include "keybytes.h"
 
 namespace wsnark {
 
@@ -98,8 +99,6 @@ int pkey_wait_tables(ProvingKey* K) {
     return pkey_table_state(K, true, &cw, &ch);
 }
 
-const std::string& get_last_error();
-
 static bool range_ok(uint64_t off, uint64_t bytes, size_t len) { return off <= len && bytes <= len - off; }
 
 int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
@@ -107,14 +106,7 @@ int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
     if (!C) return WS_ERR_NOINIT;
     const uint32_t nv = S.n_vars, np = S.n_public, dom = S.domain;
     if (shard.world == 0 || shard.rank >= shard.world) return WS_ERR_ARG;
-    if (nv == 0 || (uint64_t)np + 1 > nv) { set_last_error("proving key: nPublic + 1 > nVars"); return WS_ERR_FORMAT; }
-    if (dom < 2 || (dom & (dom - 1)) || dom > (1u << 27)) { set_last_error("proving key: domainSize must be a power of two in [2, 2^27]"); return WS_ERR_SIZE; }
-    const uint64_t nC = (uint64_t)nv - np - 1;
-    if (S.lenPA < (uint64_t)nv * 64 || S.lenPB1 < (uint64_t)nv * 64 || S.lenPB2 < (uint64_t)nv * 128 || S.lenPC < nC * 64 ||
-        S.lenPH < (uint64_t)dom * 64) {
-        set_last_error("proving key: a point section is shorter than its header-implied size");
-        return WS_ERR_FORMAT;
-    }
+    if (int bad = key_shape_check(S)) return bad;
     std::unique_ptr<ProvingKey> K(new ProvingKey());
     K->owner = C;
     K->n_vars = nv; K->n_public = np; K->domain = dom;
@@ -348,7 +340,7 @@ int pkey_parse(const uint8_t* buf, size_t len, KeySections* out) {
     memcpy(h, buf, 40);
     const uint32_t nv = h[0], np = h[1], dom = h[2];
     const uint64_t pPolsA = h[3], pPolsB = h[4], pA = h[5], pB1 = h[6], pB2 = h[7], pC = h[8], pH = h[9];
-    if (nv == 0 || (uint64_t)np + 1 > nv) { set_last_error("proving key: nPublic + 1 > nVars"); return WS_ERR_FORMAT; }
+    if (int bad = key_vars_check(nv, np)) return bad;
     const uint64_t nC = (uint64_t)nv - np - 1;
     if (!(pPolsA >= 488 && pPolsA <= pPolsB && pPolsB <= pA) || !range_ok(pA, (uint64_t)nv * 64, len) ||
         !range_ok(pB1, (uint64_t)nv * 64, len) || !range_ok(pB2, (uint64_t)nv * 128, len) ||
@@ -362,14 +354,6 @@ int pkey_parse(const uint8_t* buf, size_t len, KeySections* out) {
                        buf + pA, buf + pB1, buf + pB2, buf + pC, buf + pH,
                        len - pA, len - pB1, len - pB2, len - pC, len - pH};
     return WS_OK;
-}
-int pkey_load(const uint8_t* buf, size_t len, ProvingKey** out) {
-    if (!ctx()) return WS_ERR_NOINIT;
-    if (!out) return WS_ERR_ARG;
-    KeySections S;
-    int rc = pkey_parse(buf, len, &S);
-    if (rc) return rc;
-    return pkey_load_sections(S, out, KeyShard{});
 }
 
 void pkey_free(ProvingKey* K) { delete K; }
