@@ -554,6 +554,59 @@ int wsnark_selftest_field(int which, int impl, int op, const void* a, const void
  *   them, field29.h) followed by its narrowing, 8 = timesScalar (src/build_timesscalar.js:20-80): q's bytes are NOT a point
  *   but a little-endian scalar in bytes [0, 64) and its length -- 32 or 64 -- in byte 64 (impl 0-3). */
 int wsnark_selftest_curve(int g, int impl, int op, const void* p, const void* q, void* out, uint64_t n);
+/* The radix-2^29 field (csrc/field29.h) on RAW limbs, one lane per case: the operand bounds its contracts allow cannot be reached
+ * through the packed 32-byte form (8p, 10p and 16p do not fit it, a carry-free sum's limbs are not tight, and to_internal turns every
+ * input into an ordinary representative below 2p), so here the nine 29-bit limbs of every operand (value = sum v[i] 2^(29 i); the top
+ * limb takes the rest) reach the function under test exactly as given, and the result's limbs come back as returned.
+ *   which   : 0 = Fq, 1 = Fr
+ *   impl    : 0 = device Field29<P> (the noinline products: mad_chain.h on the GPU), 3 = device Field29I<P> (Fq only: the inlined
+ *             products and mul2add_inl of the reduction tails), 2 = the same functions run on the host (the C bodies)
+ *   operands: n x arity(op) x 9 uint32_t (the extension's ops: arity x 18, (c0, c1)); nothing is reduced or converted on the way in
+ *   out     : n x 9 uint32_t (the extension's ops: 18), nothing canonicalised; predicates write 0 or 1 in limb 0; ops that return the
+ *             32-byte form write its eight 32-bit words and 0 in the ninth
+ * Unknown which / impl / op: WSNARK_ERR_ARG.  n <= 2^20. */
+enum {
+    WSNARK_F29_MUL = 0,            /* 2: mul(a, b)                                                   */
+    WSNARK_F29_SQR = 1,            /* 1: sqr(a)                                                      */
+    WSNARK_F29_MUL_INL = 2,        /* 2: mul_inl(a, b)                                               */
+    WSNARK_F29_MUL2ADD = 3,        /* 4: mul2add(a, b, c, d) = a b + c d                             */
+    WSNARK_F29_MUL2ADD_INL = 4,    /* 4: mul2add_inl(a, b, c, d)                                     */
+    WSNARK_F29_MUL4ADD = 5,        /* 8: mul4add(a, ..., h) = a b + c d + e f + g h                  */
+    WSNARK_F29_MULSUB2 = 6,        /* 4: mulsub2(a, b, c, d) = a b - c d                             */
+    WSNARK_F29_ADD = 7,            /* 2 */
+    WSNARK_F29_SUB = 8,            /* 2 */
+    WSNARK_F29_NEG = 9,            /* 1 */
+    WSNARK_F29_SUB_WEAK = 10,      /* 2: a - b + 2p                                                  */
+    WSNARK_F29_SUB_WEAK4 = 11,     /* 2: a - b + 4p                                                  */
+    WSNARK_F29_SUB_WEAK8 = 12,     /* 2: a - b + 8p                                                  */
+    WSNARK_F29_NEG_WEAK = 13,      /* 1: 2p - a                                                      */
+    WSNARK_F29_NEG_WEAK4 = 14,     /* 1: 4p - a                                                      */
+    WSNARK_F29_ADD_NR = 15,        /* 2: a + b, carries propagated, no reduction                     */
+    WSNARK_F29_ADD_LAZY_MUL = 16,  /* 3: mul(add_lazy(a, b), c): the carry-free sum is valid inside a product only */
+    WSNARK_F29_FOLD8 = 17,         /* 1 */
+    WSNARK_F29_FOLD16 = 18,        /* 1 */
+    WSNARK_F29_FOLD4TO2 = 19,      /* 1 */
+    WSNARK_F29_COND_SUB_2P = 20,   /* 1 */
+    WSNARK_F29_NARROW = 21,        /* 1 */
+    WSNARK_F29_CANONICAL = 22,     /* 1 */
+    WSNARK_F29_X3_WIDE = 23,       /* 3: x3_wide(rr, ppp, q) = rr - ppp - 2q + 6p                    */
+    WSNARK_F29_SUB_WIDE = 24,      /* 2: a - b + 8p                                                  */
+    WSNARK_F29_IS_ZERO = 25,       /* 1, predicate */
+    WSNARK_F29_IS_ZERO_WEAK = 26,  /* 1, predicate */
+    WSNARK_F29_IS_ZERO_WIDE = 27,  /* 1, predicate */
+    WSNARK_F29_MAYBE_ZERO_WEAK = 28, /* 1, predicate (maybe_kp(a, 3)) */
+    WSNARK_F29_MAYBE_ZERO_WIDE = 29, /* 1, predicate (maybe_kp(a, 9)) */
+    WSNARK_F29_PACK_UNPACK = 30,   /* 1: pack(unpack(x)); x = eight 32-bit words, the ninth is ignored; out = eight words */
+    WSNARK_F29_PACKED_IS_ZERO = 31,/* 1, predicate on eight 32-bit words                             */
+    WSNARK_F29_TO_INTERNAL = 32,   /* 1: to_internal(x) of a raw 256-bit x (eight words)             */
+    WSNARK_F29_FROM_INTERNAL = 33, /* 1: from_internal(a); out = eight words                         */
+    WSNARK_F29_DBL = 34,           /* 1 */
+    WSNARK_F29_EQ = 35,            /* 2, predicate */
+    WSNARK_F29_FP2_MUL = 36,       /* 2 x 18: Fp2T<Fq29>::mul(a, b)            (which 0, impl 0 or 2) */
+    WSNARK_F29_FP2_SQR = 37,       /* 1 x 18: Fp2T<Fq29>::sqr(a)                                      */
+    WSNARK_F29_FP2_MULSUB2 = 38    /* 4 x 18: Fp2T<Fq29>::mulsub2(a, b, c, d) = a b - c d             */
+};
+int wsnark_selftest_field29(int which, int impl, int op, const uint32_t* operands, uint32_t* out, uint64_t n);
 /* The Fp12 arithmetic of the batch verifier (csrc/fp12.h), one lane per element.
  * op 0 = a * b, 1 = a^2, 2 = 1 / a, 3 = a^(p^2), 4 = final exponentiation of a (the shipped path: easy part by inversion,
  * conjugation and Frobenius, then the hard exponent), 5 = final exponentiation by the plain exponent (p^12 - 1)/r;

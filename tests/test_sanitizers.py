@@ -24,7 +24,8 @@ RUNS = {
              ("tests/test_key_file.py", "not js_writer"),
              ("tests/test_prove_cpu.py", "two_proofs_in_flight or proofs_before_the_table_rows or staging_ring or key_format_errors or partial_finish or key_falls_back or reduction_tail"),
              ("tests/test_emul_kernels.py", None),
-             ("tests/test_dist_ntt_gloo.py", "native")],
+             ("tests/test_dist_ntt_gloo.py", "native"),
+             ("tests/test_emul_field29_contracts.py", None)],    # (UBSan on the signed borrow arithmetic at the operand bounds)
     # (TSan with one fibre per kernel thread is ~50x the plain emulator: 15 min for the first file, 46 min for three more group tests
     #  in round 6's first run -- the list keeps what has threads in it: lanes, the background build, a group's workers and its death)
     "tsan": [("tests/test_prove_cpu.py", "two_proofs_in_flight or proofs_before_the_table_rows"),

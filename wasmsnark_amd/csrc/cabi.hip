@@ -494,6 +494,12 @@ int wsnark_selftest_fp12(int impl, int op, const void* a, const void* b, void* o
     return selftest_fp12(impl, op, (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)out, n);
 }
 
+int wsnark_selftest_field29(int which, int impl, int op, const uint32_t* operands, uint32_t* out, uint64_t n) {
+    REQUIRE_CTX();
+    if (n && (!operands || !out)) return WSNARK_ERR_ARG;
+    return selftest_field29(which, impl, op, operands, out, n);
+}
+
 int wsnark_peak_probe(int probe, double* gops_per_s) {
     REQUIRE_CTX();
     return peak_probe(probe, gops_per_s);

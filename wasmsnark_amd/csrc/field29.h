@@ -168,8 +168,9 @@ struct Field29 {
         return cond_sub_2p(s);
     }
     WS_HD static F29 dbl(const F29& a) { return add(a, a); }
-    // a + b WITHOUT carry propagation or reduction: limbs < 2^30, value < 4p.  Only valid as a direct
-    // operand of mul/sqr (column sums stay < 9*2^60 + 9*2^58 < 2^64; output < p(1 + 16p/2^261) < 2p).
+    // a + b WITHOUT carry propagation or reduction: limbs < 2^30.  a, b strict give a value < 4p; the quadratic extension's squaring
+    // passes two uncorrected differences (< 4p each): value < 8p.  Only valid as a direct operand of mul / mul_inl, against a tight
+    // operand below 8p (column sums stay < 9*2^60 + 9*2^58 < 2^64; output < p(1 + 64p/2^261) < 1.4p).
     WS_HD static F29 add_lazy(const F29& a, const F29& b) {
         F29 s;
 #pragma unroll
@@ -190,7 +191,8 @@ struct Field29 {
         return cond_sub_2p(d);
     }
     // a - b + 2p in (0, 4p) WITHOUT the final correction: tight limbs.  Valid only as an operand of
-    // mul / sqr / is_zero_weak (16 p^2 / 2^261 < 0.1 p keeps products below 2p).
+    // mul / sqr / mulsub2's first pair / is_zero_weak (16 p^2 / 2^261 < 0.1 p keeps products below 2p), and as a value of the
+    // transforms' tiles, which live in [0, 4p).
     WS_HD static F29 sub_weak(const F29& a, const F29& b) {
         F29 d;
         int32_t c = 0;
@@ -388,19 +390,23 @@ struct Field29 {
     }
     WS_HD static F29 cneg(const F29& a, bool s) { return s ? neg(a) : a; }
 
-    // ---- Montgomery product a*b*2^-261 mod p; inputs < 2p (limbs < 2^29), output < 2p ----
+    // ---- Montgomery product a*b*2^-261 mod p; tight limbs, output < 2p.  Operands are strict (< 2p) or any of the lazy forms above:
+    // (a b + m p) / 2^261 < p (1 + ka kb p / 2^261) for a < ka p, b < kb p, and p / 2^261 < 2^-7.4, so the output stays below 2p
+    // while ka kb <= 100.  The widest operands passed: 16p x 2p (the transforms' sub_weak8 differences), 10p x 2p and 10p squared
+    // (sub_wide differences), 8p x 8p (the extension's squaring, one of them a carry-free sum).  Columns: <= 9 products + 9 reduction terms, < 2^63 even with a carry-free operand. ----
     WS_HD static F29 mul(const F29& a, const F29& b) { return mont_mul29<P>(WS_A9(a), WS_A9(b)); }
     WS_HD static F29 sqr(const F29& a) { return mont_sqr29<P>(WS_A9(a)); }
     WS_HD static F29 mul_inl(const F29& a, const F29& b) { return mont_mul29_body<P>(a, b); }
     // (a*b + c*d) * 2^-261 mod p with ONE Montgomery reduction (the quadratic-extension product needs two
-    // of these instead of three products and five additions).  Inputs < 2p, output < 2p:
-    // (8p^2 + 2^261 p)/2^261 < 1.05p; columns <= 18 products + 9 reduction terms < 2^63.
+    // of these instead of three products and five additions).  Tight limbs; inputs < 2p, or as wide as mulsub2 and the
+    // extension's product pass them -- a < 4p, b < 10p, c <= 2p, d < 2p; a, c < 4p, b < 2p, d <= 2p -- output < 2p:
+    // (44p^2 + 2^261 p)/2^261 < 1.3p; columns <= 18 products + 9 reduction terms < 2^63.
     WS_HD static F29 mul2add(const F29& a, const F29& b, const F29& c, const F29& d) {
         return mont_mul2add29<P>(WS_A9(a), WS_A9(b), WS_A9(c), WS_A9(d));
     }
 
-    // a*b - c*d with one reduction: a*b + (2p - c)*d.  a, b may be sub_weak results (< 4p), c, d < 2p:
-    // (16 p^2 + 4 p^2 + 2^261 p) / 2^261 < 1.12 p.
+    // a*b - c*d with one reduction: a*b + (2p - c)*d.  a may be a sub_weak result (< 4p), b a sub_weak or sub_wide result
+    // (< 10p: the accumulation loop's Q - X3), c, d < 2p: (40 p^2 + 4 p^2 + 2^261 p) / 2^261 < 1.3 p.
     // 2p - c for c in [0, 2p): in (0, 2p], tight limbs; only ever an operand of a product
     WS_HD static F29 neg_weak(const F29& c) {
         F29 n;
@@ -460,8 +466,9 @@ struct Field29 {
         return r;
     }
     // (a*b + c*d + e*f + g*h) * 2^-261 mod p with ONE reduction: one component of a*b - c*d in the quadratic
-    // extension.  Operands < 2p with tight limbs: every column holds <= 36 products + 9 reduction terms
-    // < 45 * 2^58 < 2^64; (16 p^2 + 2^261 p) / 2^261 < 1.1 p.  Inlined (eight operands do not fit the registers
+    // extension.  Tight limbs: every column holds <= 36 products + 9 reduction terms < 45 * 2^58 < 2^64, whatever the top
+    // limbs are.  Operands < 2p, or as fp2.h's mulsub2 passes them: a, b, c < 4p, d <= 4p (a neg_weak4 result), e, g <= 2p
+    // (neg_weak results), f, h < 2p: (40 p^2 + 2^261 p) / 2^261 < 1.3 p.  Inlined (eight operands do not fit the registers
     // of the calling convention).
     WS_HD static F29 mul4add(const F29& a, const F29& b, const F29& c, const F29& d, const F29& e, const F29& f,
                              const F29& g, const F29& h) {
@@ -504,7 +511,6 @@ struct Field29 {
         return r;
     }
 
-    // canonical representative in [0, p) of a value in [0, 2p)
     // a^(p-2), square-and-multiply over the 254 bits of p - 2.  Key-load time only (msm_table_kernel); ~380 products.
     WS_HD static F29 inv(const F29& a) {
         const uint64_t e[4] = {P::P0 - 2, P::P1, P::P2, P::P3};
@@ -515,6 +521,7 @@ struct Field29 {
         }
         return acc;
     }
+    // canonical representative in [0, p) of a value in [0, 2p)
     WS_HD static F29 canonical(const F29& a) {
         F29 d;
         int32_t bw = 0;

@@ -381,6 +381,7 @@ int g2_mul_base_batch(const void* base, const void* scalars, uint64_t n, void* o
 int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
 int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, uint8_t* out, uint64_t n);
 int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);
+int selftest_field29(int which, int impl, int op, const uint32_t* operands, uint32_t* out, uint64_t n);
 int peak_probe(int probe, double* gops);
 
 // ---- one proof over the ranks of a node (dist.hip) ----

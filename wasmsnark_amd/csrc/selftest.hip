@@ -474,6 +474,165 @@ int selftest_fp12(int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t*
     return B.down(out, n * 384, s);
 }
 
+// ---- the radix-2^29 field on RAW limbs (wsnark_selftest_field29; tests/field29_contracts.py) ----
+// Every other hook enters the field through to_internal, a Montgomery product: its operands are pseudo-random representatives
+// below 2p whatever the vector was.  Here the nine limbs of every operand reach the function under test exactly as given -- limbs of
+// 2^29 - 1 (2^30 - 2 in a carry-free sum), top limbs at the 4p / 8p / 10p / 16p level, representatives j p + x -- and the result's
+// limbs come back as returned, so that the caller can check the interval and the limb form, not only the residue.
+WS_HD F29 st29_ld(const uint32_t* x) {
+    F29 r;
+    for (int i = 0; i < 9; i++) r.v[i] = x[i];
+    return r;
+}
+WS_HD void st29_st(uint32_t* o, const F29& a) {
+    for (int i = 0; i < 9; i++) o[i] = a.v[i];
+}
+WS_HD void st29_flag(uint32_t* o, bool v) {
+    for (int i = 0; i < 9; i++) o[i] = 0;
+    o[0] = v ? 1 : 0;
+}
+WS_HD Fe st29_ld_fe(const uint32_t* x) {                 // eight 32-bit words; the ninth is ignored
+    Fe r;
+    for (int k = 0; k < 4; k++) r.l[k] = (uint64_t)x[2 * k] | ((uint64_t)x[2 * k + 1] << 32);
+    return r;
+}
+WS_HD void st29_st_fe(uint32_t* o, const Fe& a) {
+    for (int k = 0; k < 4; k++) { o[2 * k] = (uint32_t)a.l[k]; o[2 * k + 1] = (uint32_t)(a.l[k] >> 32); }
+    o[8] = 0;
+}
+// operands per case and limbs per operand / result of an op; false = no such op
+static bool st29_shape(int op, int* arity, int* limbs) {
+    *limbs = 9;
+    switch (op) {
+        case WSNARK_F29_SQR: case WSNARK_F29_NEG: case WSNARK_F29_NEG_WEAK: case WSNARK_F29_NEG_WEAK4: case WSNARK_F29_FOLD8:
+        case WSNARK_F29_FOLD16: case WSNARK_F29_FOLD4TO2: case WSNARK_F29_COND_SUB_2P: case WSNARK_F29_NARROW: case WSNARK_F29_CANONICAL:
+        case WSNARK_F29_IS_ZERO: case WSNARK_F29_IS_ZERO_WEAK: case WSNARK_F29_IS_ZERO_WIDE: case WSNARK_F29_MAYBE_ZERO_WEAK:
+        case WSNARK_F29_MAYBE_ZERO_WIDE: case WSNARK_F29_PACK_UNPACK: case WSNARK_F29_PACKED_IS_ZERO: case WSNARK_F29_TO_INTERNAL:
+        case WSNARK_F29_FROM_INTERNAL: case WSNARK_F29_DBL:
+            *arity = 1; return true;
+        case WSNARK_F29_MUL: case WSNARK_F29_MUL_INL: case WSNARK_F29_ADD: case WSNARK_F29_SUB: case WSNARK_F29_SUB_WEAK:
+        case WSNARK_F29_SUB_WEAK4: case WSNARK_F29_SUB_WEAK8: case WSNARK_F29_ADD_NR: case WSNARK_F29_SUB_WIDE: case WSNARK_F29_EQ:
+            *arity = 2; return true;
+        case WSNARK_F29_ADD_LAZY_MUL: case WSNARK_F29_X3_WIDE:
+            *arity = 3; return true;
+        case WSNARK_F29_MUL2ADD: case WSNARK_F29_MUL2ADD_INL: case WSNARK_F29_MULSUB2:
+            *arity = 4; return true;
+        case WSNARK_F29_MUL4ADD:
+            *arity = 8; return true;
+        case WSNARK_F29_FP2_SQR: *arity = 1; *limbs = 18; return true;
+        case WSNARK_F29_FP2_MUL: *arity = 2; *limbs = 18; return true;
+        case WSNARK_F29_FP2_MULSUB2: *arity = 4; *limbs = 18; return true;
+        default: return false;
+    }
+}
+// one case: x = the operands' limbs one after the other, o = the result's (9, or 18 for the extension's ops)
+template <class F, bool EXT>
+WS_HD void st29_op(int op, const uint32_t* x, uint32_t* o) {
+    const F29 a = st29_ld(x);
+    switch (op) {
+        case WSNARK_F29_MUL: st29_st(o, F::mul(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_SQR: st29_st(o, F::sqr(a)); return;
+        case WSNARK_F29_MUL_INL: st29_st(o, F::mul_inl(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_MUL2ADD: st29_st(o, F::mul2add(a, st29_ld(x + 9), st29_ld(x + 18), st29_ld(x + 27))); return;
+        case WSNARK_F29_MUL2ADD_INL: st29_st(o, F::mul2add_inl(a, st29_ld(x + 9), st29_ld(x + 18), st29_ld(x + 27))); return;
+        case WSNARK_F29_MUL4ADD:
+            st29_st(o, F::mul4add(a, st29_ld(x + 9), st29_ld(x + 18), st29_ld(x + 27), st29_ld(x + 36), st29_ld(x + 45), st29_ld(x + 54),
+                                  st29_ld(x + 63)));
+            return;
+        case WSNARK_F29_MULSUB2: st29_st(o, F::mulsub2(a, st29_ld(x + 9), st29_ld(x + 18), st29_ld(x + 27))); return;
+        case WSNARK_F29_ADD: st29_st(o, F::add(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_SUB: st29_st(o, F::sub(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_NEG: st29_st(o, F::neg(a)); return;
+        case WSNARK_F29_SUB_WEAK: st29_st(o, F::sub_weak(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_SUB_WEAK4: st29_st(o, F::sub_weak4(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_SUB_WEAK8: st29_st(o, F::sub_weak8(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_NEG_WEAK: st29_st(o, F::neg_weak(a)); return;
+        case WSNARK_F29_NEG_WEAK4: st29_st(o, F::neg_weak4(a)); return;
+        case WSNARK_F29_ADD_NR: st29_st(o, F::add_nr(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_ADD_LAZY_MUL: st29_st(o, F::mul(F::add_lazy(a, st29_ld(x + 9)), st29_ld(x + 18))); return;
+        case WSNARK_F29_FOLD8: st29_st(o, F::fold8(a)); return;
+        case WSNARK_F29_FOLD16: st29_st(o, F::fold16(a)); return;
+        case WSNARK_F29_FOLD4TO2: st29_st(o, F::fold4to2(a)); return;
+        case WSNARK_F29_COND_SUB_2P: st29_st(o, F::cond_sub_2p(a)); return;
+        case WSNARK_F29_NARROW: st29_st(o, F::narrow(a)); return;
+        case WSNARK_F29_CANONICAL: st29_st(o, F::canonical(a)); return;
+        case WSNARK_F29_X3_WIDE: st29_st(o, F::x3_wide(a, st29_ld(x + 9), st29_ld(x + 18))); return;
+        case WSNARK_F29_SUB_WIDE: st29_st(o, F::sub_wide(a, st29_ld(x + 9))); return;
+        case WSNARK_F29_IS_ZERO: st29_flag(o, F::is_zero(a)); return;
+        case WSNARK_F29_IS_ZERO_WEAK: st29_flag(o, F::is_zero_weak(a)); return;
+        case WSNARK_F29_IS_ZERO_WIDE: st29_flag(o, F::is_zero_wide(a)); return;
+        case WSNARK_F29_MAYBE_ZERO_WEAK: st29_flag(o, F::maybe_zero_weak(a)); return;
+        case WSNARK_F29_MAYBE_ZERO_WIDE: st29_flag(o, F::maybe_zero_wide(a)); return;
+        case WSNARK_F29_PACK_UNPACK: st29_st_fe(o, F::pack(F::unpack(st29_ld_fe(x)))); return;
+        case WSNARK_F29_PACKED_IS_ZERO: st29_flag(o, F::packed_is_zero(st29_ld_fe(x))); return;
+        case WSNARK_F29_TO_INTERNAL: st29_st(o, F::to_internal(st29_ld_fe(x))); return;
+        case WSNARK_F29_FROM_INTERNAL: st29_st_fe(o, F::from_internal(a)); return;
+        case WSNARK_F29_DBL: st29_st(o, F::dbl(a)); return;
+        case WSNARK_F29_EQ: st29_flag(o, F::eq(a, st29_ld(x + 9))); return;
+        default: break;
+    }
+    // the quadratic extension over this field, as the G2 formulas stack the forms (fp2.h): (c0, c1) = 18 limbs per operand
+    if constexpr (EXT) {
+        typedef Fp2T<F> F2;
+        typename F2::El r = F2::zero();
+        const typename F2::El a2 = {a, st29_ld(x + 9)};
+        if (op == WSNARK_F29_FP2_SQR) r = F2::sqr(a2);
+        else if (op == WSNARK_F29_FP2_MUL) r = F2::mul(a2, typename F2::El{st29_ld(x + 18), st29_ld(x + 27)});
+        else if (op == WSNARK_F29_FP2_MULSUB2)
+            r = F2::mulsub2(a2, typename F2::El{st29_ld(x + 18), st29_ld(x + 27)}, typename F2::El{st29_ld(x + 36), st29_ld(x + 45)},
+                            typename F2::El{st29_ld(x + 54), st29_ld(x + 63)});
+        st29_st(o, r.c0);
+        st29_st(o + 9, r.c1);
+    } else {
+        for (int i = 0; i < 18; i++) o[i] = 0;          // (refused on the host before any launch)
+    }
+}
+template <class F, bool EXT>
+__global__ __launch_bounds__(64) void st29_kernel(int op, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n, uint32_t in_words,
+                                                    uint32_t out_words) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t o[18];
+    st29_op<F, EXT>(op, in + i * in_words, o);
+    for (uint32_t k = 0; k < out_words; k++) out[i * out_words + k] = o[k];
+}
+template <class F, bool EXT>
+static int st29_dev(int op, const uint32_t* in, uint32_t* out, uint64_t n, uint32_t in_words, uint32_t out_words, hipStream_t s) {
+    DevBuf din, dout;
+    WS_HIP_CHECK(din.alloc(n * in_words * 4));
+    WS_HIP_CHECK(dout.alloc(n * out_words * 4));
+    WS_HIP_CHECK(hipMemcpyAsync(din.p, in, n * in_words * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL((st29_kernel<F, EXT>), dim3(ceil_div_u64(n, 64)), dim3(64), 0, s, op, din.as<uint32_t>(), dout.as<uint32_t>(), n, in_words, out_words);
+    WS_HIP_CHECK(hipGetLastError());
+    WS_HIP_CHECK(hipMemcpyAsync(out, dout.p, n * out_words * 4, hipMemcpyDeviceToHost, s));
+    WS_HIP_CHECK(hipStreamSynchronize(s));
+    return WS_OK;
+}
+template <class F, bool EXT>
+static int st29_host(int op, const uint32_t* in, uint32_t* out, uint64_t n, uint32_t in_words, uint32_t out_words) {
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t o[18];
+        st29_op<F, EXT>(op, in + i * in_words, o);
+        memcpy(out + i * out_words, o, out_words * 4);
+    }
+    return WS_OK;
+}
+int selftest_field29(int which, int impl, int op, const uint32_t* operands, uint32_t* out, uint64_t n) {
+    Context* X = ctx();
+    if (!X) return WS_ERR_NOINIT;
+    int arity = 0, limbs = 0;
+    if (!st29_shape(op, &arity, &limbs) || (which != 0 && which != 1) || (impl != 0 && impl != 2 && impl != 3)) return WS_ERR_ARG;
+    if (limbs == 18 && (which != 0 || impl == 3)) { set_last_error("selftest: the extension's ops are Fp2T<Fq29>'s (which 0, impl 0 or 2)"); return WS_ERR_ARG; }
+    if (impl == 3 && which != 0) { set_last_error("selftest: the inlined-product variant exists for Fq only"); return WS_ERR_ARG; }
+    if (n == 0) return WS_OK;
+    if (n > (1u << 20)) return WS_ERR_SIZE;
+    const uint32_t in_words = (uint32_t)(arity * limbs), out_words = (uint32_t)limbs;
+    if (impl == 2) return which == 0 ? st29_host<Fq29, true>(op, operands, out, n, in_words, out_words) : st29_host<Fr29, false>(op, operands, out, n, in_words, out_words);
+    hipStream_t s = X->stream;
+    if (impl == 3) return st29_dev<Fq29I, false>(op, operands, out, n, in_words, out_words, s);
+    return which == 0 ? st29_dev<Fq29, true>(op, operands, out, n, in_words, out_words, s) : st29_dev<Fr29, false>(op, operands, out, n, in_words, out_words, s);
+}
+
 // ---- peak probes (bench.py: the integer roofline's peak, re-measured on the box the run is on) ----
 // probe 0: every lane runs one dependent chain of the PRODUCT'S OWN radix-2^29 Montgomery product (Fq29::mul, the
 //          function the accumulation kernels call): what a kernel made of nothing but products reaches = the "multiplier
