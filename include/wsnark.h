@@ -315,6 +315,82 @@ int wsnark_pkey_delta_verify(const void* old_pkey, size_t old_len, const void* n
 int wsnark_pkey_delta_verify_sections(const wsnark_key_sections_t* old_key, const wsnark_key_sections_t* new_key, const void* seed32,
                                       wsnark_pkey_delta_verdict_t* out);
 int wsnark_pkey_delta_verify_file(const char* old_path, const char* new_path, const void* seed32, wsnark_pkey_delta_verdict_t* out);
+/* ---- the first key of a ceremony from a powers-of-tau transcript (csrc/pkeysetup.hip; snarkjs: `zkey new`) ----
+ * The step before the three above.  A key's points are the circuit's columns evaluated "in the exponent" on the Lagrange basis, and
+ * L_i(tau) G = (1/n) sum_k w_n^(-ik) (tau^k G) is the inverse transform of the powers: wsnark_fr_ntt with points in place of field
+ * elements (no counterpart in the reference, whose FFT is built over frm only).
+ *   wsnark_g{1,2}_ntt         forward: out[i] = sum_k w_n^(ik) P_k;   inverse: out[i] = n^-1 sum_k w_n^(-ik) P_k.  w_n is the root
+ *                             wsnark_fr_ntt uses (5^((r-1)/2^28) squared down); natural order in and out: this is
+ *                             wsnark_fr_ntt(odd = 0, inverse) applied to the discrete logarithms.  points / out: host, n affine
+ *                             Montgomery points of 64 (G1) / 128 (G2) bytes; out may be points.  x == 0 is infinity on input; a result
+ *                             at infinity is written as zero bytes and every other result is affine and canonical: outputs compare
+ *                             byte for byte.  n: a power of two, 1 <= n <= 2^24 (n == 1: the identity), else WSNARK_ERR_SIZE.  Every
+ *                             input gets the audit's two cheap tests as in wsnark_g{1,2}_scale_batch (NOT the G2 subgroup test): a
+ *                             bad point is WSNARK_ERR_FORMAT (wsnark_last_error names the first index), out is then untouched.
+ *                             n/2 log2 n scalar multiplications, one butterfly per lane; needs wsnark_init (WSNARK_ERR_NOINIT) and
+ *                             takes a lane of the context.  WSNARK_PKSETUP_NTT_UNIFORM=0 reads every stage's twiddle digits per lane
+ *                             (a measurement switch: the bytes do not depend on it). */
+int wsnark_g1_ntt(const void* points, uint64_t n, int inverse, void* out);
+int wsnark_g2_ntt(const void* points, uint64_t n, int inverse, void* out);
+/* wsnark_pkey_setup*: the key of a circuit under delta = 1 and gamma = 1 -- the key wsnark_pkey_contribute is then applied to.
+ *   alfa1 = alpha_tau_g1[0], beta1 = beta_tau_g1[0], beta2 as given; delta1, delta2 (and the verification key's gamma2) are the
+ *   standard generators.  With L1, L2, aL, bL the INVERSE group transforms of the first n entries of tau_g1, tau_g2, alpha_tau_g1,
+ *   beta_tau_g1:   A_j = sum_i a_ji L1_i    B1_j = sum_i b_ji L1_i    B2_j = sum_i b_ji L2_i
+ *                  K_j = sum_i a_ji bL_i + sum_i b_ji aL_i + sum_i c_ji L1_i:  C for j > nPublic, IC (the verification key's) for j <= nPublic
+ *                  hExps_i = tau_g1[n + i] - tau_g1[i]
+ *   polsA and polsB go into the key unchanged; polsC is not part of a proving key and is needed once, here.
+ *   column sums               one lane per (signal, sum) walks the signal's records: coefficients are Montgomery in the stream and are
+ *                             taken out of Montgomery form on the device; a zero coefficient adds nothing, repeated constraint indices
+ *                             simply add, a signal without records is infinity (zero bytes).  A column with more than
+ *                             WSNARK_PKSETUP_MSM_MIN records (default 32) has its points gathered and goes through the ordinary MSM
+ *                             instead -- a real circuit's constant signal sits in 10^5 rows; the bytes do not depend on the switch.
+ *   errors                    what the loaders reject fails before anything is written, the report untouched: nPublic + 1 > nVars
+ *                             (WSNARK_ERR_FORMAT), domain not a power of two in [2, 2^24] or the two structs' domains different
+ *                             (WSNARK_ERR_SIZE), an array shorter than its domain implies, a truncated record stream or a record
+ *                             index >= domain, tau_g1[0] or tau_g2[0] not the generator (WSNARK_ERR_FORMAT); out_cap too small or a
+ *                             key beyond proving_key.bin's 4 GiB (WSNARK_ERR_SIZE); before wsnark_init WSNARK_ERR_NOINIT.
+ *   a bad power is a RESULT   as in the audit and the contribution: WSNARK_OK with ok = 0 for a power with a coordinate >= q or off
+ *                             the curve (per array points / infinity / bad / first_bad / first_reason, reduced on the device; tau_g1
+ *                             counts all its 2n entries) and for a beta2 that fails the audit's fixed-point tests.  The outputs are
+ *                             then unspecified.
+ * Not tested here: whether the powers ARE powers of one tau (the pairing relations of a transcript are its own audit), and the G2
+ * subgroup test of tau_g2.  No .ptau / .r1cs readers, no file-to-file variant, one GPU.  Each call takes a lane of the context; nothing
+ * else calls these functions and no other entry point changes. */
+typedef struct {                 /* what a phase-1 transcript holds for a domain of n = `domain` */
+    uint32_t domain;             /* power of two */
+    const void* tau_g1;       uint64_t tau_g1_len;        /* 2n x 64 B : tau^k G1, k = 0 .. 2n-1 (hExps needs tau^(n+i)) */
+    const void* tau_g2;       uint64_t tau_g2_len;        /*  n x 128 B: tau^k G2 */
+    const void* alpha_tau_g1; uint64_t alpha_tau_g1_len;  /*  n x 64 B : alpha tau^k G1 */
+    const void* beta_tau_g1;  uint64_t beta_tau_g1_len;   /*  n x 64 B : beta tau^k G1 */
+    const void* beta_g2;                                   /*  128 B */
+} wsnark_powers_t;
+typedef struct {                 /* the circuit in the key's own column form: record streams of src/build_pol.js:62-144 */
+    uint32_t n_vars, n_public, domain;
+    const void* polsA; uint64_t polsA_len;
+    const void* polsB; uint64_t polsB_len;
+    const void* polsC; uint64_t polsC_len;                 /* not part of a proving key: needed once, here */
+} wsnark_circuit_t;
+enum { WSNARK_PW_TAU_G1 = 0, WSNARK_PW_TAU_G2 = 1, WSNARK_PW_ALPHA_TAU_G1 = 2, WSNARK_PW_BETA_TAU_G1 = 3 };      /* arrays in report order */
+typedef struct {
+    uint64_t points[4], infinity[4], bad[4];
+    uint64_t first_bad[4];               /* UINT64_MAX if none */
+    uint32_t first_reason[4];            /* WSNARK_PK_UNREDUCED / WSNARK_PK_OFF_CURVE */
+    uint32_t beta2_reason;               /* 0 = good */
+    uint32_t ok;                         /* 1 iff no bad power and beta2 passed */
+    uint32_t msm_columns;                /* column sums that went through the MSM */
+    uint32_t reserved;
+    double   ms[4];                      /* transforms (with the upload and the input tests), column sums, hExps, whole call */
+} wsnark_pkey_setup_report_t;
+/* the sections as wsnark_pkey_load_sections reads them: nVars, nVars, nVars (128 B each), nVars - nPublic - 1 and domain points; the
+ * five fixed points; out_ic: (nPublic + 1) x 64 B.  out_pointsC may be NULL when nVars == nPublic + 1. */
+int wsnark_pkey_setup(const wsnark_powers_t* powers, const wsnark_circuit_t* circuit,
+                      void* out_pointsA, void* out_pointsB1, void* out_pointsB2, void* out_pointsC, void* out_pointsH,
+                      void* out_alfa1_64, void* out_beta1_64, void* out_delta1_64, void* out_beta2_128, void* out_delta2_128,
+                      void* out_ic, wsnark_pkey_setup_report_t* rep);
+/* the same key as a whole proving_key.bin in out_pkey[0 .. *out_len); wsnark_pkey_setup_size gives the length without any device work */
+int wsnark_pkey_setup_pkey(const wsnark_powers_t* powers, const wsnark_circuit_t* circuit, void* out_pkey, size_t out_cap, size_t* out_len,
+                           void* out_ic, wsnark_pkey_setup_report_t* rep);
+int wsnark_pkey_setup_size(const wsnark_circuit_t* circuit, size_t* out_len);
 /* which share a handle holds: (0, 1, 0, nVars, domain, 0) for a whole key.  Any out pointer may be NULL. */
 int wsnark_pkey_shard_info(const wsnark_pkey_t* handle, uint32_t* rank, uint32_t* world, uint64_t* first_signal,
                            uint64_t* n_signals, uint64_t* n_hexps, uint32_t* h_interleave_log);

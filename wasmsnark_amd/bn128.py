@@ -96,6 +96,64 @@ class _DeltaVerdict(C.Structure):  # wsnark_pkey_delta_verdict_t
     _fields_ = [("checks_run", C.c_uint32), ("checks_bad", C.c_uint32), ("ok", C.c_uint32), ("ms", C.c_double * 3)]
 
 
+class _Powers(C.Structure):        # wsnark_powers_t
+    _fields_ = [("domain", C.c_uint32), ("tau_g1", C.c_void_p), ("tau_g1_len", C.c_uint64), ("tau_g2", C.c_void_p), ("tau_g2_len", C.c_uint64),
+                ("alpha_tau_g1", C.c_void_p), ("alpha_tau_g1_len", C.c_uint64), ("beta_tau_g1", C.c_void_p), ("beta_tau_g1_len", C.c_uint64),
+                ("beta_g2", C.c_void_p)]
+
+
+class _Circuit(C.Structure):       # wsnark_circuit_t
+    _fields_ = [("n_vars", C.c_uint32), ("n_public", C.c_uint32), ("domain", C.c_uint32),
+                ("polsA", C.c_void_p), ("polsA_len", C.c_uint64), ("polsB", C.c_void_p), ("polsB_len", C.c_uint64),
+                ("polsC", C.c_void_p), ("polsC_len", C.c_uint64)]
+
+
+class _SetupReport(C.Structure):   # wsnark_pkey_setup_report_t
+    _fields_ = [("points", C.c_uint64 * 4), ("infinity", C.c_uint64 * 4), ("bad", C.c_uint64 * 4), ("first_bad", C.c_uint64 * 4),
+                ("first_reason", C.c_uint32 * 4), ("beta2_reason", C.c_uint32), ("ok", C.c_uint32), ("msm_columns", C.c_uint32),
+                ("reserved", C.c_uint32), ("ms", C.c_double * 4)]
+
+
+POWERS_ARRAYS = ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1")         # report order (WSNARK_PW_TAU_G1 ..)
+
+
+def _setup_report_dict(r):
+    out = {}
+    for k, name in enumerate(POWERS_ARRAYS):
+        bad = int(r.bad[k])
+        out[name] = {"points": int(r.points[k]), "infinity": int(r.infinity[k]), "bad": bad,
+                     "first_bad": int(r.first_bad[k]) if bad else None, "first_reason": KEY_REASONS[r.first_reason[k]] if bad else None}
+    out["beta_g2"] = KEY_REASONS[r.beta2_reason]
+    out["ok"] = bool(r.ok)
+    out["msm_columns"] = int(r.msm_columns)
+    out["ms"] = {"transforms": r.ms[0], "column_sums": r.ms[1], "hexps": r.ms[2], "total": r.ms[3]}
+    return out
+
+
+def _powers_struct(powers):
+    """dict of byte strings -> (wsnark_powers_t, the buffers it points into)"""
+    ps, keep = _Powers(powers["domain"]), []
+    for name in POWERS_ARRAYS + ("beta_g2",):
+        b, n = _ro(powers[name])
+        keep.append(b)
+        setattr(ps, name, C.cast(b, C.c_void_p))
+        if name != "beta_g2":
+            setattr(ps, name + "_len", n)
+        elif n < 128:
+            raise ValueError("beta_g2 must be 128 bytes")
+    return ps, keep
+
+
+def _circuit_struct(circuit):
+    cs, keep = _Circuit(circuit["n_vars"], circuit["n_public"], circuit["domain"]), []
+    for name in ("polsA", "polsB", "polsC"):
+        b, n = _ro(circuit[name])
+        keep.append(b)
+        setattr(cs, name, C.cast(b, C.c_void_p))
+        setattr(cs, name + "_len", n)
+    return cs, keep
+
+
 DELTA_CHECKS = ("unchanged", "delta1~delta2", "C", "H", "delta_changed")    # bits 0..4 of wsnark_pkey_delta_verdict_t
 
 
@@ -532,6 +590,56 @@ class Bn128:
         fn = self.lib.c.wsnark_g1_scale_batch if g == 1 else self.lib.c.wsnark_g2_scale_batch
         self.lib.check(fn(p, nb // sz, kb, out))
         return bytes(out)[:nb]
+
+    # --- the first key of a ceremony (csrc/pkeysetup.hip; no reference counterpart -- snarkjs: zkey new) ---
+    def group_ntt(self, g, points, inverse=False):
+        """The transform over group elements: out[i] = sum_k w_n^(ik) P_k (inverse: n^-1 sum_k w_n^(-ik) P_k), natural order, the
+        root of fft() -- fft(odd=0) applied to the discrete logarithms.  points: n affine Montgomery points (64 bytes each for
+        g = 1, 128 for g = 2; x == 0 is infinity), n a power of two up to 2^24.  A result at infinity is zero bytes:
+        wsnark_g{1,2}_ntt."""
+        p, nb = _ro(points)
+        sz = 64 if g == 1 else 128
+        if nb % sz:
+            raise ValueError("points: not a whole number of %d-byte points" % sz)
+        out = (C.c_uint8 * max(nb, 1))()
+        fn = self.lib.c.wsnark_g1_ntt if g == 1 else self.lib.c.wsnark_g2_ntt
+        self.lib.check(fn(p, nb // sz, 1 if inverse else 0, out))
+        return bytes(out)[:nb]
+
+    def setup_key(self, powers, circuit, pkey=False):
+        """The first key of a ceremony: the key of `circuit` under delta = gamma = 1 from a powers-of-tau transcript
+        (wsnark_pkey_setup / _setup_pkey), the key contribute_key is then applied to.
+        powers: {"domain": n, "tau_g1": 2n points (tau^k G1), "tau_g2": n points, "alpha_tau_g1": n, "beta_tau_g1": n, "beta_g2": 128
+        bytes}; circuit: {"n_vars", "n_public", "domain", "polsA", "polsB", "polsC"}, the record streams of a key plus the C
+        matrix's (synth.circuit_blobs).  Returns (the key -- a sections dict as load_key takes it, or proving_key.bin bytes with
+        pkey=True --, (IC points, gamma2 bytes) for the verification key, report dict: "tau_g1", "tau_g2", "alpha_tau_g1",
+        "beta_tau_g1" -> {points, infinity, bad, first_bad, first_reason}, beta_g2, ok, msm_columns, ms).  An unreduced or off-curve
+        power is a result: ok is False and the key is None.  Whether the powers ARE powers of one tau is not tested here."""
+        ps, keep_p = _powers_struct(powers)
+        cs, keep_c = _circuit_struct(circuit)
+        nv, npub, dom = circuit["n_vars"], circuit["n_public"], circuit["domain"]
+        rep = _SetupReport()
+        ic = (C.c_uint8 * max(64 * (npub + 1), 1))()
+        if pkey:
+            n = C.c_size_t()
+            self.lib.check(self.lib.c.wsnark_pkey_setup_size(C.byref(cs), C.byref(n)))
+            out = (C.c_uint8 * n.value)()
+            self.lib.check(self.lib.c.wsnark_pkey_setup_pkey(C.byref(ps), C.byref(cs), out, n.value, C.byref(n), ic, C.byref(rep)))
+            key = bytes(out)[:n.value] if rep.ok else None
+        else:
+            nC = max(nv - npub - 1, 0)
+            sizes = (("pointsA", 64 * nv), ("pointsB1", 64 * nv), ("pointsB2", 128 * nv), ("pointsC", 64 * nC), ("pointsH", 64 * dom),
+                     ("alfa1", 64), ("beta1", 64), ("delta1", 64), ("beta2", 128), ("delta2", 128))
+            bufs = [(C.c_uint8 * max(sz, 1))() for _, sz in sizes]
+            self.lib.check(self.lib.c.wsnark_pkey_setup(C.byref(ps), C.byref(cs), *bufs, ic, C.byref(rep)))
+            key = None
+            if rep.ok:
+                key = {"n_vars": nv, "n_public": npub, "domain": dom, "polsA": bytes(circuit["polsA"]), "polsB": bytes(circuit["polsB"])}
+                for (name, sz), b in zip(sizes, bufs):
+                    key[name] = bytes(b)[:sz]
+        report = _setup_report_dict(rep)
+        vk_parts = ([bytes(ic)[64 * i:64 * i + 64] for i in range(npub + 1)], G2_GEN) if rep.ok else None
+        return key, vk_parts, report
 
     def contribute_key(self, pkey=None, sections=None, path=None, out_path=None, d=None):
         """One phase-2 contribution: the same key under delta * d.  Exactly one of pkey (proving_key.bin bytes), sections (the

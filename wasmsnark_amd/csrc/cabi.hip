@@ -13,6 +13,7 @@ static_assert(sizeof(Affine<Fq>) == 64 && sizeof(Affine<Fq2>) == 128, "affine la
 static_assert(sizeof(Jac<Fq>) == 96 && sizeof(Jac<Fq2>) == 192, "jacobian layouts");
 static_assert(sizeof(XYZZ<Fq>) == 128 && sizeof(XYZZ<Fq2>) == 256, "xyzz layouts");
 static_assert(sizeof(wsnark_pkey_delta_report_t) == 104 && sizeof(wsnark_pkey_delta_verdict_t) == 40, "the bindings read these by offset");
+static_assert(sizeof(wsnark_pkey_setup_report_t) == 192, "the bindings read this by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
 // addon runs on the libuv pool): select the context's device first.
@@ -358,6 +359,29 @@ int wsnark_pkey_contribute_file(const char* in_path, const char* out_path, const
     int rc = in.open(in_path);
     return rc ? rc : pkey_contribute_file(in.S, in.file, in_path, out_path, (const uint8_t*)d32, rep);
 }
+// ---- the first key of a ceremony (pkeysetup.hip) ----
+int wsnark_g1_ntt(const void* points, uint64_t n, int inverse, void* out) {
+    REQUIRE_CTX();
+    return g1_group_ntt(points, n, inverse, out);
+}
+int wsnark_g2_ntt(const void* points, uint64_t n, int inverse, void* out) {
+    REQUIRE_CTX();
+    return g2_group_ntt(points, n, inverse, out);
+}
+int wsnark_pkey_setup(const wsnark_powers_t* powers, const wsnark_circuit_t* circuit, void* out_pointsA, void* out_pointsB1, void* out_pointsB2,
+                      void* out_pointsC, void* out_pointsH, void* out_alfa1_64, void* out_beta1_64, void* out_delta1_64, void* out_beta2_128,
+                      void* out_delta2_128, void* out_ic, wsnark_pkey_setup_report_t* rep) {
+    REQUIRE_CTX();
+    void* const out[11] = {out_pointsA, out_pointsB1, out_pointsB2, out_pointsC, out_pointsH, out_alfa1_64, out_beta1_64, out_delta1_64,
+                           out_beta2_128, out_delta2_128, out_ic};
+    return pkey_setup_sections(powers, circuit, out, rep);
+}
+int wsnark_pkey_setup_pkey(const wsnark_powers_t* powers, const wsnark_circuit_t* circuit, void* out_pkey, size_t out_cap, size_t* out_len,
+                           void* out_ic, wsnark_pkey_setup_report_t* rep) {
+    REQUIRE_CTX();
+    return pkey_setup_bytes(powers, circuit, (uint8_t*)out_pkey, out_cap, out_len, (uint8_t*)out_ic, rep);
+}
+int wsnark_pkey_setup_size(const wsnark_circuit_t* circuit, size_t* out_len) { return pkey_setup_size(circuit, out_len); }
 int wsnark_pkey_delta_verify(const void* old_pkey, size_t old_len, const void* new_pkey, size_t new_len, const void* seed32,
                              wsnark_pkey_delta_verdict_t* out) {
     REQUIRE_CTX();

@@ -78,6 +78,11 @@ __device__ inline void pk_reduce(int st, uint64_t index, PkAcc* __restrict__ acc
     if (st >= 1 && st <= 3) atomicMax(&acc->first, ~(((unsigned long long)index << 3) | (unsigned long long)st));
 }
 
+// ---- one scalar for many points (pkeydelta.hip: scale_points_kernel; pkeysetup.hip: the twiddles of the group transform) ----
+// the scalar in non-adjacent form: digit i is non-zero iff bit i of nz, negative iff bit i of neg; top = index of the leading digit
+// (always +1), -1 for k = 0.  k < r < 2^254, so the form has at most 255 digits.
+struct ScaleDigits { uint64_t nz[4], neg[4]; int32_t top; };
+
 // ---- host ----
 // a section's result as the reports hold it: *first_bad = UINT64_MAX and *first_reason = 0 without a bad point
 inline void pk_decode(const PkAcc& a, uint64_t* inf, uint64_t* bad, uint64_t* first_bad, uint32_t* first_reason) {
@@ -156,6 +161,17 @@ struct RhoSum {
 int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* seed32, wsnark_pkey_report_t* out);
 int g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
 int g2_scale_batch(const void* points, uint64_t n, const void* k32, void* out);
+// d_out[i] = k d_in[i] on device-resident points in reference format (k given by its digits), on queue s; d_acc takes pk_reduce's counts
+int g1_scale_dev(Context* X, const void* d_in, uint64_t n, const ScaleDigits& D, void* d_out, PkAcc* d_acc, hipStream_t s);
+int g2_scale_dev(Context* X, const void* d_in, uint64_t n, const ScaleDigits& D, void* d_out, PkAcc* d_acc, hipStream_t s);
+// the group transforms (pkeysetup.hip)
+int g1_group_ntt(const void* points, uint64_t n, int inverse, void* out);
+int g2_group_ntt(const void* points, uint64_t n, int inverse, void* out);
+// out: pointsA, pointsB1, pointsB2, pointsC, pointsH, alfa1, beta1, delta1, beta2, delta2, IC
+int pkey_setup_sections(const wsnark_powers_t* P, const wsnark_circuit_t* K, void* const out[11], wsnark_pkey_setup_report_t* rep);
+int pkey_setup_size(const wsnark_circuit_t* K, size_t* out_len);
+int pkey_setup_bytes(const wsnark_powers_t* P, const wsnark_circuit_t* K, uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* out_ic,
+                     wsnark_pkey_setup_report_t* rep);
 int pkey_contribute_sections(const KeySections& S, const uint8_t* d32, uint8_t* out_pointsC, uint8_t* out_pointsH, uint8_t* out_delta1,
                              uint8_t* out_delta2, wsnark_pkey_delta_report_t* rep);
 // S: the sections of the image pkey[0 .. len) (pkey_parse)

@@ -43,10 +43,7 @@ namespace wsnark {
 using namespace hostpair;
 
 // ---- device ----
-// the scalar in non-adjacent form: digit i is non-zero iff bit i of nz, negative iff bit i of neg; top = index of the leading digit
-// (always +1), -1 for k = 0.  k < r < 2^254, so the form has at most 255 digits.
-struct ScaleDigits { uint64_t nz[4], neg[4]; int32_t top; };
-
+// (the scalar in non-adjacent form: keybytes.h, ScaleDigits)
 template <class C>
 __global__ __launch_bounds__(256) void scale_points_kernel(const typename C::AffP* __restrict__ pts, uint64_t n, uint64_t base, ScaleDigits D,
                                                              typename C::El curve_b, int norm, typename C::AffP* __restrict__ out,
@@ -384,6 +381,28 @@ int contribute_run(const KeySections& S, const Secret& K, const Sink& outC, cons
     return WS_OK;
 }
 }  // namespace
+
+// the kernel alone, on points that are already on the device (pkeysetup.hip: the 1/n of an inverse group transform)
+template <class C>
+static int scale_dev(Context* X, const void* d_in, uint64_t n, const ScaleDigits& D, void* d_out, PkAcc* d_acc, hipStream_t s) {
+    typedef typename C::AffP AffP;
+    typename C::El cb;
+    const int rc = curve_b(&cb);
+    if (rc) return rc;
+    const int norm = delta_norm();
+    X->timer.begin(scale_name<C>(norm), s);
+    hipLaunchKernelGGL(scale_points_kernel<C>, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, reinterpret_cast<const AffP*>(d_in), n, (uint64_t)0, D, cb,
+                       norm, reinterpret_cast<AffP*>(d_out), d_acc);
+    WS_HIP_CHECK(hipGetLastError());
+    X->timer.end(s);
+    return WS_OK;
+}
+int g1_scale_dev(Context* X, const void* d_in, uint64_t n, const ScaleDigits& D, void* d_out, PkAcc* d_acc, hipStream_t s) {
+    return scale_dev<G1R29>(X, d_in, n, D, d_out, d_acc, s);
+}
+int g2_scale_dev(Context* X, const void* d_in, uint64_t n, const ScaleDigits& D, void* d_out, PkAcc* d_acc, hipStream_t s) {
+    return scale_dev<G2R29>(X, d_in, n, D, d_out, d_acc, s);
+}
 
 int g1_scale_batch(const void* points, uint64_t n, const void* k32, void* out) { return scale_batch<G1R29>(points, n, k32, out); }
 int g2_scale_batch(const void* points, uint64_t n, const void* k32, void* out) { return scale_batch<G2R29>(points, n, k32, out); }

@@ -108,6 +108,23 @@ function deltaVerdict(ab) {
     DELTA_CHECKS.forEach((name, k) => { out.checks[name] = (run >> k) & 1 ? !((bad >> k) & 1) : null; });
     return out;
 }
+/* wsnark_pkey_setup_report_t (192 bytes) -> the report object of newKey() */
+const POWERS_ARRAYS = ["tauG1", "tauG2", "alphaTauG1", "betaTauG1"];
+function setupReport(ab) {
+    const v = new DataView(ab, 0, 192);
+    const u64 = (o) => Number(v.getBigUint64(o, true));
+    const out = {};
+    POWERS_ARRAYS.forEach((name, k) => {
+        const bad = u64(64 + 8 * k);
+        out[name] = { points: u64(8 * k), infinity: u64(32 + 8 * k), bad, firstBad: bad ? u64(96 + 8 * k) : null,
+                      firstReason: bad ? KEY_REASONS[v.getUint32(128 + 4 * k, true)] : null };
+    });
+    out.betaG2 = KEY_REASONS[v.getUint32(144, true)];
+    out.ok = v.getUint32(148, true) === 1;
+    out.msmColumns = v.getUint32(152, true);
+    out.ms = { transforms: v.getFloat64(160, true), columnSums: v.getFloat64(168, true), hexps: v.getFloat64(176, true), total: v.getFloat64(184, true) };
+    return out;
+}
 function firstFinding(rep) {
     for (const name of KEY_SECTIONS) if (rep[name].bad) return `${rep[name].bad} bad point(s) in section ${name}, the first at index ${rep[name].firstBad}: ${rep[name].firstReason}`;
     for (const name of KEY_FIXED) if (rep.fixed[name]) return `${name}: ${rep.fixed[name]}`;
@@ -218,6 +235,32 @@ class Bn128 {
         const ab = await addon.contributeKey(key, isPath ? opts.outPath : null, opts && opts.entropy ? opts.entropy : null);
         const report = deltaReport(ab);
         return { key: !report.ok ? null : isPath ? opts.outPath : ab.slice(104), report };
+    }
+    /* No counterpart in the reference: the transform over GROUP elements (include/wsnark.h: wsnark_g{1,2}_ntt) -- fft(odd = 0) / ifft
+     * applied to the points' discrete logarithms, natural order in and out.  group: 1 (64-byte affine Montgomery points) or 2 (128);
+     * a power-of-two number of points up to 2^24; a result at infinity is zero bytes.  Resolves to a fresh ArrayBuffer. */
+    groupNtt(group, points, inverse) {
+        if (!this._live) return Promise.reject(new Error("wsnark: this Bn128 object has been terminated"));
+        if (this._group) return Promise.reject(new Error("wsnark: groupNtt runs on a single GPU (build a Bn128 without {devices})"));
+        asBytes(points);
+        return addon.groupNtt(group, points, !!inverse);
+    }
+    /* No counterpart in the reference (snarkjs: `zkey new`): the first key of a ceremony, the key of a circuit under delta = gamma = 1
+     * from a powers-of-tau transcript (include/wsnark.h: wsnark_pkey_setup_pkey) -- the key contributeKey() is then applied to.
+     * powers: {domain, tauG1 (2 x domain points), tauG2, alphaTauG1, betaTauG1 (domain points each), betaG2 (128 bytes)}; circuit:
+     * {nVars, nPublic, domain, polsA, polsB, polsC}: a key's two record streams and the C matrix's.  Resolves to {key: proving_key.bin
+     * as an ArrayBuffer, ic: the nPublic + 1 IC points of the verification key (gamma2 and delta2 are the G2 generator), report}; an
+     * unreduced or off-curve power is a result ({key: null, ic: null, report: {ok: false, ...}}), not a rejection. */
+    async newKey(powers, circuit) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: newKey runs on a single GPU (build a Bn128 without {devices})");
+        if (powers.domain !== circuit.domain) throw new TypeError("newKey: the powers and the circuit name different domains");
+        const bufs = [powers.tauG1, powers.tauG2, powers.alphaTauG1, powers.betaTauG1, powers.betaG2, circuit.polsA, circuit.polsB, circuit.polsC];
+        bufs.forEach(asBytes);
+        const ab = await addon.newKey(circuit.nVars, circuit.nPublic, circuit.domain, bufs);
+        const report = setupReport(ab);
+        const head = 192 + 64 * (circuit.nPublic + 1);
+        return { key: report.ok ? ab.slice(head) : null, ic: report.ok ? ab.slice(192, head) : null, report };
     }
     /* What the next participant runs: is newKey exactly oldKey under another delta (include/wsnark.h: wsnark_pkey_delta_verify)?  Both
      * keys as bytes, or both as file paths.  opts.seed: 32 bytes for the two random combinations, by default from the OS (a seed the

@@ -71,6 +71,11 @@ static struct {
     int (*pkey_contribute_file)(const char*, const char*, const void*, void*);
     int (*pkey_delta_verify)(const void*, size_t, const void*, size_t, const void*, void*);
     int (*pkey_delta_verify_file)(const char*, const char*, const void*, void*);
+    /* the first key of a ceremony (include/wsnark.h: wsnark_g{1,2}_ntt, wsnark_pkey_setup_pkey) */
+    int (*g1_ntt)(const void*, uint64_t, int, void*);
+    int (*g2_ntt)(const void*, uint64_t, int, void*);
+    int (*pkey_setup_pkey)(const void*, const void*, void*, size_t, size_t*, void*, void*);
+    int (*pkey_setup_size)(const void*, size_t*);
     char dir[4096];
 } L;
 
@@ -114,6 +119,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(pkey_check, "wsnark_pkey_check") SYM(pkey_check_file, "wsnark_pkey_check_file")
     SYM(pkey_contribute, "wsnark_pkey_contribute") SYM(pkey_contribute_file, "wsnark_pkey_contribute_file")
     SYM(pkey_delta_verify, "wsnark_pkey_delta_verify") SYM(pkey_delta_verify_file, "wsnark_pkey_delta_verify_file")
+    SYM(g1_ntt, "wsnark_g1_ntt") SYM(g2_ntt, "wsnark_g2_ntt") SYM(pkey_setup_pkey, "wsnark_pkey_setup_pkey") SYM(pkey_setup_size, "wsnark_pkey_setup_size")
 #undef SYM
     return 0;
 }
@@ -141,7 +147,7 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
-       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY };
+       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -180,10 +186,13 @@ typedef struct {
     int op, rc;
     napi_async_work work;
     napi_deferred deferred;
-    napi_ref refs[4];
+    napi_ref refs[8];
     int nrefs;
     uint8_t *a, *b, *c, *r32, *s32;
     size_t na, nb, nc;
+    uint8_t* in[8];             /* OP_NEW_KEY: tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, polsA, polsB, polsC */
+    size_t nin[8];
+    uint32_t u2;
     uint32_t u0, u1;
     int i0, i1;
     wsnark_pkey_t* key;
@@ -262,6 +271,26 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
 
 #define PKEY_DELTA_REPORT_BYTES 104      /* sizeof(wsnark_pkey_delta_report_t) */
 #define PKEY_DELTA_VERDICT_BYTES 40      /* sizeof(wsnark_pkey_delta_verdict_t) */
+#define PKEY_SETUP_REPORT_BYTES 192      /* sizeof(wsnark_pkey_setup_report_t) */
+/* wsnark_powers_t and wsnark_circuit_t (include/wsnark.h) */
+typedef struct {
+    uint32_t domain;
+    const void* tau_g1; uint64_t tau_g1_len;
+    const void* tau_g2; uint64_t tau_g2_len;
+    const void* alpha_tau_g1; uint64_t alpha_tau_g1_len;
+    const void* beta_tau_g1; uint64_t beta_tau_g1_len;
+    const void* beta_g2;
+} powers_t;
+typedef struct {
+    uint32_t n_vars, n_public, domain;
+    const void* polsA; uint64_t polsA_len;
+    const void* polsB; uint64_t polsB_len;
+    const void* polsC; uint64_t polsC_len;
+} circuit_t;
+static void job_structs(const job_t* j, powers_t* P, circuit_t* K) {
+    *P = (powers_t){j->u2, j->in[0], j->nin[0], j->in[1], j->nin[1], j->in[2], j->nin[2], j->in[3], j->nin[3], j->in[4]};
+    *K = (circuit_t){j->u0, j->u1, j->u2, j->in[5], j->nin[5], j->in[6], j->nin[6], j->in[7], j->nin[7]};
+}
 static void job_execute(napi_env env, void* data) {
     (void)env;
     job_t* j = (job_t*)data;
@@ -294,6 +323,15 @@ static void job_execute(napi_env env, void* data) {
     case OP_DELTA_VERIFY:
         j->rc = j->path ? L.pkey_delta_verify_file(j->path, j->path2, j->r32, j->out) : L.pkey_delta_verify(j->a, j->na, j->b, j->nb, j->r32, j->out);
         break;
+    case OP_GROUP_NTT: j->rc = (j->i0 == 2 ? L.g2_ntt : L.g1_ntt)(j->a, j->na / (j->i0 == 2 ? 128 : 64), j->i1, j->out); break;
+    case OP_NEW_KEY: {       /* out = the report (192 B), IC ((nPublic + 1) x 64 B), the key */
+        powers_t P;
+        circuit_t K;
+        job_structs(j, &P, &K);
+        const size_t head = PKEY_SETUP_REPORT_BYTES + ((size_t)j->u1 + 1) * 64;
+        j->rc = L.pkey_setup_pkey(&P, &K, j->out + head, j->nout - head, NULL, j->out + PKEY_SETUP_REPORT_BYTES, j->out);
+        break;
+    }
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
     case OP_GROUP_G1: j->rc = L.group_g1_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
     case OP_GROUP_G2: j->rc = L.group_g2_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
@@ -644,6 +682,54 @@ static napi_value js_delta_verify(napi_env env, napi_callback_info info) {
     return start_job(env, j, "wsnark_pkey_delta_verify");
 }
 
+/* groupNtt(group 1 | 2, points, inverse) -> Promise<ArrayBuffer>: the transform over group elements (wsnark_g{1,2}_ntt), out of place */
+static napi_value js_group_ntt(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_GROUP_NTT;
+    if (argc < 2 || napi_get_value_int32(env, argv[0], &j->i0) != napi_ok || (j->i0 != 1 && j->i0 != 2) || !get_bytes(env, argv[1], &j->a, &j->na) ||
+        j->na % (j->i0 == 2 ? 128 : 64))
+        FAIL(env, j, "expected (group 1 | 2, a whole number of affine points[, inverse])");
+    if (argc > 2) { bool b = false; napi_coerce_to_bool(env, argv[2], &argv[2]); napi_get_value_bool(env, argv[2], &b); j->i1 = b; }
+    j->nout = j->na; j->out = (uint8_t*)calloc(j->na ? j->na : 1, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[1]);
+    return start_job(env, j, "wsnark_group_ntt");
+}
+/* newKey(nVars, nPublic, domain, [tauG1, tauG2, alphaTauG1, betaTauG1, betaG2, polsA, polsB, polsC]) -> Promise<ArrayBuffer>: the
+ * wsnark_pkey_setup_report_t (192 bytes), the nPublic + 1 IC points, then proving_key.bin (wsnark_pkey_setup_pkey) */
+static napi_value js_new_key(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4], el;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (!L.h) { napi_throw_error(env, NULL, "wsnark_napi: init() has not been called (use buildBn128())"); return NULL; }
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_NEW_KEY;
+    bool is = false;
+    if (argc < 4 || napi_get_value_uint32(env, argv[0], &j->u0) != napi_ok || napi_get_value_uint32(env, argv[1], &j->u1) != napi_ok ||
+        napi_get_value_uint32(env, argv[2], &j->u2) != napi_ok || napi_is_array(env, argv[3], &is) != napi_ok || !is)
+        FAIL(env, j, "expected (nVars, nPublic, domain, [eight byte buffers])");
+    for (uint32_t k = 0; k < 8; k++)
+        if (napi_get_element(env, argv[3], k, &el) != napi_ok || !get_bytes(env, el, &j->in[k], &j->nin[k])) FAIL(env, j, "newKey: eight byte buffers");
+    if (j->nin[4] < 128) FAIL(env, j, "betaG2 must be 128 bytes");
+    powers_t P;
+    circuit_t K;
+    size_t len = 0;
+    job_structs(j, &P, &K);
+    if (L.pkey_setup_size(&K, &len)) {
+        char msg[600];
+        snprintf(msg, sizeof msg, "wsnark error: %s", L.last_error());
+        free(j);
+        napi_throw_error(env, NULL, msg);
+        return NULL;
+    }
+    j->nout = PKEY_SETUP_REPORT_BYTES + ((size_t)j->u1 + 1) * 64 + len;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[3]);      /* the array keeps its eight buffers alive */
+    return start_job(env, j, "wsnark_pkey_setup");
+}
+
 /* allocPinned(bytes) -> ArrayBuffer over pinned host memory (wsnark_host_alloc): a witness written into it is DMA'd in place,
  * without the staging copy.  Freed by the GC finalizer. */
 static void pinned_finalize(napi_env env, void* data, void* hint) {
@@ -965,6 +1051,8 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"checkKey", NULL, js_check_key, NULL, NULL, NULL, napi_default, NULL},
         {"contributeKey", NULL, js_contribute_key, NULL, NULL, NULL, napi_default, NULL},
         {"deltaVerify", NULL, js_delta_verify, NULL, NULL, NULL, napi_default, NULL},
+        {"groupNtt", NULL, js_group_ntt, NULL, NULL, NULL, napi_default, NULL},
+        {"newKey", NULL, js_new_key, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},

@@ -204,6 +204,26 @@ def build_sections(circ, S, mul_base):
     return sec, (ic, P2(2))
 
 
+def powers_from_toxic(S, domain, mul_base):
+    """What a phase-1 transcript holds for a domain of n = `domain`, written down from the toxic waste: tau^k G1 for k < 2n,
+    tau^k G2, alpha tau^k G1 and beta tau^k G1 for k < n, beta G2 (the `powers` of Bn128.setup_key; wsnark_powers_t)."""
+    tp = [1] * (2 * domain)
+    for k in range(1, 2 * domain):
+        tp[k] = tp[k - 1] * S.tau % R
+    cat = lambda xs: b"".join(le32(x) for x in xs)
+    g1 = mul_base(1, cat(tp + [S.alpha * t % R for t in tp[:domain]] + [S.beta * t % R for t in tp[:domain]]))
+    g2 = mul_base(2, cat(tp[:domain] + [S.beta]))
+    return {"domain": domain, "tau_g1": g1[:128 * domain], "alpha_tau_g1": g1[128 * domain:192 * domain], "beta_tau_g1": g1[192 * domain:],
+            "tau_g2": g2[:128 * domain], "beta_g2": g2[128 * domain:]}
+
+
+def circuit_blobs(circ):
+    """The circuit in the key's own column form (the `circuit` of Bn128.setup_key; wsnark_circuit_t): the record streams a key
+    holds for A and B, and the C matrix's, which no key holds."""
+    return {"n_vars": circ.n_vars, "n_public": circ.n_public, "domain": circ.domain,
+            "polsA": _pol_blob(circ.A), "polsB": _pol_blob(circ.B), "polsC": _pol_blob(circ.C)}
+
+
 def build_key(circ, S, mul_base):
     """Returns (proving_key.bin bytes, verification key dict in the reference's JSON shape)."""
     npub = circ.n_public
