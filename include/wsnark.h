@@ -353,8 +353,8 @@ int wsnark_g2_ntt(const void* points, uint64_t n, int inverse, void* out);
  *                             the curve (per array points / infinity / bad / first_bad / first_reason, reduced on the device; tau_g1
  *                             counts all its 2n entries) and for a beta2 that fails the audit's fixed-point tests.  The outputs are
  *                             then unspecified.
- * Not tested here: whether the powers ARE powers of one tau (the pairing relations of a transcript are its own audit), and the G2
- * subgroup test of tau_g2.  No .ptau / .r1cs readers, no file-to-file variant, one GPU.  Each call takes a lane of the context; nothing
+ * Not tested here: whether the powers ARE powers of one tau, and the G2 subgroup test of tau_g2 -- both are wsnark_powers_check's
+ * (below): run it on a transcript before a key is built on it.  No .ptau / .r1cs readers, no file-to-file variant, one GPU.  Each call takes a lane of the context; nothing
  * else calls these functions and no other entry point changes. */
 typedef struct {                 /* what a phase-1 transcript holds for a domain of n = `domain` */
     uint32_t domain;             /* power of two */
@@ -391,6 +391,79 @@ int wsnark_pkey_setup(const wsnark_powers_t* powers, const wsnark_circuit_t* cir
 int wsnark_pkey_setup_pkey(const wsnark_powers_t* powers, const wsnark_circuit_t* circuit, void* out_pkey, size_t out_cap, size_t* out_len,
                            void* out_ic, wsnark_pkey_setup_report_t* rep);
 int wsnark_pkey_setup_size(const wsnark_circuit_t* circuit, size_t* out_len);
+/* ---- powers of tau: contribute to a transcript, audit one (csrc/pwtau.hip; snarkjs: `powersoftau contribute` / `powersoftau verify`) ----
+ * Phase 1 itself: the transcript wsnark_pkey_setup builds a key on.  A contribution by secrets t, a, b (non-zero mod r) turns the
+ * transcript of (tau, alpha, beta) into the one of (t tau, a alpha, b beta):
+ *   tau_g1'[k] = t^k tau_g1[k], k < 2n      tau_g2'[k] = t^k tau_g2[k], k < n
+ *   alpha_tau_g1'[k] = a t^k alpha_tau_g1[k]      beta_tau_g1'[k] = b t^k beta_tau_g1[k]      beta_g2' = b beta_g2 (host curve)
+ * -- a DIFFERENT scalar for every point: the third shape beside wsnark_g{1,2}_mul_base_batch (one base, many scalars) and
+ * wsnark_g{1,2}_scale_batch (many bases, one scalar).
+ *   wsnark_g{1,2}_mul_batch   out[i] = scalars[i] * points[i].  points / out: host, n affine Montgomery points of 64 (G1) / 128 (G2)
+ *                             bytes, x == 0 is infinity and is copied through byte for byte; scalars: n x 32 bytes plain LE, NOT
+ *                             required to be below r: reduced mod r.  A result at infinity (a scalar that is 0 mod r) is written as
+ *                             zero bytes, every other result is affine and canonical: outputs compare byte for byte.  out may be
+ *                             points.  Every input gets the audit's two cheap tests as in wsnark_g{1,2}_scale_batch (coordinates < q,
+ *                             the curve equation; NOT the G2 subgroup test): a bad point is WSNARK_ERR_FORMAT (wsnark_last_error
+ *                             names the first index and the count), out is then untouched.  n == 0: WSNARK_OK, nothing is touched;
+ *                             n > 2^24: WSNARK_ERR_SIZE; a NULL pointer: WSNARK_ERR_ARG; before wsnark_init WSNARK_ERR_NOINIT.
+ *                             Points, scalars and results stream through the staging ring in chunks of WSNARK_PWTAU_CHUNK points
+ *                             (default 2^18, clamped to [64, 2^22]): device memory does not grow with n.  Each call takes a lane.
+ *                             WSNARK_PWTAU_MUL picks the kernel's chain (same bytes): 1 = shipped: fixed signed 4-bit windows over a
+ *                             per-lane table of the point's multiples 1 .. 8, every lane adding at the same steps; 0 = a per-lane
+ *                             non-adjacent form, the chain of wsnark_g{1,2}_scale_batch with the digit branch divergent.
+ *   tau32, alpha32, beta32    32 bytes plain little-endian each, reduced mod r; a secret that is 0 mod r is WSNARK_ERR_ARG.  NULL
+ *                             draws the 32 bytes from the OS (getrandom): the production case.  The library never returns a secret
+ *                             and wipes t, a, b and the table of t^(2^j) (volatile stores) before it returns; the device buffer
+ *                             of the scalars c t^k is overwritten on its queue before the call returns, on every exit path; the
+ *                             table of t^(2^j) and c also cross to the device in a kernel's argument block, which the runtime owns.
+ *                             With three explicit secrets the call is deterministic.
+ *   outputs                   out_tau_g1: 2n x 64 B, out_tau_g2: n x 128 B, out_alpha_tau_g1, out_beta_tau_g1: n x 64 B,
+ *                             out_beta_g2_128.  An output may BE its input (in place); any other overlap is not allowed.
+ *   errors                    what the loaders reject fails before anything is written, the report untouched: a NULL array, output
+ *                             or report (WSNARK_ERR_ARG), domain not a power of two in [2, 2^24] (WSNARK_ERR_SIZE), an array shorter
+ *                             than its domain implies (WSNARK_ERR_FORMAT); before wsnark_init WSNARK_ERR_NOINIT.
+ *   a bad power is a RESULT   as in wsnark_pkey_setup: WSNARK_OK with ok = 0, per array points / infinity / bad / first_bad /
+ *                             first_reason reduced on the device, independent of the chunking; a beta_g2 that fails the audit's
+ *                             fixed-point tests is beta2_reason (then no array is looked at).  A power at infinity (x == 0) has no
+ *                             place in a transcript: it is counted in infinity[] and makes ok = 0.  With ok = 0 the outputs are
+ *                             unspecified.  relations_run and relations_bad stay 0.
+ * wsnark_powers_check: the audit.  flags: WSNARK_PWCHECK_POINTS, WSNARK_PWCHECK_RELATIONS, 0 = both (as wsnark_pkey_check).
+ *   points     every entry of the four arrays: coordinates < q, the curve equation; tau_g2 also the order-r subgroup test of the key
+ *              audit (WSNARK_PK_OUTSIDE_SUBGROUP) -- the test wsnark_pkey_setup leaves out; beta_g2 the fixed-point tests; infinity
+ *              counted as above.
+ *   relations  rho_k as in the key audit (ChaCha20, key = seed32, counter = the global index k), T2 = tau_g2[1]:
+ *     bit 0  tau_g1[0] and tau_g2[0] are the standard generators (byte compare)
+ *     bit 1  e(sum_{k<2n-1} rho_k tau_g1[k+1], G2) = e(sum rho_k tau_g1[k], T2)
+ *     bit 2  e(tau_g1[1], sum_{k<n-1} rho_k tau_g2[k]) = e(G1, sum rho_k tau_g2[k+1])
+ *     bit 3  e(sum_{k<n-1} rho_k alpha_tau_g1[k+1], G2) = e(sum rho_k alpha_tau_g1[k], T2)      bit 4  the same for beta_tau_g1
+ *     bit 5  e(beta_tau_g1[0], G2) = e(G1, beta_g2)
+ *              Bits 1 and 2 together say that both arrays are the consecutive powers of ONE tau (bit 2's k = 0 term ties T2 to
+ *              tau_g1[1]).  Each bit is two sums over the SAME rho against one array at offsets k and k + 1, by the ordinary MSMs chunk
+ *              by chunk, and two host Miller loops.  A relation runs only if every point it involves passed the point tests (or they
+ *              were not asked for); one that did not run leaves its relations_run bit clear, and then ok = 0.
+ *              seed32 == NULL: 32 bytes from the OS.  As in the key audit the sums are sound with probability 1 - 2^-128 over a seed
+ *              the transcript's author did NOT know; a fixed or published seed gives no soundness at all.
+ *   The audit cannot tell WHO contributed, nor whether a transcript descends from an earlier one: that needs each contributor's proof
+ *   of knowledge, which -- like a random beacon, .ptau readers and writers, file-to-file variants and more than one GPU -- is out of
+ *   scope here.  Errors as for the contribution; flags with unknown bits: WSNARK_ERR_ARG.  Nothing else calls these functions and
+ *   no other entry point changes. */
+int wsnark_g1_mul_batch(const void* points, const void* scalars, uint64_t n, void* out_affine);
+int wsnark_g2_mul_batch(const void* points, const void* scalars, uint64_t n, void* out_affine);
+#define WSNARK_PWCHECK_POINTS    1u
+#define WSNARK_PWCHECK_RELATIONS 2u      /* flags == 0 means both */
+typedef struct {
+    uint64_t points[4], infinity[4], bad[4];   /* WSNARK_PW_TAU_G1 .. WSNARK_PW_BETA_TAU_G1 */
+    uint64_t first_bad[4];               /* UINT64_MAX if none */
+    uint32_t first_reason[4];            /* WSNARK_PK_UNREDUCED / WSNARK_PK_OFF_CURVE / WSNARK_PK_OUTSIDE_SUBGROUP (tau_g2, the audit) */
+    uint32_t beta2_reason;               /* 0 = good */
+    uint32_t relations_run, relations_bad;   /* bits 0..5 as above; the contribution leaves both 0 */
+    uint32_t ok;                         /* 1 iff nothing is bad or at infinity and every requested check was run */
+    double   ms[4];                      /* contribution: device, host, 0, whole call; audit: points, relation sums, pairings, whole call */
+} wsnark_powers_report_t;
+int wsnark_powers_contribute(const wsnark_powers_t* in, const void* tau32, const void* alpha32, const void* beta32,
+                             void* out_tau_g1, void* out_tau_g2, void* out_alpha_tau_g1, void* out_beta_tau_g1,
+                             void* out_beta_g2_128, wsnark_powers_report_t* rep);
+int wsnark_powers_check(const wsnark_powers_t* powers, uint32_t flags, const void* seed32, wsnark_powers_report_t* rep);
 /* which share a handle holds: (0, 1, 0, nVars, domain, 0) for a whole key.  Any out pointer may be NULL. */
 int wsnark_pkey_shard_info(const wsnark_pkey_t* handle, uint32_t* rank, uint32_t* world, uint64_t* first_signal,
                            uint64_t* n_signals, uint64_t* n_hexps, uint32_t* h_interleave_log);

@@ -130,6 +130,40 @@ def _setup_report_dict(r):
     return out
 
 
+class _PowersReport(C.Structure):  # wsnark_powers_report_t
+    _fields_ = [("points", C.c_uint64 * 4), ("infinity", C.c_uint64 * 4), ("bad", C.c_uint64 * 4), ("first_bad", C.c_uint64 * 4),
+                ("first_reason", C.c_uint32 * 4), ("beta2_reason", C.c_uint32), ("relations_run", C.c_uint32), ("relations_bad", C.c_uint32),
+                ("ok", C.c_uint32), ("ms", C.c_double * 4)]
+
+
+# bits 0..5 of wsnark_powers_report_t.relations_run / relations_bad
+POWERS_RELATIONS = ("generators", "tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "beta_g2")
+
+
+def _powers_report_dict(r, ms_names):
+    out = {}
+    for k, name in enumerate(POWERS_ARRAYS):
+        bad = int(r.bad[k])
+        out[name] = {"points": int(r.points[k]), "infinity": int(r.infinity[k]), "bad": bad,
+                     "first_bad": int(r.first_bad[k]) if bad else None, "first_reason": KEY_REASONS[r.first_reason[k]] if bad else None}
+    out["beta_g2"] = KEY_REASONS[r.beta2_reason]
+    out["relations"] = {name: (None if not (r.relations_run >> k) & 1 else not (r.relations_bad >> k) & 1)
+                        for k, name in enumerate(POWERS_RELATIONS)}       # None: not run; True: holds; False: violated
+    out["relations_run"], out["relations_bad"] = int(r.relations_run), int(r.relations_bad)
+    out["ok"] = bool(r.ok)
+    out["ms"] = {name: r.ms[k] for k, name in ms_names}
+    return out
+
+
+def _secret32(v, name):
+    if v is None:
+        return None
+    b = int(v).to_bytes(32, "little") if isinstance(v, int) else bytes(v)
+    if len(b) != 32:
+        raise ValueError("%s must be 32 bytes" % name)
+    return b
+
+
 def _powers_struct(powers):
     """dict of byte strings -> (wsnark_powers_t, the buffers it points into)"""
     ps, keep = _Powers(powers["domain"]), []
@@ -614,7 +648,8 @@ class Bn128:
         matrix's (synth.circuit_blobs).  Returns (the key -- a sections dict as load_key takes it, or proving_key.bin bytes with
         pkey=True --, (IC points, gamma2 bytes) for the verification key, report dict: "tau_g1", "tau_g2", "alpha_tau_g1",
         "beta_tau_g1" -> {points, infinity, bad, first_bad, first_reason}, beta_g2, ok, msm_columns, ms).  An unreduced or off-curve
-        power is a result: ok is False and the key is None.  Whether the powers ARE powers of one tau is not tested here."""
+        power is a result: ok is False and the key is None.  Whether the powers ARE powers of one tau is not tested here: that is
+        check_powers, the transcript's own audit."""
         ps, keep_p = _powers_struct(powers)
         cs, keep_c = _circuit_struct(circuit)
         nv, npub, dom = circuit["n_vars"], circuit["n_public"], circuit["domain"]
@@ -640,6 +675,61 @@ class Bn128:
         report = _setup_report_dict(rep)
         vk_parts = ([bytes(ic)[64 * i:64 * i + 64] for i in range(npub + 1)], G2_GEN) if rep.ok else None
         return key, vk_parts, report
+
+    # --- powers of tau (csrc/pwtau.hip; no reference counterpart -- snarkjs: powersoftau contribute / powersoftau verify) ---
+    def mul_points(self, g, points, scalars):
+        """scalars[i] * points[i]: a scalar PER point (affine Montgomery points of 64 bytes for g = 1, 128 for g = 2; x == 0 is
+        infinity and is copied through; scalars: 32 bytes plain LE each, any 256-bit value, reduced mod r).  A result at infinity
+        is zero bytes: wsnark_g{1,2}_mul_batch -- the third shape beside mul_base (one base) and scale_points (one scalar)."""
+        p, nb = _ro(points)
+        k, nk = _ro(scalars)
+        sz = 64 if g == 1 else 128
+        if nb % sz or nk % 32 or nb // sz != nk // 32:
+            raise ValueError("mul_points: %d-byte points and 32-byte scalars, as many of one as of the other" % sz)
+        out = (C.c_uint8 * max(nb, 1))()
+        fn = self.lib.c.wsnark_g1_mul_batch if g == 1 else self.lib.c.wsnark_g2_mul_batch
+        self.lib.check(fn(p, k, nb // sz, out))
+        return bytes(out)[:nb]
+
+    def contribute_powers(self, powers, tau=None, alpha=None, beta=None):
+        """One phase-1 contribution: the transcript of (tau, alpha, beta) becomes the one of (t tau, a alpha, b beta)
+        (wsnark_powers_contribute).  powers: the dict of setup_key.  tau, alpha, beta: ints or 32 bytes plain LE, non-zero mod r --
+        for tests; None draws the secret from the OS inside the library, which never returns it and wipes it: the production
+        case.  Returns (new powers dict, report dict: the four arrays -> {points, infinity, bad, first_bad, first_reason}, beta_g2,
+        relations_run, relations_bad (both 0 here), ok, ms).  A bad power or one at infinity is a result: ok is False and the
+        returned powers are None."""
+        ps, keep = _powers_struct(powers)
+        n = powers["domain"]
+        secrets = [_secret32(v, name) for v, name in ((tau, "tau"), (alpha, "alpha"), (beta, "beta"))]
+        sizes = (("tau_g1", 128 * n), ("tau_g2", 128 * n), ("alpha_tau_g1", 64 * n), ("beta_tau_g1", 64 * n), ("beta_g2", 128))
+        bufs = [(C.c_uint8 * max(sz, 1))() for _, sz in sizes]
+        rep = _PowersReport()
+        self.lib.check(self.lib.c.wsnark_powers_contribute(C.byref(ps), *secrets, *bufs, C.byref(rep)))
+        new = None
+        if rep.ok:
+            new = {"domain": n}
+            for (name, sz), b in zip(sizes, bufs):
+                new[name] = bytes(b)[:sz]
+        return new, _powers_report_dict(rep, ((0, "device"), (1, "host"), (3, "total")))
+
+    def check_powers(self, powers, points=True, relations=True, seed=None):
+        """The audit of a powers-of-tau transcript (wsnark_powers_check): every power is a reduced, on-curve point (tau_g2: of order
+        r) and none is infinity; tau_g1[0], tau_g2[0] are the generators; both tau arrays are the consecutive powers of ONE tau,
+        alpha_tau_g1 and beta_tau_g1 are those powers times one constant each, beta_g2 holds beta_tau_g1[0]'s logarithm.  seed: 32
+        bytes for the random combinations; None draws them from the OS, which is what makes them sound -- a seed the
+        transcript's author could know proves nothing.  Returns the report dict of contribute_powers with relations (True holds /
+        False violated / None not run).  A bad transcript is a result, not an exception.  The audit cannot tell who contributed
+        nor whether the transcript descends from an earlier one."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        flags = (1 if points else 0) | (2 if relations else 0)
+        if not flags:
+            raise ValueError("check_powers: nothing to check")
+        ps, keep = _powers_struct(powers)
+        sb = _ro(bytes(seed))[0] if seed is not None else None
+        rep = _PowersReport()
+        self.lib.check(self.lib.c.wsnark_powers_check(C.byref(ps), flags, sb, C.byref(rep)))
+        return _powers_report_dict(rep, ((0, "points"), (1, "relation_sums"), (2, "pairings"), (3, "total")))
 
     def contribute_key(self, pkey=None, sections=None, path=None, out_path=None, d=None):
         """One phase-2 contribution: the same key under delta * d.  Exactly one of pkey (proving_key.bin bytes), sections (the

@@ -14,6 +14,7 @@ static_assert(sizeof(Jac<Fq>) == 96 && sizeof(Jac<Fq2>) == 192, "jacobian layout
 static_assert(sizeof(XYZZ<Fq>) == 128 && sizeof(XYZZ<Fq2>) == 256, "xyzz layouts");
 static_assert(sizeof(wsnark_pkey_delta_report_t) == 104 && sizeof(wsnark_pkey_delta_verdict_t) == 40, "the bindings read these by offset");
 static_assert(sizeof(wsnark_pkey_setup_report_t) == 192, "the bindings read this by offset");
+static_assert(sizeof(wsnark_powers_report_t) == 192, "the bindings read this by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
 // addon runs on the libuv pool): select the context's device first.
@@ -382,6 +383,25 @@ int wsnark_pkey_setup_pkey(const wsnark_powers_t* powers, const wsnark_circuit_t
     return pkey_setup_bytes(powers, circuit, (uint8_t*)out_pkey, out_cap, out_len, (uint8_t*)out_ic, rep);
 }
 int wsnark_pkey_setup_size(const wsnark_circuit_t* circuit, size_t* out_len) { return pkey_setup_size(circuit, out_len); }
+// ---- powers of tau: a scalar per point, the contribution, the audit (pwtau.hip) ----
+int wsnark_g1_mul_batch(const void* points, const void* scalars, uint64_t n, void* out_affine) {
+    REQUIRE_CTX();
+    return g1_mul_batch(points, scalars, n, out_affine);
+}
+int wsnark_g2_mul_batch(const void* points, const void* scalars, uint64_t n, void* out_affine) {
+    REQUIRE_CTX();
+    return g2_mul_batch(points, scalars, n, out_affine);
+}
+int wsnark_powers_contribute(const wsnark_powers_t* in, const void* tau32, const void* alpha32, const void* beta32, void* out_tau_g1,
+                             void* out_tau_g2, void* out_alpha_tau_g1, void* out_beta_tau_g1, void* out_beta_g2_128, wsnark_powers_report_t* rep) {
+    REQUIRE_CTX();
+    uint8_t* const out[5] = {(uint8_t*)out_tau_g1, (uint8_t*)out_tau_g2, (uint8_t*)out_alpha_tau_g1, (uint8_t*)out_beta_tau_g1, (uint8_t*)out_beta_g2_128};
+    return powers_contribute(in, (const uint8_t*)tau32, (const uint8_t*)alpha32, (const uint8_t*)beta32, out, rep);
+}
+int wsnark_powers_check(const wsnark_powers_t* powers, uint32_t flags, const void* seed32, wsnark_powers_report_t* rep) {
+    REQUIRE_CTX();
+    return powers_check(powers, flags, (const uint8_t*)seed32, rep);
+}
 int wsnark_pkey_delta_verify(const void* old_pkey, size_t old_len, const void* new_pkey, size_t new_len, const void* seed32,
                              wsnark_pkey_delta_verdict_t* out) {
     REQUIRE_CTX();

@@ -78,10 +78,70 @@ __device__ inline void pk_reduce(int st, uint64_t index, PkAcc* __restrict__ acc
     if (st >= 1 && st <= 3) atomicMax(&acc->first, ~(((unsigned long long)index << 3) | (unsigned long long)st));
 }
 
-// ---- one scalar for many points (pkeydelta.hip: scale_points_kernel; pkeysetup.hip: the twiddles of the group transform) ----
+// ---- one scalar for many points (pkeydelta.hip: scale_points_kernel; pkeysetup.hip: the twiddles of the group transform; pwtau.hip:
+// a scalar per point) ----
 // the scalar in non-adjacent form: digit i is non-zero iff bit i of nz, negative iff bit i of neg; top = index of the leading digit
 // (always +1), -1 for k = 0.  k < r < 2^254, so the form has at most 255 digits.
 struct ScaleDigits { uint64_t nz[4], neg[4]; int32_t top; };
+
+// word w of a four-word digit mask held in registers: selects, so that the masks stay in registers (an index would put them in scratch)
+__device__ __forceinline__ uint64_t word4(uint64_t a0, uint64_t a1, uint64_t a2, uint64_t a3, int w) {
+    uint64_t r = a0;
+    r = w == 1 ? a1 : r;
+    r = w == 2 ? a2 : r;
+    r = w == 3 ? a3 : r;
+    return r;
+}
+// k (plain, < 2^255) -> non-adjacent form: while k: odd -> digit 2 - (k mod 4) in {1, -1}, k -= digit; k >>= 1
+WS_HD void naf_digits(const Fe& k, ScaleDigits* D) {
+    for (int i = 0; i < 4; i++) D->nz[i] = D->neg[i] = 0;
+    D->top = -1;
+    uint64_t w[5] = {k.l[0], k.l[1], k.l[2], k.l[3], 0};
+    for (int i = 0; i < 256 && (w[0] | w[1] | w[2] | w[3] | w[4]); i++) {
+        if (w[0] & 1) {
+            D->nz[i >> 6] |= (uint64_t)1 << (i & 63);
+            D->top = i;
+            if ((w[0] & 3) == 3) {                      // digit -1: k += 1
+                D->neg[i >> 6] |= (uint64_t)1 << (i & 63);
+                for (int j = 0; j < 5 && ++w[j] == 0; j++) {}
+            } else {
+                w[0] -= 1;
+            }
+        }
+        for (int j = 0; j < 4; j++) w[j] = (w[j] >> 1) | (w[j + 1] << 63);
+        w[4] >>= 1;
+    }
+}
+
+// 1 / z for every lane of a 256-lane workgroup behind ONE inversion, scale_points_kernel's tree: heap-ordered products in LDS, node
+// j = node 2j x node 2j+1, leaves 256 + lane; wavefront 0 inverts the root; down again node j holds the INVERSE of its product.
+// Every lane of the workgroup arrives (a lane with nothing to invert passes 1); once per kernel.
+template <class F>
+__device__ inline typename F::El block_inverse(const typename F::El& z) {
+    typedef typename F::El El;
+    __shared__ El tree[512];
+    const unsigned l = threadIdx.x;
+    tree[256 + l] = z;
+    __syncthreads();
+    for (unsigned w = 128; w >= 1; w >>= 1) {
+        if (l < w) tree[w + l] = F::mul(tree[2 * (w + l)], tree[2 * (w + l) + 1]);
+        __syncthreads();
+    }
+    if (l < 64) {                             // every lane the same value: a uniform chain, one store
+        const El r = F::inv(tree[1]);
+        if (l == 0) tree[1] = r;
+    }
+    __syncthreads();
+    for (unsigned w = 1; w <= 128; w <<= 1) {
+        if (l < w) {
+            const El up = tree[w + l], lo = tree[2 * (w + l)], hi = tree[2 * (w + l) + 1];
+            tree[2 * (w + l)] = F::mul(up, hi);
+            tree[2 * (w + l) + 1] = F::mul(up, lo);
+        }
+        __syncthreads();
+    }
+    return tree[256 + l];
+}
 
 // ---- host ----
 // a section's result as the reports hold it: *first_bad = UINT64_MAX and *first_reason = 0 without a bad point
@@ -181,5 +241,15 @@ int pkey_contribute_bytes(const KeySections& S, const uint8_t* pkey, size_t len,
 int pkey_contribute_file(const KeySections& S, const KeyFile& F, const char* in_path, const char* out_path, const uint8_t* d32,
                          wsnark_pkey_delta_report_t* rep);
 int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const uint8_t* seed32, wsnark_pkey_delta_verdict_t* out);
+// the audit's per-point kernels on device-resident points in reference format (pkeycheck.hip): counts into d_acc with the global index
+// base + i; the G2 one with the order-r subgroup test (PKCHECK_SUBGROUP picks its form), d_K: the pairing constants on the device
+int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s);
+int pkcheck_g2_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, const PairConsts* d_K, PkAcc* d_acc, hipStream_t s);
+// powers of tau (pwtau.hip): a scalar per point, the phase-1 contribution, the transcript's audit
+int g1_mul_batch(const void* points, const void* scalars, uint64_t n, void* out);
+int g2_mul_batch(const void* points, const void* scalars, uint64_t n, void* out);
+int powers_contribute(const wsnark_powers_t* P, const uint8_t* tau32, const uint8_t* alpha32, const uint8_t* beta32, uint8_t* const out[5],
+                      wsnark_powers_report_t* rep);
+int powers_check(const wsnark_powers_t* P, uint32_t flags, const uint8_t* seed32, wsnark_powers_report_t* rep);
 
 }  // namespace wsnark

@@ -202,6 +202,28 @@ bool same_pairing(const G1A& P1, const G2A& Q1, const G1A& P2, const G2A& Q2) {
     return f12_is_one(final_exponentiation(f12_mul(m1, m2)));
 }
 
+// the two per-point kernels alone, on points that are already on the device (pwtau.hip: the audit of a transcript's four arrays)
+int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s) {
+    G1c::El b1;
+    if (int rc = pk_curve_b(&b1, nullptr)) return rc;
+    X->timer.begin("pkcheck_g1", s);
+    hipLaunchKernelGGL(pkcheck_g1_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, reinterpret_cast<const G1c::AffP*>(d_pts), n, base, b1, d_acc);
+    WS_HIP_CHECK(hipGetLastError());
+    X->timer.end(s);
+    return WS_OK;
+}
+int pkcheck_g2_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, const PairConsts* d_K, PkAcc* d_acc, hipStream_t s) {
+    G2c::El b2;
+    if (int rc = pk_curve_b(nullptr, &b2)) return rc;
+    const int sub_mode = tuning_get("PKCHECK_SUBGROUP", 0) == 1 ? 1 : 0;
+    X->timer.begin(sub_mode ? "pkcheck_g2_psi" : "pkcheck_g2", s);
+    hipLaunchKernelGGL(pkcheck_g2_kernel, dim3(ceil_div_u64(n, 64)), dim3(64), 0, s, reinterpret_cast<const G2c::AffP*>(d_pts), n, base, b2, d_K, sub_mode,
+                       d_acc);
+    WS_HIP_CHECK(hipGetLastError());
+    X->timer.end(s);
+    return WS_OK;
+}
+
 int pkey_check_sections(const KeySections& S, uint32_t flags, const uint8_t* seed32, wsnark_pkey_report_t* out) {
     Context* X = ctx();
     if (!X) return WS_ERR_NOINIT;

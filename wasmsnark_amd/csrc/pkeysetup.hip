@@ -42,8 +42,9 @@
 //   Every power gets pk_classify's two tests before anything is computed from it; a bad one is a RESULT (ok = 0, per-array counts
 //     through pk_reduce), as in the audit and the contribution.
 //
-// Not here: whether the powers ARE powers (the pairing relations of a transcript: its own audit), the G2 subgroup test of the
-// inputs, .ptau / .r1cs parsers, file-to-file variants, more than one GPU.
+// Not here: whether the powers ARE powers of one tau and the G2 subgroup test of tau_g2 -- both are the transcript's own audit,
+// wsnark_powers_check (pwtau.hip), to be run before a key is built on the powers; .ptau / .r1cs parsers, file-to-file variants, more
+// than one GPU.
 #include <string.h>
 
 #include "keybytes.h"
@@ -64,35 +65,8 @@ __device__ inline uint64_t wave_u64(uint64_t v) {
 }
 
 // ---- device ----
-// word w of a four-word digit mask held in registers: selects, so that the masks stay in registers (an index would put them in scratch)
-__device__ __forceinline__ uint64_t word4(uint64_t a0, uint64_t a1, uint64_t a2, uint64_t a3, int w) {
-    uint64_t r = a0;
-    r = w == 1 ? a1 : r;
-    r = w == 2 ? a2 : r;
-    r = w == 3 ? a3 : r;
-    return r;
-}
-// k (plain, < 2^255) -> non-adjacent form: while k: odd -> digit 2 - (k mod 4) in {1, -1}, k -= digit; k >>= 1
-WS_HD void naf_digits(const Fe& k, ScaleDigits* D) {
-    for (int i = 0; i < 4; i++) D->nz[i] = D->neg[i] = 0;
-    D->top = -1;
-    uint64_t w[5] = {k.l[0], k.l[1], k.l[2], k.l[3], 0};
-    for (int i = 0; i < 256 && (w[0] | w[1] | w[2] | w[3] | w[4]); i++) {
-        if (w[0] & 1) {
-            D->nz[i >> 6] |= (uint64_t)1 << (i & 63);
-            D->top = i;
-            if ((w[0] & 3) == 3) {                      // digit -1: k += 1
-                D->neg[i >> 6] |= (uint64_t)1 << (i & 63);
-                for (int j = 0; j < 5 && ++w[j] == 0; j++) {}
-            } else {
-                w[0] -= 1;
-            }
-        }
-        for (int j = 0; j < 4; j++) w[j] = (w[j] >> 1) | (w[j + 1] << 63);
-        w[4] >>= 1;
-    }
-}
-
+// (word4, naf_digits and block_inverse -- the digit masks in registers, the recoding, the shared inversion -- are keybytes.h's: the
+// phase-1 contribution's kernel, pwtau.hip, uses them too)
 struct TwiddleBase { Fe p[24]; };      // w^(2^i), Montgomery
 __global__ __launch_bounds__(256) void group_twiddle_kernel(TwiddleBase W, uint32_t count, ScaleDigits* __restrict__ out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -103,36 +77,6 @@ __global__ __launch_bounds__(256) void group_twiddle_kernel(TwiddleBase W, uint3
     ScaleDigits D;
     naf_digits(Fr::from_mont(acc), &D);
     out[k] = D;
-}
-
-// 1 / z for every lane of a 256-lane workgroup behind ONE inversion, scale_points_kernel's tree: heap-ordered products in LDS, node
-// j = node 2j x node 2j+1, leaves 256 + lane; wavefront 0 inverts the root; down again node j holds the INVERSE of its product.
-// Every lane of the workgroup arrives (a lane with nothing to invert passes 1); once per kernel.
-template <class F>
-__device__ inline typename F::El block_inverse(const typename F::El& z) {
-    typedef typename F::El El;
-    __shared__ El tree[512];
-    const unsigned l = threadIdx.x;
-    tree[256 + l] = z;
-    __syncthreads();
-    for (unsigned w = 128; w >= 1; w >>= 1) {
-        if (l < w) tree[w + l] = F::mul(tree[2 * (w + l)], tree[2 * (w + l) + 1]);
-        __syncthreads();
-    }
-    if (l < 64) {                             // every lane the same value: a uniform chain, one store
-        const El r = F::inv(tree[1]);
-        if (l == 0) tree[1] = r;
-    }
-    __syncthreads();
-    for (unsigned w = 1; w <= 128; w <<= 1) {
-        if (l < w) {
-            const El up = tree[w + l], lo = tree[2 * (w + l)], hi = tree[2 * (w + l) + 1];
-            tree[2 * (w + l)] = F::mul(up, hi);
-            tree[2 * (w + l) + 1] = F::mul(up, lo);
-        }
-        __syncthreads();
-    }
-    return tree[256 + l];
 }
 
 template <class C>

@@ -125,6 +125,29 @@ function setupReport(ab) {
     out.ms = { transforms: v.getFloat64(160, true), columnSums: v.getFloat64(168, true), hexps: v.getFloat64(176, true), total: v.getFloat64(184, true) };
     return out;
 }
+/* wsnark_powers_report_t (192 bytes) -> the report object of contributePowers() and checkPowers(); relations: true holds, false
+ * violated, null not run */
+const POWERS_RELATIONS = ["generators", "tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2"];
+function powersReport(ab, msNames) {
+    const v = new DataView(ab, 0, 192);
+    const u64 = (o) => Number(v.getBigUint64(o, true));
+    const out = {};
+    POWERS_ARRAYS.forEach((name, k) => {
+        const bad = u64(64 + 8 * k);
+        out[name] = { points: u64(8 * k), infinity: u64(32 + 8 * k), bad, firstBad: bad ? u64(96 + 8 * k) : null,
+                      firstReason: bad ? KEY_REASONS[v.getUint32(128 + 4 * k, true)] : null };
+    });
+    out.betaG2 = KEY_REASONS[v.getUint32(144, true)];
+    const run = v.getUint32(148, true), bad = v.getUint32(152, true);
+    out.relations = {};
+    POWERS_RELATIONS.forEach((name, k) => { out.relations[name] = (run >> k) & 1 ? !((bad >> k) & 1) : null; });
+    out.relationsRun = run;
+    out.relationsBad = bad;
+    out.ok = v.getUint32(156, true) === 1;
+    out.ms = {};
+    msNames.forEach((name, k) => { if (name) out.ms[name] = v.getFloat64(160 + 8 * k, true); });
+    return out;
+}
 function firstFinding(rep) {
     for (const name of KEY_SECTIONS) if (rep[name].bad) return `${rep[name].bad} bad point(s) in section ${name}, the first at index ${rep[name].firstBad}: ${rep[name].firstReason}`;
     for (const name of KEY_FIXED) if (rep.fixed[name]) return `${name}: ${rep.fixed[name]}`;
@@ -261,6 +284,48 @@ class Bn128 {
         const report = setupReport(ab);
         const head = 192 + 64 * (circuit.nPublic + 1);
         return { key: report.ok ? ab.slice(head) : null, ic: report.ok ? ab.slice(192, head) : null, report };
+    }
+    /* No counterpart in the reference: scalars[i] * points[i], a scalar PER point (include/wsnark.h: wsnark_g{1,2}_mul_batch) -- the
+     * third shape beside one base with many scalars and many bases with one scalar.  group: 1 (64-byte affine Montgomery points) or 2
+     * (128); scalars: 32 bytes plain little-endian each, reduced mod r; x == 0 is infinity and is copied through; a result at infinity
+     * is zero bytes.  Resolves to a fresh ArrayBuffer. */
+    mulPoints(group, points, scalars) {
+        if (!this._live) return Promise.reject(new Error("wsnark: this Bn128 object has been terminated"));
+        if (this._group) return Promise.reject(new Error("wsnark: mulPoints runs on a single GPU (build a Bn128 without {devices})"));
+        asBytes(points); asBytes(scalars);
+        return addon.mulPoints(group, points, scalars);
+    }
+    /* No counterpart in the reference (snarkjs: `powersoftau contribute`): one phase-1 contribution -- the transcript of (tau, alpha,
+     * beta) becomes the one of (t tau, a alpha, b beta) (include/wsnark.h: wsnark_powers_contribute).  powers: the object of newKey().
+     * opts.tau, opts.alpha, opts.beta: 32 bytes plain little-endian, non-zero mod r -- for tests; a secret left out is drawn from the
+     * OS inside the library, which never returns it and wipes it: the production case.  Resolves to {powers: the new transcript
+     * (ArrayBuffers), report}; a bad power or one at infinity is a result ({powers: null, report: {ok: false, ...}}). */
+    async contributePowers(powers, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: contributePowers runs on a single GPU (build a Bn128 without {devices})");
+        const bufs = [powers.tauG1, powers.tauG2, powers.alphaTauG1, powers.betaTauG1, powers.betaG2];
+        bufs.forEach(asBytes);
+        const secrets = ["tau", "alpha", "beta"].map((k) => (opts && opts[k] ? opts[k] : null));
+        const ab = await addon.contributePowers(powers.domain, bufs, secrets);
+        const report = powersReport(ab, ["device", "host", null, "total"]);
+        if (!report.ok) return { powers: null, report };
+        const n = powers.domain, o = 192;
+        return { powers: { domain: n, tauG1: ab.slice(o, o + 128 * n), tauG2: ab.slice(o + 128 * n, o + 256 * n), alphaTauG1: ab.slice(o + 256 * n, o + 320 * n),
+                           betaTauG1: ab.slice(o + 320 * n, o + 384 * n), betaG2: ab.slice(o + 384 * n, o + 384 * n + 128) }, report };
+    }
+    /* No counterpart in the reference (snarkjs: `powersoftau verify`): the audit of a transcript (include/wsnark.h:
+     * wsnark_powers_check) -- every power a reduced, on-curve point (tauG2: of order r), none at infinity, and the six pairing relations
+     * that make the arrays the consecutive powers of ONE tau.  opts.points / opts.relations === false leave that half out; opts.seed: 32
+     * bytes for the random combinations, by default from the OS (a seed the transcript's author could know proves nothing).  Resolves
+     * to the report; a bad transcript is a result, not a rejection.  The audit cannot tell who contributed. */
+    async checkPowers(powers, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: checkPowers runs on a single GPU (build a Bn128 without {devices})");
+        const flags = ((opts && opts.points === false) ? 0 : 1) | ((opts && opts.relations === false) ? 0 : 2);
+        if (!flags) throw new TypeError("checkPowers: nothing to check");
+        const bufs = [powers.tauG1, powers.tauG2, powers.alphaTauG1, powers.betaTauG1, powers.betaG2];
+        bufs.forEach(asBytes);
+        return powersReport(await addon.checkPowers(powers.domain, bufs, flags, opts && opts.seed ? opts.seed : null), ["points", "relationSums", "pairings", "total"]);
     }
     /* What the next participant runs: is newKey exactly oldKey under another delta (include/wsnark.h: wsnark_pkey_delta_verify)?  Both
      * keys as bytes, or both as file paths.  opts.seed: 32 bytes for the two random combinations, by default from the OS (a seed the

@@ -76,6 +76,11 @@ static struct {
     int (*g2_ntt)(const void*, uint64_t, int, void*);
     int (*pkey_setup_pkey)(const void*, const void*, void*, size_t, size_t*, void*, void*);
     int (*pkey_setup_size)(const void*, size_t*);
+    /* powers of tau (include/wsnark.h: wsnark_g{1,2}_mul_batch, wsnark_powers_contribute, wsnark_powers_check) */
+    int (*g1_mul)(const void*, const void*, uint64_t, void*);
+    int (*g2_mul)(const void*, const void*, uint64_t, void*);
+    int (*powers_contribute)(const void*, const void*, const void*, const void*, void*, void*, void*, void*, void*, void*);
+    int (*powers_check)(const void*, uint32_t, const void*, void*);
     char dir[4096];
 } L;
 
@@ -120,6 +125,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(pkey_contribute, "wsnark_pkey_contribute") SYM(pkey_contribute_file, "wsnark_pkey_contribute_file")
     SYM(pkey_delta_verify, "wsnark_pkey_delta_verify") SYM(pkey_delta_verify_file, "wsnark_pkey_delta_verify_file")
     SYM(g1_ntt, "wsnark_g1_ntt") SYM(g2_ntt, "wsnark_g2_ntt") SYM(pkey_setup_pkey, "wsnark_pkey_setup_pkey") SYM(pkey_setup_size, "wsnark_pkey_setup_size")
+    SYM(g1_mul, "wsnark_g1_mul_batch") SYM(g2_mul, "wsnark_g2_mul_batch") SYM(powers_contribute, "wsnark_powers_contribute") SYM(powers_check, "wsnark_powers_check")
 #undef SYM
     return 0;
 }
@@ -147,7 +153,8 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
-       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY };
+       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
+       OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -272,6 +279,7 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
 #define PKEY_DELTA_REPORT_BYTES 104      /* sizeof(wsnark_pkey_delta_report_t) */
 #define PKEY_DELTA_VERDICT_BYTES 40      /* sizeof(wsnark_pkey_delta_verdict_t) */
 #define PKEY_SETUP_REPORT_BYTES 192      /* sizeof(wsnark_pkey_setup_report_t) */
+#define POWERS_REPORT_BYTES 192          /* sizeof(wsnark_powers_report_t) */
 /* wsnark_powers_t and wsnark_circuit_t (include/wsnark.h) */
 typedef struct {
     uint32_t domain;
@@ -330,6 +338,23 @@ static void job_execute(napi_env env, void* data) {
         job_structs(j, &P, &K);
         const size_t head = PKEY_SETUP_REPORT_BYTES + ((size_t)j->u1 + 1) * 64;
         j->rc = L.pkey_setup_pkey(&P, &K, j->out + head, j->nout - head, NULL, j->out + PKEY_SETUP_REPORT_BYTES, j->out);
+        break;
+    }
+    case OP_MUL_POINTS: j->rc = (j->i0 == 2 ? L.g2_mul : L.g1_mul)(j->a, j->b, j->nb / 32, j->out); break;
+    case OP_POWERS_CONTRIBUTE: {      /* out = the report (192 B), then tau_g1', tau_g2', alpha_tau_g1', beta_tau_g1', beta_g2' */
+        powers_t P;
+        circuit_t K;
+        job_structs(j, &P, &K);
+        const size_t n = j->u1;       /* the domain if it is one the library accepts, else 0: nothing is written then */
+        uint8_t* o = j->out + POWERS_REPORT_BYTES;
+        j->rc = L.powers_contribute(&P, j->r32, j->s32, j->c, o, o + 128 * n, o + 256 * n, o + 320 * n, o + 384 * n, j->out);
+        break;
+    }
+    case OP_POWERS_CHECK: {
+        powers_t P;
+        circuit_t K;
+        job_structs(j, &P, &K);
+        j->rc = L.powers_check(&P, j->u0, j->r32, j->out);
         break;
     }
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
@@ -730,6 +755,72 @@ static napi_value js_new_key(napi_env env, napi_callback_info info) {
     return start_job(env, j, "wsnark_pkey_setup");
 }
 
+/* mulPoints(group 1 | 2, points, scalars) -> Promise<ArrayBuffer>: scalars[i] * points[i] (wsnark_g{1,2}_mul_batch), out of place */
+static napi_value js_mul_points(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_MUL_POINTS;
+    if (argc < 3 || napi_get_value_int32(env, argv[0], &j->i0) != napi_ok || (j->i0 != 1 && j->i0 != 2) || !get_bytes(env, argv[1], &j->a, &j->na) ||
+        !get_bytes(env, argv[2], &j->b, &j->nb) || j->na % (j->i0 == 2 ? 128 : 64) || j->nb % 32 || j->na / (j->i0 == 2 ? 128 : 64) != j->nb / 32)
+        FAIL(env, j, "expected (group 1 | 2, a whole number of affine points, as many 32-byte scalars)");
+    j->nout = j->na; j->out = (uint8_t*)calloc(j->na ? j->na : 1, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[1]); keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_mul_batch");
+}
+/* the five buffers of a transcript (tauG1, tauG2, alphaTauG1, betaTauG1, betaG2) into j->in[0..4], the domain into j->u2 */
+static int get_powers(napi_env env, napi_value domain, napi_value arr, job_t* j) {
+    bool is = false;
+    napi_value el;
+    if (napi_get_value_uint32(env, domain, &j->u2) != napi_ok || napi_is_array(env, arr, &is) != napi_ok || !is) return 0;
+    for (uint32_t k = 0; k < 5; k++)
+        if (napi_get_element(env, arr, k, &el) != napi_ok || !get_bytes(env, el, &j->in[k], &j->nin[k])) return 0;
+    return j->nin[4] >= 128;
+}
+/* contributePowers(domain, [tauG1, tauG2, alphaTauG1, betaTauG1, betaG2], [tau32 | null, alpha32 | null, beta32 | null]) ->
+ * Promise<ArrayBuffer>: the wsnark_powers_report_t (192 bytes), then the five parts of the new transcript in that order
+ * (wsnark_powers_contribute).  A null secret is drawn by the library and wiped. */
+static napi_value js_contribute_powers(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3], el;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_POWERS_CONTRIBUTE;
+    bool is = false;
+    if (argc < 3 || !get_powers(env, argv[0], argv[1], j) || napi_is_array(env, argv[2], &is) != napi_ok || !is)
+        FAIL(env, j, "expected (domain, [five byte buffers, betaG2 of 128 bytes], [three secrets of 32 bytes or null])");
+    uint8_t** secret[3] = {&j->r32, &j->s32, &j->c};
+    for (uint32_t k = 0; k < 3; k++) {
+        size_t ns = 0;
+        if (napi_get_element(env, argv[2], k, &el) == napi_ok && get_bytes(env, el, secret[k], &ns) && ns != 32) FAIL(env, j, "a secret must be 32 bytes");
+    }
+    const uint32_t n = j->u2;
+    j->u1 = (n >= 2 && !(n & (n - 1)) && n <= (1u << 24)) ? n : 0;      /* any other domain is rejected before a byte is written */
+    j->nout = POWERS_REPORT_BYTES + (size_t)j->u1 * 384 + 128;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[1]); keep(env, j, argv[2]);      /* the arrays keep their buffers alive */
+    return start_job(env, j, "wsnark_powers_contribute");
+}
+/* checkPowers(domain, [tauG1, tauG2, alphaTauG1, betaTauG1, betaG2], flags, seed32 | null) -> Promise<ArrayBuffer 192>: the
+ * wsnark_powers_report_t of the audit (wsnark_powers_check).  flags: 1 points, 2 relations, 0 both. */
+static napi_value js_check_powers(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_POWERS_CHECK;
+    if (argc < 3 || !get_powers(env, argv[0], argv[1], j) || napi_get_value_uint32(env, argv[2], &j->u0) != napi_ok)
+        FAIL(env, j, "expected (domain, [five byte buffers, betaG2 of 128 bytes], flags[, seed32])");
+    size_t ns = 0;
+    if (argc > 3 && get_bytes(env, argv[3], &j->r32, &ns) && ns != 32) FAIL(env, j, "the seed must be 32 bytes");
+    j->nout = POWERS_REPORT_BYTES;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[1]);
+    if (j->r32) keep(env, j, argv[3]);
+    return start_job(env, j, "wsnark_powers_check");
+}
+
 /* allocPinned(bytes) -> ArrayBuffer over pinned host memory (wsnark_host_alloc): a witness written into it is DMA'd in place,
  * without the staging copy.  Freed by the GC finalizer. */
 static void pinned_finalize(napi_env env, void* data, void* hint) {
@@ -1053,6 +1144,9 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"deltaVerify", NULL, js_delta_verify, NULL, NULL, NULL, napi_default, NULL},
         {"groupNtt", NULL, js_group_ntt, NULL, NULL, NULL, napi_default, NULL},
         {"newKey", NULL, js_new_key, NULL, NULL, NULL, napi_default, NULL},
+        {"mulPoints", NULL, js_mul_points, NULL, NULL, NULL, napi_default, NULL},
+        {"contributePowers", NULL, js_contribute_powers, NULL, NULL, NULL, napi_default, NULL},
+        {"checkPowers", NULL, js_check_powers, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},

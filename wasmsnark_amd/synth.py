@@ -217,6 +217,20 @@ def powers_from_toxic(S, domain, mul_base):
             "tau_g2": g2[:128 * domain], "beta_g2": g2[128 * domain:]}
 
 
+def contributed_toxic(S, t, a, b, circ=None):
+    """The toxic waste behind a transcript after a phase-1 contribution by (t, a, b) (Bn128.contribute_powers): a copy of S with
+    tau, alpha and beta multiplied mod r.  With circ the per-signal evaluations a_s, b_s, c_s and Z are taken again at the new tau,
+    as build_sections needs them; without it they are the old ones (powers_from_toxic reads tau, alpha and beta only)."""
+    import copy
+    S2 = copy.copy(S)
+    S2.tau, S2.alpha, S2.beta = S.tau * t % R, S.alpha * a % R, S.beta * b % R
+    if circ is not None:
+        L, S2.z = lagrange_at(S2.tau, circ.domain.bit_length() - 1)
+        ev = lambda col: sum(coef * L[c] for c, coef in col.items()) % R
+        S2.a, S2.b, S2.c = [ev(c) for c in circ.A], [ev(c) for c in circ.B], [ev(c) for c in circ.C]
+    return S2
+
+
 def circuit_blobs(circ):
     """The circuit in the key's own column form (the `circuit` of Bn128.setup_key; wsnark_circuit_t): the record streams a key
     holds for A and B, and the C matrix's, which no key holds."""
