@@ -222,8 +222,8 @@ int wsnark_pkey_file_info(const char* path, uint32_t* n_vars, uint32_t* n_public
  *                             seed32 == NULL: 32 bytes from the OS (getrandom), as the blinding values.  Bit 2 is sound with
  *                             probability 1 - 2^-128 over a seed that whoever made the key did NOT know: a fixed or published seed
  *                             gives no soundness.  What the audit cannot see: a permutation applied to B1 and B2 alike, and any
- *                             relation to the circuit (A, C, hExps against the polynomials): that needs the toxic waste or a
- *                             verification key.
+ *                             relation to the circuit (A, C, hExps against the polynomials): both are wsnark_pkey_circuit_check's
+ *                             (below), which needs the circuit and the powers of tau the key was built on, not the toxic waste.
  * A bad key is a RESULT: WSNARK_OK with ok = 0.  What the loaders reject (a short section, a bad header, a file that cannot be
  * opened) fails with the loader's code and writes nothing.  Needs wsnark_init (WSNARK_ERR_NOINIT); callable from any thread, each call
  * takes a lane of the context.  Sections are streamed through the staging ring in chunks of WSNARK_PKCHECK_CHUNK points (default
@@ -391,6 +391,59 @@ int wsnark_pkey_setup(const wsnark_powers_t* powers, const wsnark_circuit_t* cir
 int wsnark_pkey_setup_pkey(const wsnark_powers_t* powers, const wsnark_circuit_t* circuit, void* out_pkey, size_t out_cap, size_t* out_len,
                            void* out_ic, wsnark_pkey_setup_report_t* rep);
 int wsnark_pkey_setup_size(const wsnark_circuit_t* circuit, size_t* out_len);
+/* ---- a key against its circuit and its powers of tau (csrc/pkeycircuit.hip; snarkjs: `zkey verify <r1cs> <ptau> <zkey>`) ----
+ * Is this the key of THIS circuit on THIS transcript?  Before the first contribution wsnark_pkey_setup and a byte compare answer
+ * that, at the price of four group transforms; afterwards C and hExps are scaled by an unknown 1/delta and only a replay of every
+ * wsnark_pkey_delta_verify would.  This check needs neither: with rho_j = ChaCha20(seed32, counter j) for signal j < nVars (the audit's
+ * generator), u_M = (rows of matrix M) . rho and c(x) = fromMontgomery(iNTT(x)),
+ *     sum_j rho_j A_j = sum_i u_A,i L_i(tau) G = sum_k c(u_A)_k tau^k G
+ * -- a transform over the FIELD, not the group.  Split by public and private signal (p_M: columns j <= nPublic, v_M: j > nPublic,
+ * u_M = p_M + v_M; one walk of every row, lc_split_kernel), n = domain, np = nPublic, rho'_i = the generator at counter nVars + i:
+ *   bit 0  the key's nVars, nPublic and domainSize equal the circuit's, and its polsA and polsB are the circuit's byte for byte (host
+ *          memcmp).  If the COUNTS differ the bit is bad and nothing else runs.
+ *   bit 1  alfa1 == alpha_tau_g1[0], beta1 == beta_tau_g1[0], beta2 == beta_g2 (bytes)
+ *   bit 2  e(delta1, G2) = e(G1, delta2); run only if both pass the audit's fixed-point tests
+ *   bit 3  sum_j rho_j A_j  == sum_k c(u_A)_k tau_g1[k]      (equality of the normalised sums, no pairing)
+ *   bit 4  sum_j rho_j B1_j == sum_k c(u_B)_k tau_g1[k]      bit 5  sum_j rho_j B2_j == sum_k c(u_B)_k tau_g2[k]
+ *   bit 6  e(sum_{j>np} rho_j C_j, delta2) = e(K_v, G2),  K_v = sum_k [c(v_A)_k beta_tau_g1[k] + c(v_B)_k alpha_tau_g1[k] + c(v_C)_k tau_g1[k]];
+ *          point k of the C section is signal np + 1 + k and is weighted by THAT rho.  nVars == np + 1: two points at infinity, holds.
+ *   bit 7  e(sum_i rho'_i hExps_i, delta2) = e(sum_i rho'_i tau_g1[n + i] - sum_i rho'_i tau_g1[i], G2)
+ *          Bits 6 and 7 run only if bit 2 ran and held: that is what makes them mean something.
+ *   bit 8  vk given: n_inputs == nPublic, and the vk's alfa1, beta2, delta2 are the key's (after conversion to Montgomery form)
+ *   bit 9  vk given: e(sum_{j<=np} rho_j IC_j, gamma2) = e(K_p, G2), K_p as K_v over p_A, p_B, p_C; run only if n_inputs == nPublic and
+ *          the vk's gamma2 and IC points pass the audit's fixed-point tests.
+ *   vk: the layout wsnark_groth16_verify reads (plain: alfa1 | beta2 | gamma2 | delta2 | IC[0 .. n_inputs]); NULL: bits 8 and 9 are not
+ *   requested.  ok = 1 iff every requested bit ran and none is bad; a bit that did not run stays clear in checks_run.
+ *   seed32 == NULL: 32 bytes from the OS.  Each relation is sound with probability 1 - 2^-128 over a seed the key's author did NOT
+ *   know; a fixed or published seed gives no soundness.
+ *   The check does NOT test individual points: that is wsnark_pkey_check's job on the key and wsnark_powers_check's on the transcript.
+ *   Unreduced or off-curve bytes do not fault it, they only make the sums meaningless.  It cannot tell whether the circuit is the
+ *   intended one, nor who contributed.
+ *   streaming   key sections and transcript arrays go through the staging ring in chunks of WSNARK_PKCIRCUIT_CHUNK points (default
+ *               2^18, clamped to [64, 2^22]; no verdict depends on it).  The three CSR matrices and the six domain-length vectors are
+ *               resident for the call (the nVars weights only while the row sums run), everything else is bounded by the chunk; the
+ *               sums are the ordinary MSMs, partial sums added on the host.  The file variant maps the key read-only and hands every
+ *               staged range back.  Each call takes one lane; no other entry point changes.
+ *   errors      what the loaders and wsnark_pkey_setup reject fails with their code before anything is written, the verdict untouched
+ *               (a short section or array, a truncated stream, a record index >= domain, a domain that is no power of two in
+ *               [2, 2^24], the two structs' domains differing, tau_g1[0] / tau_g2[0] not the generators); a NULL pointer WSNARK_ERR_ARG;
+ *               a vk shorter than n_inputs + 1 IC points WSNARK_ERR_SIZE; before wsnark_init WSNARK_ERR_NOINIT.  A wrong key is a
+ *               RESULT: WSNARK_OK with ok = 0.
+ * wsnark_circuit_row_sums: the building block -- the six vectors themselves for caller-given weights (nVars x 32 B plain, any 256-bit
+ *   value): out_public = p_A | p_B | p_C, out_private = v_A | v_B | v_C, 3 x domain x 32 B each, Montgomery and canonical. */
+typedef struct {
+    uint32_t checks_run, checks_bad;   /* bits 0..9 as above */
+    uint32_t ok, reserved;
+    double   ms[5];                    /* matrices (CSR + row sums + transforms), key-side sums, transcript-side sums, pairings, whole call */
+} wsnark_pkey_circuit_verdict_t;
+int wsnark_pkey_circuit_check(const void* pkey, size_t len, const wsnark_powers_t* powers, const wsnark_circuit_t* circuit,
+                              const void* vk, size_t vk_len, uint64_t n_inputs, const void* seed32, wsnark_pkey_circuit_verdict_t* out);
+int wsnark_pkey_circuit_check_sections(const wsnark_key_sections_t* key, const wsnark_powers_t* powers, const wsnark_circuit_t* circuit,
+                                       const void* vk, size_t vk_len, uint64_t n_inputs, const void* seed32,
+                                       wsnark_pkey_circuit_verdict_t* out);
+int wsnark_pkey_circuit_check_file(const char* path, const wsnark_powers_t* powers, const wsnark_circuit_t* circuit,
+                                   const void* vk, size_t vk_len, uint64_t n_inputs, const void* seed32, wsnark_pkey_circuit_verdict_t* out);
+int wsnark_circuit_row_sums(const wsnark_circuit_t* circuit, const void* weights, void* out_public, void* out_private);
 /* ---- powers of tau: contribute to a transcript, audit one (csrc/pwtau.hip; snarkjs: `powersoftau contribute` / `powersoftau verify`) ----
  * Phase 1 itself: the transcript wsnark_pkey_setup builds a key on.  A contribution by secrets t, a, b (non-zero mod r) turns the
  * transcript of (tau, alpha, beta) into the one of (t tau, a alpha, b beta):

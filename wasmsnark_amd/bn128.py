@@ -96,6 +96,10 @@ class _DeltaVerdict(C.Structure):  # wsnark_pkey_delta_verdict_t
     _fields_ = [("checks_run", C.c_uint32), ("checks_bad", C.c_uint32), ("ok", C.c_uint32), ("ms", C.c_double * 3)]
 
 
+class _CircuitVerdict(C.Structure):  # wsnark_pkey_circuit_verdict_t
+    _fields_ = [("checks_run", C.c_uint32), ("checks_bad", C.c_uint32), ("ok", C.c_uint32), ("reserved", C.c_uint32), ("ms", C.c_double * 5)]
+
+
 class _Powers(C.Structure):        # wsnark_powers_t
     _fields_ = [("domain", C.c_uint32), ("tau_g1", C.c_void_p), ("tau_g1_len", C.c_uint64), ("tau_g2", C.c_void_p), ("tau_g2_len", C.c_uint64),
                 ("alpha_tau_g1", C.c_void_p), ("alpha_tau_g1_len", C.c_uint64), ("beta_tau_g1", C.c_void_p), ("beta_tau_g1_len", C.c_uint64),
@@ -206,6 +210,17 @@ def _delta_verdict_dict(v):
     out = {"checks": {name: (None if not (v.checks_run >> k) & 1 else not (v.checks_bad >> k) & 1) for k, name in enumerate(DELTA_CHECKS)},
            "checks_run": int(v.checks_run), "checks_bad": int(v.checks_bad), "ok": bool(v.ok),
            "ms": {"sums": v.ms[0], "pairings": v.ms[1], "total": v.ms[2]}}
+    return out
+
+
+# bits 0..9 of wsnark_pkey_circuit_verdict_t
+CIRCUIT_CHECKS = ("shape_and_streams", "fixed_points", "delta1~delta2", "A", "B1", "B2", "C", "H", "vk_fixed_points", "IC")
+
+
+def _circuit_verdict_dict(v):
+    out = {"checks": {name: (None if not (v.checks_run >> k) & 1 else not (v.checks_bad >> k) & 1) for k, name in enumerate(CIRCUIT_CHECKS)},
+           "checks_run": int(v.checks_run), "checks_bad": int(v.checks_bad), "ok": bool(v.ok),
+           "ms": {"matrices": v.ms[0], "key_sums": v.ms[1], "powers_sums": v.ms[2], "pairings": v.ms[3], "total": v.ms[4]}}
     return out
 
 
@@ -793,6 +808,61 @@ class Bn128:
             rc = self.lib.c.wsnark_pkey_delta_verify(bo, no, bn_, nn, sb, C.byref(v))
         self.lib.check(rc)
         return _delta_verdict_dict(v)
+
+    # --- a key against its circuit and its powers of tau (csrc/pkeycircuit.hip; no reference counterpart -- snarkjs: zkey verify) ---
+    def check_key_circuit(self, powers, circuit, pkey=None, sections=None, path=None, vk=None, seed=None):
+        """Is this the key of `circuit` on the transcript `powers`?  (wsnark_pkey_circuit_check*.)  powers, circuit: the dicts of
+        setup_key; exactly one of pkey (proving_key.bin bytes), sections (the dict of load_key) and path (a key file).  Works on
+        the first key and on a key after any number of contributions: no toxic waste, no group transform -- random combinations of
+        the key's points against field transforms of the circuit's row sums.  vk: the verification key, the JSON dict
+        groth16Verify takes (or its bytes in wsnark_groth16_verify's layout); with it the IC points and the key's fixed points are
+        checked too.  seed: as check_key's -- None draws it from the OS, which is what makes the combinations sound.  Returns
+        {checks: {shape_and_streams, fixed_points, delta1~delta2, A, B1, B2, C, H, vk_fixed_points, IC -> True holds / False violated
+        / None not run}, checks_run, checks_bad, ok, ms}.  A wrong key is a result, not an exception.  The check looks at no single
+        point (check_key and check_powers do), and cannot tell whether the circuit is the intended one nor who contributed."""
+        if (pkey is not None) + (sections is not None) + (path is not None) != 1:
+            raise ValueError("check_key_circuit: exactly one of pkey, sections, path")
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        ps, keep_p = _powers_struct(powers)
+        cs, keep_c = _circuit_struct(circuit)
+        vkb, n_inputs = None, 0
+        if vk is not None:
+            if isinstance(vk, dict):
+                n_inputs = len(vk["IC"]) - 1
+                vk = vk_to_bytes(vk, n_inputs)
+            else:
+                vk = bytes(vk)
+                n_inputs = (len(vk) - 448) // 64 - 1
+            if n_inputs < 0:
+                raise ValueError("vk: no IC point")
+            vkb = _ro(vk)[0]
+        sb = _ro(bytes(seed))[0] if seed is not None else None
+        v = _CircuitVerdict()
+        tail = (C.byref(ps), C.byref(cs), vkb, len(vk) if vk is not None else 0, n_inputs, sb, C.byref(v))
+        if path is not None:
+            rc = self.lib.c.wsnark_pkey_circuit_check_file(os.fsencode(path), *tail)
+        elif sections is not None:
+            ks, keep = _key_sections(sections)
+            rc = self.lib.c.wsnark_pkey_circuit_check_sections(C.byref(ks), *tail)
+        else:
+            b, n = _ro(pkey)
+            rc = self.lib.c.wsnark_pkey_circuit_check(b, n, *tail)
+        self.lib.check(rc)
+        return _circuit_verdict_dict(v)
+
+    def circuit_row_sums(self, circuit, weights):
+        """The building block of check_key_circuit (wsnark_circuit_row_sums): for weights w_j per signal (nVars x 32 bytes plain LE,
+        any 256-bit value) the sums sum_j coef_ij w_j of every row i of A, B and C, split into the public columns (j <= nPublic) and
+        the private ones.  Returns (public, private): 3 x domain x 32 bytes each, order A, B, C, Montgomery and canonical."""
+        cs, keep = _circuit_struct(circuit)
+        w, nw = _ro(weights)
+        if nw != 32 * circuit["n_vars"]:
+            raise ValueError("weights: 32 bytes per signal")
+        size = 3 * 32 * circuit["domain"]
+        pub, prv = (C.c_uint8 * max(size, 1))(), (C.c_uint8 * max(size, 1))()
+        self.lib.check(self.lib.c.wsnark_circuit_row_sums(C.byref(cs), w, pub, prv))
+        return bytes(pub)[:size], bytes(prv)[:size]
 
     def key_file_info(self, path):
         """Header of a key file (no GPU work): {n_vars, n_public, domain, file_bytes, format: 'proving_key.bin' | 'WSNARK64'}."""

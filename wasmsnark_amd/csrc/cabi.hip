@@ -15,6 +15,7 @@ static_assert(sizeof(XYZZ<Fq>) == 128 && sizeof(XYZZ<Fq2>) == 256, "xyzz layouts
 static_assert(sizeof(wsnark_pkey_delta_report_t) == 104 && sizeof(wsnark_pkey_delta_verdict_t) == 40, "the bindings read these by offset");
 static_assert(sizeof(wsnark_pkey_setup_report_t) == 192, "the bindings read this by offset");
 static_assert(sizeof(wsnark_powers_report_t) == 192, "the bindings read this by offset");
+static_assert(sizeof(wsnark_pkey_circuit_verdict_t) == 56, "the bindings read this by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
 // addon runs on the libuv pool): select the context's device first.
@@ -425,6 +426,35 @@ int wsnark_pkey_delta_verify_file(const char* old_path, const char* new_path, co
     int rc = o.open(old_path);
     if (!rc) rc = n.open(new_path);
     return rc ? rc : pkey_delta_verify_sections(o.S, n.S, (const uint8_t*)seed32, out);
+}
+// ---- a key against its circuit and its powers of tau (pkeycircuit.hip) ----
+int wsnark_pkey_circuit_check(const void* pkey, size_t len, const wsnark_powers_t* powers, const wsnark_circuit_t* circuit, const void* vk,
+                              size_t vk_len, uint64_t n_inputs, const void* seed32, wsnark_pkey_circuit_verdict_t* out) {
+    REQUIRE_CTX();
+    if (!out) return WSNARK_ERR_ARG;
+    KeyInput in;
+    int rc = in.open(pkey, len);
+    return rc ? rc : pkey_circuit_check_sections(in.S, powers, circuit, (const uint8_t*)vk, vk_len, n_inputs, (const uint8_t*)seed32, out);
+}
+int wsnark_pkey_circuit_check_sections(const wsnark_key_sections_t* key, const wsnark_powers_t* powers, const wsnark_circuit_t* circuit,
+                                       const void* vk, size_t vk_len, uint64_t n_inputs, const void* seed32,
+                                       wsnark_pkey_circuit_verdict_t* out) {
+    REQUIRE_CTX();
+    KeyInput in;
+    if (!out || in.open(key)) return WSNARK_ERR_ARG;
+    return pkey_circuit_check_sections(in.S, powers, circuit, (const uint8_t*)vk, vk_len, n_inputs, (const uint8_t*)seed32, out);
+}
+int wsnark_pkey_circuit_check_file(const char* path, const wsnark_powers_t* powers, const wsnark_circuit_t* circuit, const void* vk,
+                                   size_t vk_len, uint64_t n_inputs, const void* seed32, wsnark_pkey_circuit_verdict_t* out) {
+    REQUIRE_CTX();
+    if (!path || !out) return WSNARK_ERR_ARG;
+    KeyInput in;
+    int rc = in.open(path);
+    return rc ? rc : pkey_circuit_check_sections(in.S, powers, circuit, (const uint8_t*)vk, vk_len, n_inputs, (const uint8_t*)seed32, out);
+}
+int wsnark_circuit_row_sums(const wsnark_circuit_t* circuit, const void* weights, void* out_public, void* out_private) {
+    REQUIRE_CTX();
+    return circuit_row_sums(circuit, weights, out_public, out_private);
 }
 int wsnark_pkey_shard_info(const wsnark_pkey_t* h, uint32_t* rank, uint32_t* world, uint64_t* first_signal, uint64_t* n_signals,
                            uint64_t* n_hexps, uint32_t* h_interleave_log) {

@@ -171,7 +171,7 @@ int draw_seed(const uint8_t* caller32, uint8_t out[32]);
 typedef std::chrono::steady_clock Clock;
 inline double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
 
-// points per chunk of a streamed section: the switch `name` (PKCHECK_CHUNK, PKDELTA_CHUNK; default 2^18) within [64, 2^22]
+// points per chunk of a streamed section: the switch `name` (PKCHECK_CHUNK, PKDELTA_CHUNK, PKCIRCUIT_CHUNK; default 2^18) within [64, 2^22]
 inline uint64_t key_chunk(const char* name) {
     return std::min<uint64_t>(std::max<uint64_t>((uint64_t)tuning_get(name, 1 << 18), 64), (uint64_t)1 << 22);
 }
@@ -241,6 +241,10 @@ int pkey_contribute_bytes(const KeySections& S, const uint8_t* pkey, size_t len,
 int pkey_contribute_file(const KeySections& S, const KeyFile& F, const char* in_path, const char* out_path, const uint8_t* d32,
                          wsnark_pkey_delta_report_t* rep);
 int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const uint8_t* seed32, wsnark_pkey_delta_verdict_t* out);
+// a key against its circuit and its powers of tau (pkeycircuit.hip); vk: wsnark_groth16_verify's layout or nullptr
+int pkey_circuit_check_sections(const KeySections& S, const wsnark_powers_t* P, const wsnark_circuit_t* K, const uint8_t* vk, size_t vk_len,
+                                uint64_t n_inputs, const uint8_t* seed32, wsnark_pkey_circuit_verdict_t* out);
+int circuit_row_sums(const wsnark_circuit_t* K, const void* weights, void* out_public, void* out_private);
 // the audit's per-point kernels on device-resident points in reference format (pkeycheck.hip): counts into d_acc with the global index
 // base + i; the G2 one with the order-r subgroup test (PKCHECK_SUBGROUP picks its form), d_K: the pairing constants on the device
 int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s);

@@ -108,6 +108,17 @@ function deltaVerdict(ab) {
     DELTA_CHECKS.forEach((name, k) => { out.checks[name] = (run >> k) & 1 ? !((bad >> k) & 1) : null; });
     return out;
 }
+/* wsnark_pkey_circuit_verdict_t (56 bytes) -> the object of checkKeyCircuit() */
+const CIRCUIT_CHECKS = ["shape_and_streams", "fixed_points", "delta1~delta2", "A", "B1", "B2", "C", "H", "vk_fixed_points", "IC"];
+function circuitVerdict(ab) {
+    const v = new DataView(ab);
+    const run = v.getUint32(0, true), bad = v.getUint32(4, true);
+    const out = { checks: {}, checksRun: run, checksBad: bad, ok: v.getUint32(8, true) === 1,
+                  ms: { matrices: v.getFloat64(16, true), keySums: v.getFloat64(24, true), powersSums: v.getFloat64(32, true),
+                        pairings: v.getFloat64(40, true), total: v.getFloat64(48, true) } };
+    CIRCUIT_CHECKS.forEach((name, k) => { out.checks[name] = (run >> k) & 1 ? !((bad >> k) & 1) : null; });
+    return out;
+}
 /* wsnark_pkey_setup_report_t (192 bytes) -> the report object of newKey() */
 const POWERS_ARRAYS = ["tauG1", "tauG2", "alphaTauG1", "betaTauG1"];
 function setupReport(ab) {
@@ -342,6 +353,29 @@ class Bn128 {
             if (!report.ok) throw Object.assign(new Error("wsnark: proving key failed its audit: " + firstFinding(report)), { report });
         }
         return deltaVerdict(await addon.deltaVerify(oldKey, newKey, opts && opts.seed ? opts.seed : null));
+    }
+    /* No counterpart in the reference (snarkjs: `zkey verify <r1cs> <ptau> <zkey>`): is this the key of THIS circuit on THIS transcript
+     * (include/wsnark.h: wsnark_pkey_circuit_check)?  Works on the first key and after any number of contributions, without toxic waste
+     * and without a group transform.  powers, circuit: the objects of newKey(); key: proving_key.bin bytes, or the path of a key file;
+     * opts.vk: the verification_key.json object -- with it the IC points and the key's fixed points are checked too; opts.seed: 32 bytes
+     * for the random combinations, by default from the OS (a seed the key's author could know proves nothing).  Resolves to {checks:
+     * {shape_and_streams, fixed_points, "delta1~delta2", A, B1, B2, C, H, vk_fixed_points, IC: true holds / false violated / null not
+     * run}, checksRun, checksBad, ok, ms}; a wrong key is a result, not a rejection.  The check looks at no single point (checkKey and
+     * checkPowers do), and cannot tell whether the circuit is the intended one nor who contributed. */
+    async checkKeyCircuit(powers, circuit, key, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: checkKeyCircuit runs on a single GPU (build a Bn128 without {devices})");
+        if (typeof key !== "string") asBytes(key);
+        const bufs = [powers.tauG1, powers.tauG2, powers.alphaTauG1, powers.betaTauG1, powers.betaG2, circuit.polsA, circuit.polsB, circuit.polsC];
+        bufs.forEach(asBytes);
+        let vk = null;
+        if (opts && opts.vk) {
+            const k = opts.vk;
+            if (!k.IC || k.IC.length < 1) throw new Error("verification key has no IC point");
+            const g1 = (p) => [p[0], p[1]], g2 = (p) => [p[0][0], p[0][1], p[1][0], p[1][1]];
+            vk = le32cat([].concat(g1(k.vk_alfa_1), g2(k.vk_beta_2), g2(k.vk_gamma_2), g2(k.vk_delta_2), ...k.IC.map(g1)));
+        }
+        return circuitVerdict(await addon.checkKeyCircuit(key, circuit.nVars, circuit.nPublic, circuit.domain, bufs, vk, opts && opts.seed ? opts.seed : null));
     }
     /* A key FILE -- the reference's proving_key.bin or the WSNARK64 container for keys beyond its 4 GiB (js/formats.js:
      * writeKeyContainer; 2^24 constraints = 7.8 GB, more than one Buffer holds).  The library maps the file and reads only what it makes

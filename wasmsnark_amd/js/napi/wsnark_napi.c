@@ -81,6 +81,9 @@ static struct {
     int (*g2_mul)(const void*, const void*, uint64_t, void*);
     int (*powers_contribute)(const void*, const void*, const void*, const void*, void*, void*, void*, void*, void*, void*);
     int (*powers_check)(const void*, uint32_t, const void*, void*);
+    /* a key against its circuit and its powers of tau (include/wsnark.h: wsnark_pkey_circuit_check*) */
+    int (*pkey_circuit_check)(const void*, size_t, const void*, const void*, const void*, size_t, uint64_t, const void*, void*);
+    int (*pkey_circuit_check_file)(const char*, const void*, const void*, const void*, size_t, uint64_t, const void*, void*);
     char dir[4096];
 } L;
 
@@ -126,6 +129,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(pkey_delta_verify, "wsnark_pkey_delta_verify") SYM(pkey_delta_verify_file, "wsnark_pkey_delta_verify_file")
     SYM(g1_ntt, "wsnark_g1_ntt") SYM(g2_ntt, "wsnark_g2_ntt") SYM(pkey_setup_pkey, "wsnark_pkey_setup_pkey") SYM(pkey_setup_size, "wsnark_pkey_setup_size")
     SYM(g1_mul, "wsnark_g1_mul_batch") SYM(g2_mul, "wsnark_g2_mul_batch") SYM(powers_contribute, "wsnark_powers_contribute") SYM(powers_check, "wsnark_powers_check")
+    SYM(pkey_circuit_check, "wsnark_pkey_circuit_check") SYM(pkey_circuit_check_file, "wsnark_pkey_circuit_check_file")
 #undef SYM
     return 0;
 }
@@ -154,7 +158,7 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
        OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
-       OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK };
+       OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -280,6 +284,7 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
 #define PKEY_DELTA_VERDICT_BYTES 40      /* sizeof(wsnark_pkey_delta_verdict_t) */
 #define PKEY_SETUP_REPORT_BYTES 192      /* sizeof(wsnark_pkey_setup_report_t) */
 #define POWERS_REPORT_BYTES 192          /* sizeof(wsnark_powers_report_t) */
+#define PKEY_CIRCUIT_VERDICT_BYTES 56    /* sizeof(wsnark_pkey_circuit_verdict_t) */
 /* wsnark_powers_t and wsnark_circuit_t (include/wsnark.h) */
 typedef struct {
     uint32_t domain;
@@ -355,6 +360,15 @@ static void job_execute(napi_env env, void* data) {
         circuit_t K;
         job_structs(j, &P, &K);
         j->rc = L.powers_check(&P, j->u0, j->r32, j->out);
+        break;
+    }
+    case OP_CHECK_KEY_CIRCUIT: {      /* b: the verification key's bytes (alfa1 | beta2 | gamma2 | delta2 | IC) or NULL */
+        powers_t P;
+        circuit_t K;
+        job_structs(j, &P, &K);
+        const uint64_t n_inputs = j->b ? (j->nb - 448) / 64 - 1 : 0;
+        j->rc = j->path ? L.pkey_circuit_check_file(j->path, &P, &K, j->b, j->nb, n_inputs, j->r32, j->out)
+                        : L.pkey_circuit_check(j->a, j->na, &P, &K, j->b, j->nb, n_inputs, j->r32, j->out);
         break;
     }
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
@@ -755,6 +769,35 @@ static napi_value js_new_key(napi_env env, napi_callback_info info) {
     return start_job(env, j, "wsnark_pkey_setup");
 }
 
+/* checkKeyCircuit(pkeyBytes | path, nVars, nPublic, domain, [tauG1, tauG2, alphaTauG1, betaTauG1, betaG2, polsA, polsB, polsC], vkBytes | null,
+ * seed32 | null) -> Promise<ArrayBuffer 56>: the wsnark_pkey_circuit_verdict_t (wsnark_pkey_circuit_check / _check_file; index.js turns
+ * it into an object).  vkBytes: wsnark_groth16_verify's layout with all the key's IC points. */
+static napi_value js_check_key_circuit(napi_env env, napi_callback_info info) {
+    size_t argc = 7; napi_value argv[7], el;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CHECK_KEY_CIRCUIT;
+    bool is = false;
+    if (argc < 5 || (!(j->path = get_path(env, argv[0])) && !get_bytes(env, argv[0], &j->a, &j->na)) ||
+        napi_get_value_uint32(env, argv[1], &j->u0) != napi_ok || napi_get_value_uint32(env, argv[2], &j->u1) != napi_ok ||
+        napi_get_value_uint32(env, argv[3], &j->u2) != napi_ok || napi_is_array(env, argv[4], &is) != napi_ok || !is)
+        FAIL(env, j, "expected (proving_key.bin bytes | key file path, nVars, nPublic, domain, [eight byte buffers][, vkBytes, seed32])");
+    for (uint32_t k = 0; k < 8; k++)
+        if (napi_get_element(env, argv[4], k, &el) != napi_ok || !get_bytes(env, el, &j->in[k], &j->nin[k])) FAIL(env, j, "checkKeyCircuit: eight byte buffers");
+    if (j->nin[4] < 128) FAIL(env, j, "betaG2 must be 128 bytes");
+    if (argc > 5 && get_bytes(env, argv[5], &j->b, &j->nb) && (j->nb < 448 + 64 || (j->nb - 448) % 64)) FAIL(env, j, "vkBytes: alfa1 | beta2 | gamma2 | delta2 | IC points");
+    size_t ns = 0;
+    if (argc > 6 && get_bytes(env, argv[6], &j->r32, &ns) && ns != 32) FAIL(env, j, "the seed must be 32 bytes");
+    j->nout = PKEY_CIRCUIT_VERDICT_BYTES;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    if (!j->path) keep(env, j, argv[0]);
+    keep(env, j, argv[4]);      /* the array keeps its eight buffers alive */
+    if (j->b) keep(env, j, argv[5]);
+    if (j->r32) keep(env, j, argv[6]);
+    return start_job(env, j, "wsnark_pkey_circuit_check");
+}
+
 /* mulPoints(group 1 | 2, points, scalars) -> Promise<ArrayBuffer>: scalars[i] * points[i] (wsnark_g{1,2}_mul_batch), out of place */
 static napi_value js_mul_points(napi_env env, napi_callback_info info) {
     size_t argc = 3; napi_value argv[3];
@@ -1147,6 +1190,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"mulPoints", NULL, js_mul_points, NULL, NULL, NULL, napi_default, NULL},
         {"contributePowers", NULL, js_contribute_powers, NULL, NULL, NULL, napi_default, NULL},
         {"checkPowers", NULL, js_check_powers, NULL, NULL, NULL, napi_default, NULL},
+        {"checkKeyCircuit", NULL, js_check_key_circuit, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},
