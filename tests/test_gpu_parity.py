@@ -78,7 +78,7 @@ def test_proofs_golden(bn, name):
 
 
 # ------------------------------------------------------------------ vs the oracle
-@pytest.mark.parametrize("bits", [1, 2, 3, 4, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21])
+@pytest.mark.parametrize("bits", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21])
 def test_ntt_vs_oracle(bn, orc, bits):
     """Random data at every digit split of the transform's plan: 12, 13 and 15 are the two-pass splits (6,6), (7,6), (8,7); 19, 20 and 21
     the three-pass splits (7,6,6), (7,7,6), (7,7,7).  At 2^20 and 2^21 the oracle's own transform takes 2-4 s a piece on the host, so
@@ -771,16 +771,23 @@ def test_degenerate_key_points_against_the_oracle_prover_on_gpu(bn, orc, tune, m
     k.free()
 
 
+def _device_random_fr(n, seed, top_limb_mask=0x1FFFFFFF):
+    """n seeded random values below 2^253 < r as n*32 bytes, drawn on the device (eight 32-bit limbs each; the top one masked)."""
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.randint(-(1 << 31), (1 << 31) - 1, (n, 8), dtype=torch.int32, device="cuda", generator=g)
+    x[:, 7] &= top_limb_mask
+    return x.view(torch.uint8).view(-1)
+
+
 def test_ntt_2p25_four_pass_roundtrip_and_linearity(bn):
-    """2^25 needs four digit passes (middle-digit reversal): round trip, and F(x + y) == F(x) + F(y)
-    checked through the evaluation at one point: sum_k F(x)[k] == n * x[0] (DFT of the constant-one vector)."""
+    """2^25 needs four digit passes (middle-digit reversal): the round trip ifft(fft(x)) == x on random data, and two forward coset
+    transforms in a row do not give x back.  (No linearity check, whatever the name says; the values of the four-pass sizes are
+    checked in tests/test_gpu_ntt_plans.py and by test_four_step_ntt_building_blocks_on_gpu.)"""
     import torch
     sync = torch.cuda.synchronize
     n = 1 << 25
-    g = torch.Generator(device="cpu").manual_seed(25)
-    x = torch.randint(0, 256, (n * 32,), dtype=torch.uint8, generator=g)
-    x[31::32] &= 0x0F
-    d = x.cuda()
+    d = _device_random_fr(n, 25, 0x0FFFFFFF)
     y = d.clone()
     sync()
     bn.fft_dev(y.data_ptr(), n, 1)
@@ -795,22 +802,32 @@ def test_ntt_2p25_four_pass_roundtrip_and_linearity(bn):
     assert not torch.equal(y, d)
 
 
-@pytest.mark.parametrize("bits", [6, 11, 16, 20, 22])
+@pytest.mark.parametrize("bits", [6, 11, 16, 20, 22, 23, 24, 25, 26, 27])
 def test_four_step_ntt_building_blocks_on_gpu(bn, orc, bits):
     """wsnark_fr_ntt_batch_dev + wsnark_fr_dist_scale_dev through dist_ntt with a world of one (column step, twiddle,
     transpose, row step on ONE GPU): bit-identical to the single-kernel-chain transform wsnark_fr_ntt_dev for odd 0/1,
     forward and inverse (and to the oracle where it is fast).  The N > 1 exchange itself is in tests/test_gpu_multi.py
-    (nccl) and tests/test_dist_ntt_gloo.py (CPU)."""
+    (nccl) and tests/test_dist_ntt_gloo.py (CPU).
+    2^23 - 2^27: the four-step route's column and row transforms are two-pass sizes (2^11 - 2^14) that the oracle pins, so this is a
+    whole-vector check, on dense data, of the three-pass plans (8,8,7), (8,8,8) and of the three four-pass plans (7,6,6,6), (7,7,6,6),
+    (7,7,7,6).  Data drawn on the device; 2^27 keeps forward odd 0 and inverse odd 1 (every variant leaves a 4 GB table resident)."""
     import torch
     from wasmsnark_amd import dist as wd
     n = 1 << bits
-    g = torch.Generator(device="cpu").manual_seed(bits)
-    x = torch.randint(0, 256, (n * 32,), dtype=torch.uint8, generator=g)
-    x[31::32] &= 0x1F
-    d = x.cuda()
+    if bits >= 23:
+        x = None
+        d = _device_random_fr(n, bits)
+    else:
+        g = torch.Generator(device="cpu").manual_seed(bits)
+        x = torch.randint(0, 256, (n * 32,), dtype=torch.uint8, generator=g)
+        x[31::32] &= 0x1F
+        d = x.cuda()
     l1, l2 = wd.ntt_layout_split(bits, 1)
+    ran = 0
     for odd in (0, 1):
         for inverse in (False, True):
+            if bits >= 27 and (odd, inverse) not in ((0, False), (1, True)):
+                continue
             ref = d.clone()
             torch.cuda.synchronize()
             bn.fft_dev(ref.data_ptr(), n, odd, inverse=inverse)
@@ -820,6 +837,12 @@ def test_four_step_ntt_building_blocks_on_gpu(bn, orc, bits):
             assert torch.equal(y, ref), (bits, odd, inverse)
             if bits <= 16:
                 assert ref.cpu().numpy().tobytes() == orc.fft(x.numpy().tobytes(), n, odd, inverse=inverse)
+            ran += 1
+            del ref, loc, y
+    assert ran == (2 if bits >= 27 else 4)
+    if bits >= 23:
+        del d
+        torch.cuda.empty_cache()
 
 
 def test_native_verifier_accepts_gpu_proofs(bn):

@@ -103,7 +103,7 @@ struct Context {
     std::mutex lane_mu;                         // waiting for a lane: released lanes are announced on lane_cv
     std::condition_variable lane_cv;
     std::mutex mu;                              // NTT plan cache
-    std::map<int, std::shared_ptr<NttPlan>> ntt_plans;   // by log2(n)
+    std::map<int, std::shared_ptr<NttPlan>> ntt_plans;   // by log2(n) * 8 + digit passes
     KernelTimer timer;
     // host-pointer boundary: pinned staging ring for uploads
     void* pin_ring = nullptr;

@@ -459,9 +459,19 @@ static int upload(DevBuf& b, const std::vector<Fe>& v, hipStream_t s) {
     return WS_OK;
 }
 
-static int build_plan(int bits, NttPlan& P, hipStream_t s) {
+// Digit passes of a length-2^bits transform.  WSNARK_NTT_PASSES = f (tests: the large sizes' pass counts on small inputs) replaces
+// the count where every digit stays a size the pass kernel runs anyway, 2 <= bits / f and ceil(bits / f) <= 10; results never
+// depend on it.
+static int default_passes(int bits) { return bits <= LOG_LMAX ? 1 : (bits <= 16 ? 2 : (bits <= 24 ? 3 : 4)); }
+static int plan_passes(int bits) {
+    const long f = tuning_get("NTT_PASSES", 0);
+    if (f >= 1 && f <= 4 && 2 * f <= bits && bits <= LOG_LMAX * f) return (int)f;
+    return default_passes(bits);
+}
+
+static int build_plan(int bits, int np, NttPlan& P, hipStream_t s) {
     P.bits = bits;
-    P.np = bits <= LOG_LMAX ? 1 : (bits <= 16 ? 2 : (bits <= 24 ? 3 : 4));
+    P.np = np;
     // (2^20 in TWO passes of 2^10 was measured in round 5: 0.164 ms per transform against 0.157 in three, whole proofs 9.98 against
     //  9.70 ms -- profiles/r05_schedule_experiments.txt: ten butterfly stages per tile cost a pass more LDS round trips than they save)
     int basek = bits / P.np, rem = bits % P.np;
@@ -515,14 +525,17 @@ static int build_plan(int bits, NttPlan& P, hipStream_t s) {
     return WS_OK;
 }
 
-static int get_plan(Context* C, int bits, std::shared_ptr<NttPlan>& P, hipStream_t s) {
+// One plan per (size, pass count): the per-pass tables of a plan belong to its digits.  The table accessors below ask for the
+// default count whatever the switch says, so the pointers they hand out stay those of one plan.
+static int get_plan(Context* C, int bits, int np, std::shared_ptr<NttPlan>& P, hipStream_t s) {
     std::lock_guard<std::mutex> lk(C->mu);
-    auto it = C->ntt_plans.find(bits);
+    const int key = bits * 8 + np;
+    auto it = C->ntt_plans.find(key);
     if (it == C->ntt_plans.end()) {
         P = std::make_shared<NttPlan>();
-        int rc = build_plan(bits, *P, s);
+        int rc = build_plan(bits, np, *P, s);
         if (rc) return rc;
-        C->ntt_plans[bits] = P;
+        C->ntt_plans[key] = P;
     } else {
         P = it->second;
     }
@@ -535,7 +548,7 @@ int ntt_coset_tables(int bits, const Fe** lo, const Fe** hi, int* hc, Fe* n_inv,
     if (!C) return WS_ERR_NOINIT;
     if (bits < 1 || bits >= 28) return WS_ERR_SIZE;
     std::shared_ptr<NttPlan> P;
-    int rc = get_plan(C, bits, P, s);
+    int rc = get_plan(C, bits, default_passes(bits), P, s);
     if (rc) return rc;
     *lo = P->cs_lo_ref.as<Fe>(); *hi = P->cs_hi_ref.as<Fe>(); *hc = P->hc; *n_inv = P->n_inv;
     return WS_OK;
@@ -547,7 +560,7 @@ int ntt_coset_tables_kernel_format(int bits, const Fe** lo, const Fe** hi, uint3
     if (!C) return WS_ERR_NOINIT;
     if (bits < 1 || bits >= 28) return WS_ERR_SIZE;
     std::shared_ptr<NttPlan> P;
-    int rc = get_plan(C, bits, P, s);
+    int rc = get_plan(C, bits, default_passes(bits), P, s);
     if (rc) return rc;
     *lo = P->cs_lo.as<Fe>(); *hi = P->cs_hi.as<Fe>(); *hc = (uint32_t)P->hc;
     return WS_OK;
@@ -559,7 +572,7 @@ int ntt_twiddle_tables(int bits, int inverse, const Fe** lo, const Fe** hi, int*
     if (!C) return WS_ERR_NOINIT;
     if (bits < 1 || bits > 28) return WS_ERR_SIZE;
     std::shared_ptr<NttPlan> P;
-    int rc = get_plan(C, bits, P, s);
+    int rc = get_plan(C, bits, default_passes(bits), P, s);
     if (rc) return rc;
     if (internal) {
         if (!P->field29) { set_last_error("ntt: the internal twiddle tables exist on the radix-2^29 field only"); return WS_ERR_ARG; }
@@ -598,7 +611,7 @@ int ntt_run(Lane& L, const Fe* d_src, const Fe* d_in2, Fe* d_data, const Fe* com
     ScratchGuard scratch_turn(L.ntt_chain, s);   // the ping-pong buffer is shared by every transform on this lane
     std::shared_ptr<NttPlan> P;
     {
-        int rc = get_plan(C, bits, P, s);
+        int rc = get_plan(C, bits, plan_passes(bits), P, s);
         if (rc) return rc;
         if (P->np > 1) WS_HIP_CHECK(L.ntt_scratch.reserve(n * count * sizeof(Fe)));
     }
