@@ -754,7 +754,11 @@ int wsnark_selftest_field(int which, int impl, int op, const void* a, const void
  *   (q must be affine: z == 1, or infinity), 5 = p - q as a mixed addition with the negate flag,
  *   6 = p + q + q and 7 = p + q - q as two mixed additions of the ACCUMULATION LOOP's lazy form (x kept "wide" between
  *   them, field29.h) followed by its narrowing, 8 = timesScalar (src/build_timesscalar.js:20-80): q's bytes are NOT a point
- *   but a little-endian scalar in bytes [0, 64) and its length -- 32 or 64 -- in byte 64 (impl 0-3). */
+ *   but a little-endian scalar in bytes [0, 64) and its length -- 32 or 64 -- in byte 64 (impl 0-3),
+ *   10 and 11 (9 is not an operation) = the reduction tail's straight-path addition (curve.h / curve_pair.h: add_fast), which refuses
+ *   what is not the sum of two finite, distinct, non-opposite points: 10 = the accumulator after the call (p + q where it accepts, p
+ *   where it refuses), 11 = q where it accepts, infinity where it refuses.
+ *   impl 5 (g = 1) and 6 (g = 2): the lane-split tail curves (one point on two / four lanes), ops 0, 1, 3, 10, 11. */
 int wsnark_selftest_curve(int g, int impl, int op, const void* p, const void* q, void* out, uint64_t n);
 /* The radix-2^29 field (csrc/field29.h) on RAW limbs, one lane per case: the operand bounds its contracts allow cannot be reached
  * through the packed 32-byte form (8p, 10p and 16p do not fit it, a carry-free sum's limbs are not tight, and to_internal turns every

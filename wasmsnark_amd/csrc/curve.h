@@ -221,6 +221,30 @@ struct Curve {
         return Pt{X3, Y3, F::mul(F::mul(a.zz, b.zz), PP), F::mul(F::mul(a.zzz, b.zzz), PPP)};
     }
 
+    // The reduction tail's COMMON case as one straight path (round 7; what madd_fast is to the accumulation loop): acc += b for two
+    // finite points that are neither equal nor opposite, the formulas of add() above.  Returns false WITHOUT touching acc when an
+    // operand is infinity or when P = U2 - U1 may vanish (the cheap necessary test: the pair may be one of the reference's corner
+    // cases, build_curve_jacobian_a0.js:322-356); the caller then runs the pair through add().  msm_chunks / msm_chunks2 (msm.hip) run
+    // their chains on it and fall to a loop over add() at the first refusal: with add()'s early returns inlined in those loops every
+    // addition carries two nine-limb zero tests, the doubling branch and the register merges of five definitions of the sum.
+    WS_HD static bool add_fast(Pt& acc, const Pt& b) {
+        if (is_inf(acc) || is_inf(b)) return false;
+        El U1 = F::mul(acc.x, b.zz);
+        El U2 = F::mul(b.x, acc.zz);
+        El P = F::sub_weak(U2, U1);
+        if (F::maybe_zero_weak(P)) return false;
+        El S1 = F::mul(acc.y, b.zzz);
+        El S2 = F::mul(b.y, acc.zzz);
+        El R = F::sub_weak(S2, S1);
+        El PP = F::sqr(P);
+        El PPP = F::mul(P, PP);
+        El Q = F::mul(U1, PP);
+        El X3 = F::sub(F::sub(F::sqr(R), PPP), F::dbl(Q));
+        El Y3 = F::mulsub2(R, F::sub_weak(Q, X3), S1, PPP);
+        acc = Pt{X3, Y3, F::mul(F::mul(acc.zz, b.zz), PP), F::mul(F::mul(acc.zzz, b.zzz), PPP)};
+        return true;
+    }
+
     // k * p for a small unsigned k (MSB-first double-and-add)
     WS_HD static Pt mul_small(const Pt& p, uint32_t k) {
         Pt r = infinity();

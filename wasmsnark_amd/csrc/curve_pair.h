@@ -98,6 +98,30 @@ struct CurvePairG1 {
         const El y3 = B::sub(t7, t6);                                    // hi: Y3
         return Pt{pick(m, x3, y3), pick(m, t7, t5)};
     }
+    // The same seven steps as ONE straight path (curve.h: add_fast): p += q for finite points that are neither equal nor opposite.
+    // Returns false without touching p when an operand is infinity or P may vanish -- the lo lane's cheap test, exchanged like every
+    // predicate here, so the pair (the quad) decides as one.
+    WS_HD static bool add_fast(Pt& p, const Pt& q) {
+        if (is_inf(p) || is_inf(q)) return false;
+        const uint32_t m = hi() ? 0xFFFFFFFFu : 0u;
+        const El t1 = B::mul(p.a, q.b);                                  // U1 | S1
+        const El t2 = B::mul(q.a, p.b);                                  // U2 | S2
+        const El d = B::sub_weak(t2, t1);                                // P  | R
+        if (from_lo(B::maybe_zero_weak(d))) return false;
+        const El sq = B::sqr(d);                                         // PP | RR
+        const El t4 = B::mul(pick(m, d, p.b), pick(m, sq, q.b));         // PPP | ZZZ1 ZZZ2
+        const El o4 = swap(t4);
+        const El t5 = B::mul(pick(m, t1, t4), pick(m, sq, o4));          // Q | ZZZ3
+        const El osq = swap(sq);
+        const El x3 = B::sub(B::sub(osq, t4), B::dbl(t5));               // lo: X3
+        const El w = B::sub(t5, x3);                                     // lo: Q - X3
+        const El t6 = B::mul(pick(m, p.b, t1), pick(m, q.b, o4));        // ZZ1 ZZ2 | S1 PPP
+        const El ow = swap(w);
+        const El t7 = B::mul(pick(m, t6, d), pick(m, sq, ow));           // ZZ3 | R (Q - X3)
+        const El y3 = B::sub(t7, t6);                                    // hi: Y3
+        p = Pt{pick(m, x3, y3), pick(m, t7, t5)};
+        return true;
+    }
 };
 
 typedef CurvePairG1<Fq29I> G1P29;

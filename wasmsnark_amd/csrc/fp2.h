@@ -190,6 +190,7 @@ struct Fp2PairT {
     WS_HD static bool is_zero(const El& a) { return both(B::is_zero(a)); }
     WS_HD static bool is_zero_weak(const El& a) { return both(B::is_zero_weak(a)); }
     WS_HD static bool is_zero_wide(const El& a) { return is_zero_weak(a); }
+    WS_HD static bool maybe_zero_weak(const El& a) { return both(B::maybe_zero_weak(a)); }      // (necessary for zero: BOTH components may be)
     WS_HD static bool eq(const El& a, const El& b) { return is_zero(B::sub(a, b)); }
     WS_HD static El add(const El& a, const El& b) { return B::add(a, b); }
     WS_HD static El dbl(const El& a) { return B::dbl(a); }

@@ -269,6 +269,12 @@ int msm_g1_launch(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot,
 int msm_g2_launch(Lane& L, const Affine<Fq2>* d_points, bool prepared, int* slot, hipStream_t s);
 // plan_ids (optional): the plan each set is accumulated against (variants of one plan: same geometry)
 int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, bool prepared, int* slots, hipStream_t s, const int* plan_ids = nullptr);
+// Two sums of which only the TOTAL is wanted (the prover's C and H) under one reduction tail: each is accumulated into its buckets
+// by msm_g1_launch_acc_only (no tail), then msm_g1_launch_tail_merged reduces the bucket-wise sum of the two on `s`, which the caller
+// has ordered behind both accumulations.  The total is collected from slot_a; slot_b is released with it and never finished.  Plans
+// of different tail geometries get one tail each (*merged = false: both slots are finished as usual).
+int msm_g1_launch_acc_only(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot, hipStream_t s);
+int msm_g1_launch_tail_merged(Lane& L, int slot_a, int slot_b, hipStream_t s, bool* merged);
 // several independent plans (digit/sort/task buffers) can be alive at once; plan and launches use the selected one
 void msm_select_plan(Lane& L, int id);      // id in [0, 4)
 // A second plan over the SAME scalars that leaves out the pairs with mask[i] == 0, derived from plan `src_id`

@@ -776,9 +776,25 @@ struct TailSets {
     const uint32_t* bend[4];     // launch before -- msm_chunks checks the bounds, so no pass over the buckets has to clear them
     St* half[4];                 // msm_tree: the two halves of the unmasked rows (per piece: [A half 0, A half 1, T half 0, T half 1, W half 0, W half 1])
     uint32_t* half_done[4];      // ... and their completion counters (per piece and row; zero between launches)
+    // A SECOND bucket array of the same geometry per set (null: none), with the bounds of ITS plan: msm_chunks reduces the element-wise
+    // sum of the two arrays, so two sums of which only the total is wanted (the prover's C and H, msm_launch_tail_merged) share one tail
+    const St* buckets2[4];
+    const uint32_t* bstart2[4];
+    const uint32_t* bend2[4];
 };
 
-template <class C>
+// Round 7: the chains take the straight-path addition (curve.h: add_fast) as the accumulation loop takes madd_fast.  A lane walks down
+// to its first bucket with entries, which starts both sums; from there a FAST loop runs while add_fast accepts, and the loop over
+// add() -- the round-6 code -- finishes the chunk from the first refusal on (an operand at infinity, a doubling, a cancellation: a
+// proof's buckets never show one, the planted sums of tests/tail_patterns.py show them all).  The sum right after the start, acc + run
+// with nothing added to run in between (an empty bucket), IS a doubling and goes that way.  WS_TAIL_FAST=0: the round-6 loops.
+#ifndef WS_TAIL_FAST
+#define WS_TAIL_FAST 1
+#endif
+// DUAL: the sets carry a second bucket array.  sum_b (b + 1) (B_b + B'_b): the bucket pair is added first -- an addition that does not
+// depend on the running sums -- and the two chains run once, 3 additions per bucket pair instead of the 4 of two tails; a bucket that
+// is empty in one plan contributes the other's alone, one that is empty in both is skipped.
+template <class C, bool DUAL>
 __global__ __launch_bounds__(256) void msm_chunks(TailSets<C> ts, uint32_t nchunks, uint32_t m) {
     typedef PointIO<C> IO;
     const typename IO::Stored* __restrict__ buckets = ts.buckets[blockIdx.y];
@@ -790,8 +806,41 @@ __global__ __launch_bounds__(256) void msm_chunks(TailSets<C> ts, uint32_t nchun
     const typename IO::Stored* B = buckets + (uint64_t)j * m;
     const uint32_t* __restrict__ bs = ts.bstart[blockIdx.y] + (uint64_t)j * m;
     const uint32_t* __restrict__ be = ts.bend[blockIdx.y] + (uint64_t)j * m;
-    for (int i = (int)m - 1; i >= 0; i--) {
-        if (bs[i] != be[i]) run = C::add(run, IO::load(B, (uint64_t)i));      // (uniform over a lane pair: both lanes read the same bounds)
+    const typename IO::Stored* B2 = DUAL ? ts.buckets2[blockIdx.y] + (uint64_t)j * m : nullptr;
+    const uint32_t* __restrict__ bs2 = DUAL ? ts.bstart2[blockIdx.y] + (uint64_t)j * m : nullptr;
+    const uint32_t* __restrict__ be2 = DUAL ? ts.bend2[blockIdx.y] + (uint64_t)j * m : nullptr;
+    int i = (int)m - 1;
+    bool run_due = true;                 // the generic loop's first step: bucket i has not been added to run yet
+#if WS_TAIL_FAST
+    while (i >= 0 && bs[i] == be[i] && !(DUAL && bs2[i] != be2[i])) i--;      // (both sums stay at infinity)
+    bool started = false;
+    if (i >= 0) {
+        const bool has1 = bs[i] != be[i], has2 = DUAL && bs2[i] != be2[i];
+        typename C::Pt x = IO::load(has1 ? B : B2, (uint64_t)i);
+        if (!(has1 && has2) || C::add_fast(x, IO::load(B2, (uint64_t)i))) { run = acc = x; started = true; i--; }      // infinity + B, twice
+    }
+    if (started) {
+        for (; i >= 0; i--) {
+            const bool has1 = bs[i] != be[i], has2 = DUAL && bs2[i] != be2[i];
+            if (has1 || has2) {
+                typename C::Pt x = IO::load(has1 ? B : B2, (uint64_t)i);
+                if (has1 && has2 && !C::add_fast(x, IO::load(B2, (uint64_t)i))) break;
+                if (!C::add_fast(run, x)) break;
+            }
+            if (!C::add_fast(acc, run)) { run_due = false; break; }
+        }
+    }
+#endif
+    for (; i >= 0; i--) {
+        if (run_due) {
+            const bool has1 = bs[i] != be[i], has2 = DUAL && bs2[i] != be2[i];      // (uniform over a lane pair: both lanes read the same bounds)
+            if (has1 || has2) {
+                typename C::Pt x = IO::load(has1 ? B : B2, (uint64_t)i);
+                if (has1 && has2) x = C::add(x, IO::load(B2, (uint64_t)i));
+                run = C::add(run, x);
+            }
+        }
+        run_due = true;
         acc = C::add(acc, run);
     }
     IO::store(chunkS, j, run);
@@ -817,14 +866,29 @@ __global__ __launch_bounds__(256) void msm_chunks2(TailSets<C> ts, uint32_t npai
         k -= npairs;
         const uint64_t base = (uint64_t)k * m2;
         typename C::Pt aa = IO::load(A1, base);
-        for (uint32_t i = 1; i < m2; i++) aa = C::add(aa, IO::load(A1, base + i));
+        uint32_t i = 1;
+#if WS_TAIL_FAST
+        for (; i < m2; i++)
+            if (!C::add_fast(aa, IO::load(A1, base + i))) break;
+#endif
+        for (; i < m2; i++) aa = C::add(aa, IO::load(A1, base + i));
         IO::store(ts.chunkA[blockIdx.y], k, aa);
         return;
     }
     const uint64_t base = (uint64_t)k * m2;
     typename C::Pt run = C::infinity(), acc = C::infinity();
-    for (uint32_t i = m2 - 1; i >= 1; i--) {
-        run = C::add(run, IO::load(S1, base + i));
+    uint32_t i = m2 - 1;
+    bool run_due = true;                 // the generic loop's first step: S_i has not been added to run yet
+#if WS_TAIL_FAST
+    run = acc = IO::load(S1, base + i);              // infinity + S_{m2-1}, twice (m2 >= 2)
+    for (i--; i >= 1; i--) {
+        if (!C::add_fast(run, IO::load(S1, base + i))) break;
+        if (!C::add_fast(acc, run)) { run_due = false; break; }
+    }
+#endif
+    for (; i >= 1; i--) {
+        if (run_due) run = C::add(run, IO::load(S1, base + i));
+        run_due = true;
         acc = C::add(acc, run);                      // -> sum_{i >= 1} i S_i
     }
     run = C::add(run, IO::load(S1, base));
@@ -991,6 +1055,7 @@ struct MsmPending {
     size_t h_bytes = 0;
     hipEvent_t ev = nullptr;
     const void* d_points_used = nullptr;            // the (converted) point array the accumulation reads
+    int partner = -1;             // a launch whose buckets went through THIS launch's tail (msm_g1_launch_tail_merged): busy until this one is finished
     void release() {
         if (h_sums) (void)hipHostFree(h_sums);
         if (ev) (void)hipEventDestroy(ev);
@@ -1544,6 +1609,7 @@ static int msm_launch_acc(Lane& L, int which, const typename H::Aff* d_points_re
     P.which = which;
     P.info = I;
     P.plan_id = M.cur;
+    P.partner = -1;
     if (I.n == 0) { P.active = true; *slot_out = slot; return WS_OK; }   // multiexp with n=0 leaves pr unchanged
     const typename C::AffP* d_points = reinterpret_cast<const typename C::AffP*>(d_points_ref);
     const uint64_t n = I.n;
@@ -1615,8 +1681,10 @@ static bool tail_quad_g2() { return tuning_get("TAIL_QUAD_G2", 1) != 0; }
 template <class C> static bool tail_split() { return sizeof(typename C::AffP) > 64 ? tail_quad_g2() : tail_pair_g1(); }
 // CC: the curve of msm_chunks (throughput-bound: 2 additions per bucket on every lane of the chip -- the one-lane form is the cheaper
 // one there), C: the curve of msm_tree / msm_rows (latency-bound LDS reductions: the lane-paired forms halve every step).  Same buffers.
+// second_slot >= 0 (one launch only): that launch's buckets are added to the first one's bucket by bucket in msm_chunks, and the rows
+// that reach the host -- in the first launch's slot -- are those of the sum of the two (same geometry: the caller has checked)
 template <class C, class CC = C>
-static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t s) {
+static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t s, int second_slot = -1) {
     typedef PointIO<C> IO;
     typedef typename IO::Stored St;
     static_assert(sizeof(typename PointIO<CC>::Stored) == sizeof(St), "the chunk and tree kernels share their buffers");
@@ -1640,6 +1708,13 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
         ts.bend[k] = ws(L).plan[P.plan_id].S.bend.template as<uint32_t>();
         ts.half[k] = P.S.tree_half.template as<St>();
         ts.half_done[k] = P.S.tree_done.template as<uint32_t>();
+        ts.buckets2[k] = nullptr; ts.bstart2[k] = ts.bend2[k] = nullptr;
+        if (second_slot >= 0) {
+            MsmPending& P2 = slots[second_slot];
+            ts.buckets2[k] = P2.S.buckets.template as<St>();
+            ts.bstart2[k] = ws(L).plan[P2.plan_id].S.bstart.template as<uint32_t>();
+            ts.bend2[k] = ws(L).plan[P2.plan_id].S.bend.template as<uint32_t>();
+        }
     }
     const uint32_t J = I.J, logJ = I.logJ, nsum = I.nsum, LPP = IO::LPP, W = I.tW;
     KernelTimer& T = X->timer;
@@ -1649,7 +1724,9 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
         static_assert(sizeof tc == sizeof ts, "same pointers");
         memcpy(&tc, &ts, sizeof tc);
         for (int k = 0; k < 4; k++) { tc.chunkS[k] = const_cast<typename PointIO<CC>::Stored*>(tc.l1S[k]); tc.chunkA[k] = const_cast<typename PointIO<CC>::Stored*>(tc.l1A[k]); }
-        hipLaunchKernelGGL(msm_chunks<CC>, dim3(ceil_div_u64((uint64_t)W * I.J1 * PointIO<CC>::LPP, 256), nslots), dim3(256), 0, s, tc, W * I.J1, I.m1);
+        const dim3 grid(ceil_div_u64((uint64_t)W * I.J1 * PointIO<CC>::LPP, 256), nslots);
+        if (second_slot >= 0) hipLaunchKernelGGL((msm_chunks<CC, true>), grid, dim3(256), 0, s, tc, W * I.J1, I.m1);
+        else hipLaunchKernelGGL((msm_chunks<CC, false>), grid, dim3(256), 0, s, tc, W * I.J1, I.m1);
     }
     T.end(s);
     WS_HIP_CHECK(hipGetLastError());
@@ -1689,6 +1766,8 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
         WS_HIP_CHECK(hipMemcpyAsync(P.h_sums, P.d_sums.p, sums_bytes, hipMemcpyDeviceToHost, s));
         WS_HIP_CHECK(hipEventRecord(P.ev, s));
     }
+    // (the second launch's plan and buckets are read until here: whoever rewrites them waits for this event, wait_plan_users)
+    if (second_slot >= 0) WS_HIP_CHECK(hipEventRecord(slots[second_slot].ev, s));
     return WS_OK;
 }
 
@@ -1740,6 +1819,43 @@ int msm_g1_launch(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot,
     if (!ctx()) return WS_ERR_NOINIT;
     return msm_launch<G1R29, G1>(L, 0, d_points, prepared, slot, s);
 }
+// accumulation and combine only: the buckets wait for a tail (msm_g1_launch_tail_merged)
+int msm_g1_launch_acc_only(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot, hipStream_t s) {
+    if (!ctx()) return WS_ERR_NOINIT;
+    if (!s) s = L.stream;
+    return msm_launch_acc<G1R29, G1>(L, 0, d_points, prepared, slot, s);
+}
+// two launches of msm_g1_launch_acc_only share one reduction tail where that is possible
+static bool msm_tail_mergeable(const MsmPlanInfo& a, const MsmPlanInfo& b) {
+    return a.n && b.n && a.flat && b.flat && a.c == b.c && a.W == b.W && a.Wall == b.Wall && a.w_off == b.w_off && a.w_stride == b.w_stride &&
+           a.NB == b.NB && a.nbuckets == b.nbuckets && a.tNB == b.tNB && a.tP == b.tP && a.tW == b.tW && a.groups == b.groups &&
+           a.m1 == b.m1 && a.m2 == b.m2 && a.m == b.m && a.J1 == b.J1 && a.J == b.J && a.logJ == b.logJ && a.nsum == b.nsum &&
+           a.nrows == b.nrows && a.reduce == b.reduce;
+}
+// ONE reduction tail on `s` over the bucket-wise sum of two launches (both accumulated on queues that `s` is ordered behind).  The
+// sum of the two reaches the host in slot_a (msm_g1_finish); slot_b stays busy until then and is never finished itself.  Launches
+// whose tail geometries differ get a tail each; *merged says which it was.
+int msm_g1_launch_tail_merged(Lane& L, int slot_a, int slot_b, hipStream_t s, bool* merged) {
+    if (!ctx()) return WS_ERR_NOINIT;
+    if (!s) s = L.stream;
+    *merged = false;
+    if (!L.msm || slot_a < 0 || slot_b < 0 || slot_a >= kPendingSlots || slot_b >= kPendingSlots || slot_a == slot_b) return WS_ERR_ARG;
+    MsmPending &A = L.msm->slot[slot_a], &B = L.msm->slot[slot_b];
+    if (!A.active || !B.active || A.which != 0 || B.which != 0) return WS_ERR_ARG;
+    int rc = WS_OK;
+    if (msm_tail_mergeable(A.info, B.info)) {
+        rc = tail_pair_g1() ? msm_launch_tail<TailCurve<G1R29>::paired, TailCurve<G1R29>::type>(L, &slot_a, 1, s, slot_b)
+                            : msm_launch_tail<TailCurve<G1R29>::type>(L, &slot_a, 1, s, slot_b);
+        if (!rc) { A.partner = slot_b; *merged = true; }
+    } else {
+        for (const int* one : {&slot_a, &slot_b}) {
+            if (rc) break;
+            rc = tail_pair_g1() ? msm_launch_tail<TailCurve<G1R29>::paired, TailCurve<G1R29>::type>(L, one, 1, s)
+                                : msm_launch_tail<TailCurve<G1R29>::type>(L, one, 1, s);
+        }
+    }
+    return rc;
+}
 int msm_g2_launch(Lane& L, const Affine<Fq2>* d_points, bool prepared, int* slot, hipStream_t s) {
     if (!ctx()) return WS_ERR_NOINIT;
     return msm_launch<G2R29, G2>(L, 1, d_points, prepared, slot, s);
@@ -1755,7 +1871,12 @@ bool msm_ready(Lane& L, int slot) {
 }
 int msm_g1_finish(Lane& L, int slot, XYZZ<Fq>* out_host) {
     MsmPending* P = live_slot(L, slot, 0);
-    return P ? msm_finish_t<G1>(*P, out_host) : WS_ERR_ARG;
+    if (!P) return WS_ERR_ARG;
+    const int partner = P->partner;
+    P->partner = -1;
+    const int rc = msm_finish_t<G1>(*P, out_host);
+    if (partner >= 0) L.msm->slot[partner].active = false;      // (its buckets have been read: the merged tail has ended, or the proof is given up)
+    return rc;
 }
 int msm_g2_finish(Lane& L, int slot, XYZZ<Fq2>* out_host) {
     MsmPending* P = live_slot(L, slot, 1);

@@ -479,7 +479,7 @@ typedef std::function<int(hipStream_t, Fe*)> CalcHFn;
 // callers hand over host memory; the 32 B x nVars of H2D are inside every drop-in call).
 static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard sh, MsmSums* out, hipStream_t s,
                       const std::function<void(const MsmSums&)>& after_ab1 = nullptr, bool skip_h = false, const CalcHFn& calc_h = nullptr,
-                      const uint8_t* h_witness = nullptr) {
+                      const uint8_t* h_witness = nullptr, bool one_call = false) {
     Trace tr;
     // a points-sharded key sums its own pairs: the witness slice [lo, lo + n_local) against the resident slice of every
     // section (all windows), h[hlo ..] against its hExps slice
@@ -575,6 +575,15 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
     // chains run BESIDE each other: B2 with its tail on a third queue, A, B1 and C under ONE batched tail on the first, CALC_H and
     // H on the second (profiles/r03_s12_prove_order3.txt: 2^16 proofs -31 %, 2^18 -35 %, 2^19 -8 %, 2^20 +3 %).
     const bool small = overlap && (uint64_t)nv * msm_table_rows(table_cw ? table_cw : 16) < ((uint64_t)1 << 23) && L.stream3 && s != L.stream3;
+    // ONE reduction tail for C and H (round 7): pi_c only uses their sum, so the H buckets are added to C's bucket by bucket and the
+    // chunk sums, trees, rows, copy and host chain run once (msm.hip: msm_chunks<DUAL>; 3 additions per bucket pair instead of 4).  The
+    // merged tail goes to the first queue behind C's accumulation and waits there for H's.  Only for the one-call prover on a whole
+    // key (out->C then holds C + H, out->H infinity: a partial record keeps the two apart) and only when both plans have one tail
+    // geometry: table plans of one window width.  WSNARK_PROVE_CH_TAIL: 0 = off, 1 = wherever that holds, default: the full-size
+    // arrangement (the small one keeps C under the batched tail of A and B1).  A/B: profiles/r07_ch_tail_ab.txt
+    const long ch_sw = tuning_get("PROVE_CH_TAIL", 2);
+    const bool ch_merge = one_call && !skip_h && !calc_h && sh.off == 0 && sh.stride == 1 && K->shard_world == 1 && !K->h_log_m && table_cw &&
+                          table_cw == table_ch && nv && K->h_local && (ch_sw == 1 || (ch_sw != 0 && !small));
     const Affine<Fq>* g1sets[3] = {K->pointsA.as<Affine<Fq>>(), K->pointsB1.as<Affine<Fq>>(), K->pointsC.as<Affine<Fq>>()};
     const int plans[3] = {planA, planB, 0};
     int g1slots[3] = {-1, -1, -1};
@@ -589,9 +598,10 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
         msm_select_plan(L, 0);
         if (rc) return rc;
         WS_HIP_CHECK(hipEventRecord(L.ev_g2, s3));
-        rc = msm_g1_launch_batch(L, g1sets, 3, true, g1slots, s, plans);                                   // :617, :618, :620: one tail
+        rc = msm_g1_launch_batch(L, g1sets, ch_merge ? 2 : 3, true, g1slots, s, plans);                    // :617, :618, :620: one tail
         hA = g1slots[0]; hB1 = g1slots[1]; hC = g1slots[2];
         if (rc) return rc;
+        if (ch_merge && (rc = msm_g1_launch_acc_only(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s))) return rc;   // (its tail: with H's, below)
         WS_HIP_CHECK(hipStreamWaitEvent(s, L.ev_g2, 0));              // s stays the caller's ordering point
         tr.mark("plan(w) + B2 on queue 3 + A, B1, C batched");
     } else {
@@ -604,7 +614,9 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
         hA = g1slots[0]; hB1 = g1slots[1];
         if (rc) return rc;
         msm_select_plan(L, 0);
-        if ((rc = msm_g1_launch(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s))) return rc;                // :620 (padded)
+        rc = ch_merge ? msm_g1_launch_acc_only(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s)               // (its tail: with H's, below)
+                      : msm_g1_launch(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s);                       // :620 (padded)
+        if (rc) return rc;
         tr.mark("launch A, B1, C");
     }
     if (skip_h) {
@@ -623,20 +635,34 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
         if ((rc = enqueue_calc_h())) return rc;
         tr.mark("calc_h enqueued");
     }
-    msm_select_plan(L, s2 != s ? 1 : 0);
+    // (one queue: the H plan takes the witness plan's place -- unless C's buckets still wait for the merged tail, which reads the
+    //  bounds of both plans)
+    msm_select_plan(L, (s2 != s || ch_merge) ? 1 : 0);
     rc = msm_plan_dev(L, d_h + K->hlo, K->h_local, sh, s2, table_ch);
-    if (!rc) rc = msm_g1_launch(L, K->pointsH.as<Affine<Fq>>(), true, &hH, s2);                           // :614
+    if (!rc) rc = ch_merge ? msm_g1_launch_acc_only(L, K->pointsH.as<Affine<Fq>>(), true, &hH, s2)
+                           : msm_g1_launch(L, K->pointsH.as<Affine<Fq>>(), true, &hH, s2);                 // :614
     msm_select_plan(L, 0);
     if (rc) return rc;
     if (s2 != s) { WS_HIP_CHECK(hipEventRecord(L.ev_h, s2)); WS_HIP_CHECK(hipStreamWaitEvent(s, L.ev_h, 0)); }   // s stays the caller's ordering point
-    tr.mark("plan(h) + launch H");
+    bool ch_merged = false;                          // hC carries C + H, hH is released with it
+    if (ch_merge && (rc = msm_g1_launch_tail_merged(L, hC, hH, s, &ch_merged))) return rc;      // (behind the wait: H's buckets are complete)
+    tr.mark(ch_merged ? "plan(h) + accumulate H + one tail for C + H" : "plan(h) + launch H");
     const bool g2_fin = !small;                      // (small proofs: B2 ends on its own queue, A / B1 / C come first)
     if (g2_fin && (rc = msm_g2_finish(L, hB2, &out->B2))) return rc;
     if ((rc = msm_g1_finish(L, hA, &out->A))) return rc;
     if ((rc = msm_g1_finish(L, hB1, &out->B1))) return rc;
     tr.mark(g2_fin ? "finish B2, A, B1" : "finish A, B1");
     if (after_ab1) after_ab1(*out);
-    if (!g2_fin && (rc = msm_g1_finish(L, hC, &out->C))) return rc;
+    if (ch_merged) {
+        // one G1 sum is left, and it is the last thing on the first queue (small proofs: B2 ends on the third one, before or after it)
+        if ((rc = msm_g1_finish(L, hC, &out->C))) return rc;
+        out->H = G1::infinity();
+        if (!g2_fin && (rc = msm_g2_finish(L, hB2, &out->B2))) return rc;
+        tr.mark(g2_fin ? "finish C + H" : "finish C + H, B2");
+        guard.armed = false;
+        return WS_OK;
+    }
+    if (!g2_fin && !ch_merge && (rc = msm_g1_finish(L, hC, &out->C))) return rc;
     tr.mark(g2_fin ? "host work on A, B1" : "host work on A, B1; finish C");
     // the two queues end independently: finish whichever sum reaches the host first (its serial host tail then runs while
     // the GPU still works on the other one), so poll both instead of blocking on one
@@ -654,6 +680,7 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
             }
         }
     }
+    if (!g2_fin && ch_merge && (rc = msm_g1_finish(L, hC, &out->C))) return rc;      // (plans of two geometries after all: C had a tail of its own)
     tr.mark(g2_fin ? "finish H, C" : "finish H, B2");
     guard.armed = false;
     return WS_OK;
@@ -754,7 +781,7 @@ static int groth16_prove(ProvingKey* K, Lane& L, const Fe* d_witness, const uint
     MsmSums M;
     Blinding::Pre pp;
     EarlyParts E;
-    if ((rc = prove_msms(K, L, d_witness, WindowShard{}, &M, s, [&](const MsmSums& m) { prove_assemble_early(K, m, B, pp, &E); }, false, nullptr, h_witness)))
+    if ((rc = prove_msms(K, L, d_witness, WindowShard{}, &M, s, [&](const MsmSums& m) { prove_assemble_early(K, m, B, pp, &E); }, false, nullptr, h_witness, true)))
         return rc;
     Trace tr;
     prove_assemble(K, M, B, pp, E, out384);

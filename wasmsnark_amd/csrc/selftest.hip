@@ -242,6 +242,10 @@ __host__ __device__ inline typename C::PtP st_curve_op(int op, const typename C:
             r = C::mul_bytes(from_jac(pj), sc, nb);
             break;
         }
+        // the reduction tail's straight-path addition (add_fast): 10 = the accumulator after the call (p + q where it accepts, p untouched
+        // where it refuses), 11 = q where it accepts, infinity where it refuses
+        case 10: r = from_jac(pj); (void)C::add_fast(r, from_jac(qj)); break;
+        case 11: { Pt a = from_jac(pj); const Pt b = from_jac(qj); r = C::add_fast(a, b) ? b : C::infinity(); break; }
         default: *ok = false; break;
     }
     return C::pt_from_internal(r);
@@ -271,7 +275,7 @@ __global__ __launch_bounds__(64) void st_curve_pair_kernel(int op, const Fe* __r
     out[8 * i + h] = r.x; out[8 * i + 2 + h] = r.y; out[8 * i + 4 + h] = r.zz; out[8 * i + 6 + h] = r.zzz;
     if (!ok) *bad = 1;
 }
-// the paired G1 curve (curve_pair.h: CurvePairG1): two lanes per vector, lo = (X, ZZ), hi = (Y, ZZZ); ops 0 (add), 1 (double), 3 (copy)
+// the paired G1 curve (curve_pair.h: CurvePairG1): two lanes per vector, lo = (X, ZZ), hi = (Y, ZZZ); ops 0 (add), 1 (double), 3 (copy), 10 / 11 (add_fast)
 __global__ __launch_bounds__(64) void st_curve_pair_g1_kernel(int op, const Fe* __restrict__ p, const Fe* __restrict__ q, Fe* __restrict__ out,
                                                                 uint64_t n, int* __restrict__ bad) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -291,6 +295,8 @@ __global__ __launch_bounds__(64) void st_curve_pair_g1_kernel(int op, const Fe* 
     if (op == 0) r = G1P29::add(a, b);
     else if (op == 1) r = G1P29::dbl(a);
     else if (op == 3) r = a;
+    else if (op == 10) { r = a; (void)G1P29::add_fast(r, b); }
+    else if (op == 11) { G1P29::Pt t = a; r = G1P29::add_fast(t, b) ? b : G1P29::infinity(); }
     else *bad = 1;
     out[4 * i + h] = F::from_internal(r.a);                       // x | y
     out[4 * i + 2 + h] = F::from_internal(r.b);                   // zz | zzz
@@ -308,7 +314,7 @@ static int st_curve_pair_g1_dev(int op, const uint8_t* p, const uint8_t* q, uint
     }
     return WS_OK;
 }
-// G2 on FOUR lanes (curve_pair.h: CurvePairG1<Fp2PairT, 2>): lane (h2, h1) holds component h1 of (X, ZZ) or of (Y, ZZZ); ops 0, 1, 3
+// G2 on FOUR lanes (curve_pair.h: CurvePairG1<Fp2PairT, 2>): lane (h2, h1) holds component h1 of (X, ZZ) or of (Y, ZZZ); ops 0, 1, 3, 10, 11
 __global__ __launch_bounds__(64) void st_curve_quad_g2_kernel(int op, const Fe* __restrict__ p, const Fe* __restrict__ q, Fe* __restrict__ out,
                                                                 uint64_t n, int* __restrict__ bad) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -330,6 +336,8 @@ __global__ __launch_bounds__(64) void st_curve_quad_g2_kernel(int op, const Fe* 
     if (op == 0) r = G2Q29::add(a, b);
     else if (op == 1) r = G2Q29::dbl(a);
     else if (op == 3) r = a;
+    else if (op == 10) { r = a; (void)G2Q29::add_fast(r, b); }
+    else if (op == 11) { G2Q29::Pt t = a; r = G2Q29::add_fast(t, b) ? b : G2Q29::infinity(); }
     else *bad = 1;
     out[8 * i + h1 + 2 * h2] = F::from_internal(r.a);             // x.c | y.c
     out[8 * i + 4 + h1 + 2 * h2] = F::from_internal(r.b);         // zz.c | zzz.c
@@ -400,9 +408,9 @@ int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, 
     Context* X = ctx();
     if (!X) return WS_ERR_NOINIT;
     if (n == 0) return WS_OK;
-    if (n > (1u << 20) || op < 0 || op > 8 || (op == 8 && impl == 4)) return WS_ERR_ARG;
-    if (g == 1 && impl == 5) return (op == 0 || op == 1 || op == 3) ? st_curve_pair_g1_dev(op, p, q, out, n, X->stream) : (int)WS_ERR_ARG;
-    if (g == 2 && impl == 6) return (op == 0 || op == 1 || op == 3) ? st_curve_quad_g2_dev(op, p, q, out, n, X->stream) : (int)WS_ERR_ARG;
+    if (n > (1u << 20) || op < 0 || op > 11 || op == 9 || (op == 8 && impl == 4)) return WS_ERR_ARG;
+    if (g == 1 && impl == 5) return (op == 0 || op == 1 || op == 3 || op == 10 || op == 11) ? st_curve_pair_g1_dev(op, p, q, out, n, X->stream) : (int)WS_ERR_ARG;
+    if (g == 2 && impl == 6) return (op == 0 || op == 1 || op == 3 || op == 10 || op == 11) ? st_curve_quad_g2_dev(op, p, q, out, n, X->stream) : (int)WS_ERR_ARG;
     hipStream_t s = X->stream;
     if (g == 1) {
         if (impl == 0) return st_curve_dev<G1R29, G1>(op, p, q, out, n, s);
