@@ -444,6 +444,61 @@ int wsnark_pkey_circuit_check_sections(const wsnark_key_sections_t* key, const w
 int wsnark_pkey_circuit_check_file(const char* path, const wsnark_powers_t* powers, const wsnark_circuit_t* circuit,
                                    const void* vk, size_t vk_len, uint64_t n_inputs, const void* seed32, wsnark_pkey_circuit_verdict_t* out);
 int wsnark_circuit_row_sums(const wsnark_circuit_t* circuit, const void* weights, void* out_public, void* out_private);
+/* ---- a witness against its circuit: which constraints fail (csrc/witcheck.hip; snarkjs: `wtns check <r1cs> <wtns>`) ----
+ * wsnark_groth16_prove evaluates a = A.w and b = B.w and takes a o b on the domain as C.w: a proving key holds no C matrix, so a witness
+ * that breaks a constraint proves like any other, and every verifier rejects the proof without saying why.  This is the step between
+ * the witness generator and the prover: row i is bad iff (A_i.w)(B_i.w) != C_i.w mod r.
+ *   wsnark_circuit_load           the circuit's three matrices resident as row-major CSR on the calling thread's device (the loaders'
+ *                                 transposition); wsnark_circuit_info reads the counts, the three record counts and the device bytes
+ *                                 back (any out pointer may be NULL); wsnark_circuit_free(NULL) is ignored.  The handle is read-only
+ *                                 after the load.
+ *   wsnark_circuit_witness_check  witness: host, nVars x 32 B plain LE, any 256-bit values -- signals >= r are reduced mod r for the
+ *                                 check, as the prover reduces them, and counted in `unreduced`.  witness_len < nVars x 32 is
+ *                                 WSNARK_ERR_SIZE; a longer buffer is accepted and only nVars signals are read, as in
+ *                                 wsnark_groth16_prove.  One lane per row (lc_check_kernel): a wavefront's 64 verdicts leave as one word
+ *                                 of a bad-row bitmask, the count and the smallest bad index are reduced on the device.
+ *   bad_rows / bad_values         cap x u64, ascending, the SMALLEST bad indices; cap x 96 B, a | b | c of that row, plain LE and
+ *                                 canonical.  listed = min(bad, cap) entries are written, the rest is left as it was.  cap == 0: both
+ *                                 may be NULL.  The bitmask (domain / 8 bytes) comes to the host only when bad > 0 && cap > 0; a good
+ *                                 witness costs one small download.
+ *   wsnark_circuit_witness_check_dev   the witness already on the handle's device: d_witness is memory of THAT device (the one
+ *                                 wsnark_circuit_load ran on), 16-byte aligned -- the kernels read whole 32-byte elements; a
+ *                                 misaligned pointer is WSNARK_ERR_ARG; stream: the queue d_witness is ready on, a queue of that same
+ *                                 device (NULL = the lane's own).  The lists and the report are host memory; the call returns when they are written.
+ *   wsnark_witness_check          load, check and free in one call: the same report and lists, the matrices' time in ms[0].
+ *   A bad witness is a RESULT: WSNARK_OK with ok = 0.
+ *   errors      what wsnark_circuit_row_sums rejects of a circuit is rejected with the same codes (nPublic + 1 > nVars, a truncated
+ *               stream, a record index >= domain: WSNARK_ERR_FORMAT; a domain that is no power of two in [2, 2^24]: WSNARK_ERR_SIZE); a
+ *               NULL circuit, handle, witness or report, or cap > 0 with a NULL list: WSNARK_ERR_ARG; before wsnark_init
+ *               WSNARK_ERR_NOINIT.  On every error the report and the lists are left untouched.
+ *   threads     each call takes a lane; the bitmask, the counters and the witness copy belong to the call, not to the handle: two
+ *               threads may check two witnesses on one handle at once.
+ *   Out of scope: group (multi-GPU) handles; readers of .r1cs / .wtns files; whether the circuit's A and B are a given key's (that is
+ *   bit 0 of wsnark_pkey_circuit_check); no wsnark_groth16_prove* entry point changes. */
+typedef struct wsnark_circuit_res wsnark_circuit_res_t;      /* a circuit's three matrices resident as row-major CSR */
+int  wsnark_circuit_load(const wsnark_circuit_t* circuit, wsnark_circuit_res_t** out_handle);
+void wsnark_circuit_free(wsnark_circuit_res_t* handle);       /* NULL is ignored */
+int  wsnark_circuit_info(const wsnark_circuit_res_t* h, uint32_t* n_vars, uint32_t* n_public, uint32_t* domain,
+                         uint64_t nnz[3], uint64_t* bytes);   /* any out pointer may be NULL */
+typedef struct {
+    uint64_t rows;                  /* = domain */
+    uint64_t bad;                   /* rows with (A_i.w)(B_i.w) != C_i.w mod r */
+    uint64_t first_bad;             /* UINT64_MAX if none */
+    uint64_t listed;                /* min(bad, cap): entries written to bad_rows / bad_values */
+    uint64_t unreduced;             /* signals >= r (they are reduced mod r for the check, as the prover reduces them) */
+    uint64_t first_unreduced;       /* UINT64_MAX if none */
+    uint32_t one_ok;                /* witness[0] == 1 */
+    uint32_t ok;                    /* 1 iff bad == 0, one_ok, and no signal of index <= nPublic is >= r
+                                       (wsnark_groth16_verify rejects such a public input) */
+    double   ms[3];                 /* matrices (0 on a resident circuit), device (upload + kernels + download), whole call */
+} wsnark_witness_report_t;
+int wsnark_witness_check(const wsnark_circuit_t* circuit, const void* witness, size_t witness_len,
+                         uint64_t* bad_rows, void* bad_values, uint64_t cap, wsnark_witness_report_t* rep);
+int wsnark_circuit_witness_check(wsnark_circuit_res_t* h, const void* witness, size_t witness_len,
+                                 uint64_t* bad_rows, void* bad_values, uint64_t cap, wsnark_witness_report_t* rep);
+int wsnark_circuit_witness_check_dev(wsnark_circuit_res_t* h, const void* d_witness, size_t witness_len,
+                                     uint64_t* bad_rows_host, void* bad_values_host, uint64_t cap,
+                                     wsnark_witness_report_t* rep, void* stream);
 /* ---- powers of tau: contribute to a transcript, audit one (csrc/pwtau.hip; snarkjs: `powersoftau contribute` / `powersoftau verify`) ----
  * Phase 1 itself: the transcript wsnark_pkey_setup builds a key on.  A contribution by secrets t, a, b (non-zero mod r) turns the
  * transcript of (tau, alpha, beta) into the one of (t tau, a alpha, b beta):

@@ -224,6 +224,98 @@ def _circuit_verdict_dict(v):
     return out
 
 
+class _WitnessReport(C.Structure):  # wsnark_witness_report_t
+    _fields_ = [("rows", C.c_uint64), ("bad", C.c_uint64), ("first_bad", C.c_uint64), ("listed", C.c_uint64), ("unreduced", C.c_uint64),
+                ("first_unreduced", C.c_uint64), ("one_ok", C.c_uint32), ("ok", C.c_uint32), ("ms", C.c_double * 3)]
+
+
+def _witness_report_dict(r, rows, values):
+    """wsnark_witness_report_t and its two lists as a plain dict; first_bad / first_unreduced stay 2^64 - 1 when there is none"""
+    n = int(r.listed)
+    val = lambda k: int.from_bytes(bytes(values[32 * k:32 * k + 32]), "little")
+    return {"rows": int(r.rows), "bad": int(r.bad), "first_bad": int(r.first_bad), "listed": n, "unreduced": int(r.unreduced),
+            "first_unreduced": int(r.first_unreduced), "one_ok": int(r.one_ok), "ok": int(r.ok),
+            "ms": {"matrices": r.ms[0], "device": r.ms[1], "total": r.ms[2]},
+            "bad_rows": [int(rows[j]) for j in range(n)], "bad_values": [(val(3 * j), val(3 * j + 1), val(3 * j + 2)) for j in range(n)]}
+
+
+def witness_finding(report):
+    """One line naming the first thing check_witness found in a witness that is not ok (None for a good one)."""
+    if report["bad"]:
+        text = "constraint %d: (A.w)(B.w) != C.w" % report["first_bad"]
+        if report["bad_values"] and report["bad_rows"][0] == report["first_bad"]:
+            text += ": a=%d, b=%d, c=%d" % report["bad_values"][0]
+        return text + (" (%d bad constraints in all)" % report["bad"] if report["bad"] > 1 else "")
+    if not report["one_ok"]:
+        return "signal 0 is not 1"
+    return None if report["ok"] else "public signal >= r (the first unreduced signal is %d)" % report["first_unreduced"]
+
+
+def _witness_lists(max_rows):
+    cap = int(max_rows)
+    if cap < 0:
+        raise ValueError("max_rows must not be negative")
+    return cap, ((C.c_uint64 * cap)() if cap else None), ((C.c_uint8 * (96 * cap))() if cap else None)
+
+
+class ResidentCircuit:
+    """A circuit's three matrices resident on the device as row-major CSR (wsnark_circuit_load): witnesses are checked against it
+    without transposing the record streams again.  Read-only after the load: threads may share one."""
+
+    def __init__(self, lib, circuit):
+        self._lib = lib
+        self._h = C.c_void_p()
+        cs, keep = _circuit_struct(circuit)
+        lib.check(lib.c.wsnark_circuit_load(C.byref(cs), C.byref(self._h)))
+        inf = self.info()
+        self.n_vars, self.n_public, self.domain = inf["n_vars"], inf["n_public"], inf["domain"]
+
+    def info(self):
+        """{n_vars, n_public, domain, nnz: (A, B, C), bytes: what the matrices take on the device} (wsnark_circuit_info)"""
+        nv, npub, dom, nnz, nb = C.c_uint32(), C.c_uint32(), C.c_uint32(), (C.c_uint64 * 3)(), C.c_uint64()
+        self._lib.check(self._lib.c.wsnark_circuit_info(self._h, C.byref(nv), C.byref(npub), C.byref(dom), nnz, C.byref(nb)))
+        return {"n_vars": nv.value, "n_public": npub.value, "domain": dom.value, "nnz": tuple(int(x) for x in nnz), "bytes": nb.value}
+
+    def check_witness(self, witness, max_rows=16):
+        """Which constraints does `witness` (nVars x 32 bytes plain LE) break?  (wsnark_circuit_witness_check.)  Returns the report
+        as a dict -- rows, bad, first_bad, listed, unreduced, first_unreduced (2^64 - 1: none), one_ok, ok, ms -- plus "bad_rows",
+        the smallest min(bad, max_rows) bad indices, and "bad_values", (a, b, c) of each as ints.  A bad witness is a result."""
+        w, nw = _ro(witness)
+        cap, rows, values = _witness_lists(max_rows)
+        rep = _WitnessReport()
+        self._lib.check(self._lib.c.wsnark_circuit_witness_check(self._h, w, nw, rows, values, cap, C.byref(rep)))
+        return _witness_report_dict(rep, rows, values)
+
+    def check_witness_dev(self, d_witness, witness_len, max_rows=16, stream=None):
+        """The same for a witness already on the device (a raw device address; stream: the queue it is ready on)."""
+        cap, rows, values = _witness_lists(max_rows)
+        rep = _WitnessReport()
+        self._lib.check(self._lib.c.wsnark_circuit_witness_check_dev(self._h, d_witness, witness_len, rows, values, cap, C.byref(rep), stream))
+        return _witness_report_dict(rep, rows, values)
+
+    def free(self):
+        if self._h:
+            self._lib.c.wsnark_circuit_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _same_shape(circuit, key):
+    if (circuit.n_vars, circuit.n_public, circuit.domain) != (key.n_vars, key.n_public, key.domain):
+        raise ValueError("the circuit (nVars %d, nPublic %d, domain %d) is not the key's (%d, %d, %d)"
+                         % (circuit.n_vars, circuit.n_public, circuit.domain, key.n_vars, key.n_public, key.domain))
+
+
+def _require_good(report):
+    if not report["ok"]:
+        raise ValueError("the witness does not satisfy the circuit: " + witness_finding(report))
+
+
 def first_finding(report):
     """One line naming the first thing check_key found in a key that is not ok (None for a good key)."""
     for name in KEY_SECTIONS:
@@ -535,7 +627,11 @@ class Bn128:
     def fft_dev(self, d_buf, n, odd=0, inverse=False, stream=None):
         self.lib.check(self.lib.c.wsnark_fr_ntt_dev(d_buf, n, int(odd), 1 if inverse else 0, stream))
 
-    def groth16GenProof_dev(self, d_witness, witness_len, key, r=None, s=None, stream=None):
+    def groth16GenProof_dev(self, d_witness, witness_len, key, r=None, s=None, stream=None, circuit=None):
+        """circuit: a ResidentCircuit of the key's shape -- the witness is checked first and a bad one raises ValueError"""
+        if circuit is not None:
+            _same_shape(circuit, key)
+            _require_good(circuit.check_witness_dev(d_witness, witness_len, max_rows=1, stream=stream))
         out = (C.c_uint8 * 384)()
         rb = _ro(r)[0] if r is not None else None
         sb = _ro(s)[0] if s is not None else None
@@ -864,6 +960,22 @@ class Bn128:
         self.lib.check(self.lib.c.wsnark_circuit_row_sums(C.byref(cs), w, pub, prv))
         return bytes(pub)[:size], bytes(prv)[:size]
 
+    # --- a witness against its circuit (csrc/witcheck.hip; no reference counterpart -- snarkjs: wtns check) ---
+    def load_circuit(self, circuit):
+        """circuit: the dict of setup_key ({"n_vars", "n_public", "domain", "polsA", "polsB", "polsC"}).  Returns a ResidentCircuit:
+        .check_witness(witness, max_rows=16), .check_witness_dev(d_witness, witness_len, max_rows=16, stream=None), .info(), .free()."""
+        return ResidentCircuit(self.lib, circuit)
+
+    def check_witness(self, circuit, witness, max_rows=16):
+        """Load, check and free in one call (wsnark_witness_check): ResidentCircuit.check_witness's report and lists, with the
+        matrices' time in ms["matrices"]."""
+        cs, keep = _circuit_struct(circuit)
+        w, nw = _ro(witness)
+        cap, rows, values = _witness_lists(max_rows)
+        rep = _WitnessReport()
+        self.lib.check(self.lib.c.wsnark_witness_check(C.byref(cs), w, nw, rows, values, cap, C.byref(rep)))
+        return _witness_report_dict(rep, rows, values)
+
     def key_file_info(self, path):
         """Header of a key file (no GPU work): {n_vars, n_public, domain, file_bytes, format: 'proving_key.bin' | 'WSNARK64'}."""
         nv, npub, dom, nb, fmt = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_int()
@@ -907,10 +1019,13 @@ class Bn128:
         return proof_from_bytes(bytes(out))
 
     # --- src/bn128.js:580-720 ---
-    def groth16GenProof(self, signals, pkey, r=None, s=None):
+    def groth16GenProof(self, signals, pkey, r=None, s=None, circuit=None):
         """signals: witness.bin bytes; pkey: proving_key.bin bytes or a ProvingKey.
         r, s: optional 32-byte blinding values (the reference draws them with
-        crypto.randomBytes, src/bn128.js:642-661). Returns {pi_a, pi_b, pi_c} of decimal strings."""
+        crypto.randomBytes, src/bn128.js:642-661). Returns {pi_a, pi_b, pi_c} of decimal strings.
+        circuit: a ResidentCircuit (load_circuit) whose nVars, nPublic and domain are the key's, else ValueError before anything
+        runs.  The witness is checked against it first; one that breaks a constraint raises ValueError naming the first bad
+        constraint with its a, b, c, and no proof is computed.  None: nothing is checked, as in the reference."""
         key = pkey if isinstance(pkey, ProvingKey) else ProvingKey(self.lib, pkey)
         w, nw = _ro(signals)
         out = (C.c_uint8 * 384)()
@@ -918,6 +1033,14 @@ class Bn128:
         sb = _ro(s)[0] if s is not None else None
         if (r is not None and len(r) != 32) or (s is not None and len(s) != 32):
             raise ValueError("r and s must be 32 bytes")
+        if circuit is not None:
+            try:
+                _same_shape(circuit, key)
+                _require_good(circuit.check_witness(signals, max_rows=1))
+            except Exception:
+                if key is not pkey:
+                    key.free()
+                raise
         self.lib.check(self.lib.c.wsnark_groth16_prove(key._h, w, nw, rb, sb, out))
         if key is not pkey:
             key.free()

@@ -16,6 +16,7 @@ static_assert(sizeof(wsnark_pkey_delta_report_t) == 104 && sizeof(wsnark_pkey_de
 static_assert(sizeof(wsnark_pkey_setup_report_t) == 192, "the bindings read this by offset");
 static_assert(sizeof(wsnark_powers_report_t) == 192, "the bindings read this by offset");
 static_assert(sizeof(wsnark_pkey_circuit_verdict_t) == 56, "the bindings read this by offset");
+static_assert(sizeof(wsnark_witness_report_t) == 80, "the bindings read this by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
 // addon runs on the libuv pool): select the context's device first.
@@ -455,6 +456,46 @@ int wsnark_pkey_circuit_check_file(const char* path, const wsnark_powers_t* powe
 int wsnark_circuit_row_sums(const wsnark_circuit_t* circuit, const void* weights, void* out_public, void* out_private) {
     REQUIRE_CTX();
     return circuit_row_sums(circuit, weights, out_public, out_private);
+}
+// ---- a witness against its circuit (witcheck.hip) ----
+int wsnark_circuit_load(const wsnark_circuit_t* circuit, wsnark_circuit_res_t** out_handle) {
+    REQUIRE_CTX();
+    if (!out_handle) return WSNARK_ERR_ARG;
+    CircuitRes* H = nullptr;
+    int rc = circuit_load(circuit, &H);
+    if (rc) return rc;
+    *out_handle = reinterpret_cast<wsnark_circuit_res_t*>(H);
+    return WSNARK_OK;
+}
+void wsnark_circuit_free(wsnark_circuit_res_t* h) {
+    if (!h) return;
+    CtxScope scope(circuit_context(reinterpret_cast<const CircuitRes*>(h)));
+    circuit_free(reinterpret_cast<CircuitRes*>(h));
+}
+int wsnark_circuit_info(const wsnark_circuit_res_t* h, uint32_t* n_vars, uint32_t* n_public, uint32_t* domain, uint64_t nnz[3], uint64_t* bytes) {
+    if (!h) return WSNARK_ERR_ARG;
+    circuit_info(reinterpret_cast<const CircuitRes*>(h), n_vars, n_public, domain, nnz, bytes);
+    return WSNARK_OK;
+}
+int wsnark_witness_check(const wsnark_circuit_t* circuit, const void* witness, size_t witness_len, uint64_t* bad_rows, void* bad_values,
+                         uint64_t cap, wsnark_witness_report_t* rep) {
+    REQUIRE_CTX();
+    return witness_check(circuit, witness, witness_len, bad_rows, bad_values, cap, rep);
+}
+int wsnark_circuit_witness_check(wsnark_circuit_res_t* h, const void* witness, size_t witness_len, uint64_t* bad_rows, void* bad_values,
+                                 uint64_t cap, wsnark_witness_report_t* rep) {
+    REQUIRE_CTX();      // (before the handle is looked at: WSNARK_ERR_NOINIT whatever the arguments)
+    if (!h) return WSNARK_ERR_ARG;
+    CtxScope scope(circuit_context(reinterpret_cast<const CircuitRes*>(h)));
+    return circuit_witness_check(reinterpret_cast<CircuitRes*>(h), witness, witness_len, false, bad_rows, bad_values, cap, rep, nullptr);
+}
+int wsnark_circuit_witness_check_dev(wsnark_circuit_res_t* h, const void* d_witness, size_t witness_len, uint64_t* bad_rows_host,
+                                     void* bad_values_host, uint64_t cap, wsnark_witness_report_t* rep, void* stream) {
+    REQUIRE_CTX();
+    if (!h) return WSNARK_ERR_ARG;
+    CtxScope scope(circuit_context(reinterpret_cast<const CircuitRes*>(h)));
+    return circuit_witness_check(reinterpret_cast<CircuitRes*>(h), d_witness, witness_len, true, bad_rows_host, bad_values_host, cap, rep,
+                                 (hipStream_t)stream);
 }
 int wsnark_pkey_shard_info(const wsnark_pkey_t* h, uint32_t* rank, uint32_t* world, uint64_t* first_signal, uint64_t* n_signals,
                            uint64_t* n_hexps, uint32_t* h_interleave_log) {

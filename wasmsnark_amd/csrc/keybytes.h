@@ -245,6 +245,21 @@ int pkey_delta_verify_sections(const KeySections& O, const KeySections& N, const
 int pkey_circuit_check_sections(const KeySections& S, const wsnark_powers_t* P, const wsnark_circuit_t* K, const uint8_t* vk, size_t vk_len,
                                 uint64_t n_inputs, const uint8_t* seed32, wsnark_pkey_circuit_verdict_t* out);
 int circuit_row_sums(const wsnark_circuit_t* K, const void* weights, void* out_public, void* out_private);
+// what setup_prepare (pkeysetup.hip) rejects of a circuit, with its codes; the three record streams as row-major CSR with the loaders'
+// conditions and codes (a truncated stream, a record index >= domain: WS_ERR_FORMAT)
+int circuit_shape_check(const wsnark_circuit_t* K);
+int circuit_to_csr(const wsnark_circuit_t* K, CsrMatrix M[3], hipStream_t s);
+// a witness against its circuit (witcheck.hip): a circuit's three matrices resident as row-major CSR; which rows fail for a witness on
+// the host or (on_device) already resident, on queue s (nullptr: the lane's own)
+struct CircuitRes;
+Context* circuit_context(const CircuitRes* H);
+int circuit_load(const wsnark_circuit_t* K, CircuitRes** out);
+void circuit_free(CircuitRes* H);
+void circuit_info(const CircuitRes* H, uint32_t* n_vars, uint32_t* n_public, uint32_t* domain, uint64_t nnz[3], uint64_t* bytes);
+int circuit_witness_check(CircuitRes* H, const void* witness, size_t witness_len, bool on_device, uint64_t* bad_rows, void* bad_values,
+                          uint64_t cap, wsnark_witness_report_t* rep, hipStream_t s);
+int witness_check(const wsnark_circuit_t* K, const void* witness, size_t witness_len, uint64_t* bad_rows, void* bad_values, uint64_t cap,
+                  wsnark_witness_report_t* rep);
 // the audit's per-point kernels on device-resident points in reference format (pkeycheck.hip): counts into d_acc with the global index
 // base + i; the G2 one with the order-r subgroup test (PKCHECK_SUBGROUP picks its form), d_K: the pairing constants on the device
 int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s);

@@ -75,13 +75,7 @@ __global__ __launch_bounds__(256) void fr_add_kernel(const Fe* __restrict__ a, c
     out[i] = Fr::add(a[i], b[i]);
 }
 
-namespace {
-// a wipe the compiler cannot drop: the stores are volatile
-void wipe(void* p, size_t n) {
-    volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
-    for (size_t i = 0; i < n; i++) v[i] = 0;
-}
-
+// ---- shared with witcheck.hip (keybytes.h) ----
 // what setup_prepare (pkeysetup.hip) rejects of a circuit, with its codes
 int circuit_shape_check(const wsnark_circuit_t* K) {
     if (!K || !K->polsA || !K->polsB || !K->polsC) return WS_ERR_ARG;
@@ -90,7 +84,26 @@ int circuit_shape_check(const wsnark_circuit_t* K) {
     if (n < 2 || (n & (n - 1)) || n > ((uint64_t)1 << 24)) { set_last_error("circuit check: domain must be a power of two in [2, 2^24]"); return WS_ERR_SIZE; }
     return WS_OK;
 }
-// ... and of a transcript
+
+// the three record streams as row-major CSR (rows: constraints, columns: signals), with the loaders' conditions and codes
+int circuit_to_csr(const wsnark_circuit_t* K, CsrMatrix M[3], hipStream_t s) {
+    const uint8_t* pols[3] = {(const uint8_t*)K->polsA, (const uint8_t*)K->polsB, (const uint8_t*)K->polsC};
+    const uint64_t lens[3] = {K->polsA_len, K->polsB_len, K->polsC_len};
+    for (int m = 0; m < 3; m++) {
+        size_t used = 0;
+        if (int rc = pols_to_csr(pols[m], (size_t)lens[m], K->n_vars, K->domain, &M[m], &used, s)) return rc;
+    }
+    return WS_OK;
+}
+
+namespace {
+// a wipe the compiler cannot drop: the stores are volatile
+void wipe(void* p, size_t n) {
+    volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
+    for (size_t i = 0; i < n; i++) v[i] = 0;
+}
+
+// what setup_prepare (pkeysetup.hip) rejects of a transcript, with its codes
 int powers_shape_check(const wsnark_powers_t* P, uint64_t n) {
     if (!P || !P->tau_g1 || !P->tau_g2 || !P->alpha_tau_g1 || !P->beta_tau_g1 || !P->beta_g2) return WS_ERR_ARG;
     if (P->domain != n) { set_last_error("circuit check: the powers and the circuit name different domains"); return WS_ERR_SIZE; }
@@ -103,17 +116,6 @@ int powers_shape_check(const wsnark_powers_t* P, uint64_t n) {
     if (memcmp(P->tau_g1, &g1.x, 64) != 0 || memcmp(P->tau_g2, &g2.x, 128) != 0) {
         set_last_error("circuit check: tau_g1[0] / tau_g2[0] is not the generator");
         return WS_ERR_FORMAT;
-    }
-    return WS_OK;
-}
-
-// the three record streams as row-major CSR (rows: constraints, columns: signals), with the loaders' conditions and codes
-int circuit_to_csr(const wsnark_circuit_t* K, CsrMatrix M[3], hipStream_t s) {
-    const uint8_t* pols[3] = {(const uint8_t*)K->polsA, (const uint8_t*)K->polsB, (const uint8_t*)K->polsC};
-    const uint64_t lens[3] = {K->polsA_len, K->polsB_len, K->polsC_len};
-    for (int m = 0; m < 3; m++) {
-        size_t used = 0;
-        if (int rc = pols_to_csr(pols[m], (size_t)lens[m], K->n_vars, K->domain, &M[m], &used, s)) return rc;
     }
     return WS_OK;
 }

@@ -159,6 +159,33 @@ function powersReport(ab, msNames) {
     msNames.forEach((name, k) => { if (name) out.ms[name] = v.getFloat64(160 + 8 * k, true); });
     return out;
 }
+/* wsnark_witness_report_t (80 bytes) and its two lists of `cap` entries -> the object of checkWitness(): counts are Numbers, firstBad /
+ * firstUnreduced null when there is none, badRows Numbers, badValues [a, b, c] BigInts of each listed row */
+function witnessReport(ab, cap) {
+    const v = new DataView(ab);
+    const u64 = (o) => Number(v.getBigUint64(o, true));
+    const big = (o) => { let x = 0n; for (let i = 3; i >= 0; i--) x = (x << 64n) | v.getBigUint64(o + 8 * i, true); return x; };
+    const bad = u64(8), unreduced = u64(32), listed = u64(24);
+    const out = { rows: u64(0), bad, firstBad: bad ? u64(16) : null, listed, unreduced, firstUnreduced: unreduced ? u64(40) : null,
+                  oneOk: v.getUint32(48, true) === 1, ok: v.getUint32(52, true) === 1,
+                  ms: { matrices: v.getFloat64(56, true), device: v.getFloat64(64, true), total: v.getFloat64(72, true) }, badRows: [], badValues: [] };
+    for (let j = 0; j < listed; j++) {
+        out.badRows.push(u64(80 + 8 * j));
+        const o = 80 + 8 * cap + 96 * j;
+        out.badValues.push([big(o), big(o + 32), big(o + 64)]);
+    }
+    return out;
+}
+function witnessFinding(rep) {
+    if (rep.bad) {
+        let text = `constraint ${rep.firstBad}: (A.w)(B.w) != C.w`;
+        if (rep.badRows.length && rep.badRows[0] === rep.firstBad) text += `: a=${rep.badValues[0][0]}, b=${rep.badValues[0][1]}, c=${rep.badValues[0][2]}`;
+        return text + (rep.bad > 1 ? ` (${rep.bad} bad constraints in all)` : "");
+    }
+    if (!rep.oneOk) return "signal 0 is not 1";
+    return rep.ok ? null : `public signal >= r (the first unreduced signal is ${rep.firstUnreduced})`;
+}
+const maxRowsOf = (opts) => (opts && opts.maxRows !== undefined ? opts.maxRows : 16);
 function firstFinding(rep) {
     for (const name of KEY_SECTIONS) if (rep[name].bad) return `${rep[name].bad} bad point(s) in section ${name}, the first at index ${rep[name].firstBad}: ${rep[name].firstReason}`;
     for (const name of KEY_FIXED) if (rep.fixed[name]) return `${name}: ${rep.fixed[name]}`;
@@ -377,6 +404,47 @@ class Bn128 {
         }
         return circuitVerdict(await addon.checkKeyCircuit(key, circuit.nVars, circuit.nPublic, circuit.domain, bufs, vk, opts && opts.seed ? opts.seed : null));
     }
+    /* No counterpart in the reference (snarkjs: `wtns check <r1cs> <wtns>`): which constraints does a witness break (include/wsnark.h:
+     * wsnark_witness_check)?  The prover cannot tell -- a key holds no C matrix -- and a proof of a bad witness is simply rejected by
+     * every verifier.  circuit: the object of newKey() ({nVars, nPublic, domain, polsA, polsB, polsC}); witness: nVars x 32 bytes.
+     * Resolves to {rows, bad, firstBad, listed, unreduced, firstUnreduced, oneOk, ok, ms, badRows, badValues}: the smallest
+     * min(bad, opts.maxRows = 16) bad rows and [a, b, c] of each as BigInts.  A bad witness is a result, not a rejection. */
+    async checkWitness(circuit, witness, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: checkWitness runs on a single GPU (build a Bn128 without {devices})");
+        const bufs = [circuit.polsA, circuit.polsB, circuit.polsC];
+        bufs.forEach(asBytes);
+        asBytes(witness);
+        const cap = maxRowsOf(opts);
+        return witnessReport(await addon.checkWitness(circuit.nVars, circuit.nPublic, circuit.domain, bufs, witness, cap), cap);
+    }
+    /* The circuit's three matrices made RESIDENT once (wsnark_circuit_load): resolves to {checkWitness(witness, {maxRows}), info(),
+     * free()}.  Checks on one loaded circuit may run side by side; free() hands the device memory back once those in flight are done
+     * (the garbage collector does it otherwise).  Pass the object to groth16GenProof as opts.circuit to have every witness checked
+     * before it is proved. */
+    async loadCircuit(circuit) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: loadCircuit runs on a single GPU (build a Bn128 without {devices})");
+        const bufs = [circuit.polsA, circuit.polsB, circuit.polsC];
+        bufs.forEach(asBytes);
+        const handle = await addon.loadCircuit(circuit.nVars, circuit.nPublic, circuit.domain, bufs);
+        let inflight = 0, freed = false;
+        const release = () => { if (freed && inflight === 0) addon.circuitFree(handle); };
+        return {
+            async checkWitness(witness, opts) {
+                if (freed) throw new Error("wsnark: this circuit has been freed");
+                asBytes(witness);
+                const cap = maxRowsOf(opts);
+                inflight++;
+                try { return witnessReport(await addon.circuitCheckWitness(handle, witness, cap), cap); } finally { inflight--; release(); }
+            },
+            info() {
+                if (freed) throw new Error("wsnark: this circuit has been freed");
+                return addon.circuitInfo(handle);
+            },
+            free() { freed = true; release(); },
+        };
+    }
     /* A key FILE -- the reference's proving_key.bin or the WSNARK64 container for keys beyond its 4 GiB (js/formats.js:
      * writeKeyContainer; 2^24 constraints = 7.8 GB, more than one Buffer holds).  The library maps the file and reads only what it makes
      * resident; with a group every device reads its own shard.  Handles are cached per path while the file's size and mtime stand. */
@@ -404,10 +472,20 @@ class Bn128 {
     allocInput(bytes) { return addon.allocPinned(bytes); }
     /* pkey: proving_key.bin bytes, or a handle from loadKey().
      * opts.r / opts.s: optional 32-byte blinding values (the reference draws them from crypto.randomBytes)
-     * opts.trustCache: see loadKey.  opts.timing: an object that receives {loadKey_ms, prove_ms, format_ms} of this call */
+     * opts.trustCache: see loadKey.  opts.timing: an object that receives {loadKey_ms, prove_ms, format_ms} of this call
+     * opts.circuit: an object from loadCircuit() whose nVars, nPublic and domain are the key's (else the call rejects before anything
+     * runs on the witness): the witness is checked first, and one that breaks a constraint rejects with an Error naming the first
+     * bad constraint and its a, b, c (.report holds the whole report); no proof is computed.  Without it nothing changes. */
     async groth16GenProof(signals, pkey, opts) {
         if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
         const t0 = process.hrtime.bigint();
+        if (opts && opts.circuit) {
+            const ci = opts.circuit.info(), ki = await this.keyInfo(pkey);
+            if (ci.nVars !== ki.nVars || ci.nPublic !== ki.nPublic || ci.domain !== ki.domainSize)
+                throw new Error(`wsnark: the circuit (nVars ${ci.nVars}, nPublic ${ci.nPublic}, domain ${ci.domain}) is not the key's (${ki.nVars}, ${ki.nPublic}, ${ki.domainSize})`);
+            const report = await opts.circuit.checkWitness(signals, { maxRows: 1 });
+            if (!report.ok) throw Object.assign(new Error("wsnark: the witness does not satisfy the circuit: " + witnessFinding(report)), { report });
+        }
         // which entry point a handle goes to is fixed when the call STARTS: terminate() clears this._group while calls may still be
         // awaiting their key, and a group key must never reach the single-context prove()
         const proveFn = this._group ? addon.groupProve : addon.prove;

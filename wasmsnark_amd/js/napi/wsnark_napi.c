@@ -23,6 +23,7 @@ typedef struct wsnark_pkey wsnark_pkey_t;
 typedef struct wsnark_points wsnark_points_t;
 typedef struct wsnark_group wsnark_group_t;
 typedef struct wsnark_group_pkey wsnark_group_pkey_t;
+typedef struct wsnark_circuit_res wsnark_circuit_res_t;
 static struct {
     void* h;
     int (*init)(int);
@@ -84,6 +85,12 @@ static struct {
     /* a key against its circuit and its powers of tau (include/wsnark.h: wsnark_pkey_circuit_check*) */
     int (*pkey_circuit_check)(const void*, size_t, const void*, const void*, const void*, size_t, uint64_t, const void*, void*);
     int (*pkey_circuit_check_file)(const char*, const void*, const void*, const void*, size_t, uint64_t, const void*, void*);
+    /* a witness against its circuit (include/wsnark.h: wsnark_circuit_load, wsnark_witness_check, wsnark_circuit_witness_check) */
+    int (*circuit_load)(const void*, wsnark_circuit_res_t**);
+    void (*circuit_free)(wsnark_circuit_res_t*);
+    int (*circuit_info)(const wsnark_circuit_res_t*, uint32_t*, uint32_t*, uint32_t*, uint64_t*, uint64_t*);
+    int (*witness_check)(const void*, const void*, size_t, uint64_t*, void*, uint64_t, void*);
+    int (*circuit_witness_check)(wsnark_circuit_res_t*, const void*, size_t, uint64_t*, void*, uint64_t, void*);
     char dir[4096];
 } L;
 
@@ -130,6 +137,8 @@ static int load_lib(char* err, size_t errlen) {
     SYM(g1_ntt, "wsnark_g1_ntt") SYM(g2_ntt, "wsnark_g2_ntt") SYM(pkey_setup_pkey, "wsnark_pkey_setup_pkey") SYM(pkey_setup_size, "wsnark_pkey_setup_size")
     SYM(g1_mul, "wsnark_g1_mul_batch") SYM(g2_mul, "wsnark_g2_mul_batch") SYM(powers_contribute, "wsnark_powers_contribute") SYM(powers_check, "wsnark_powers_check")
     SYM(pkey_circuit_check, "wsnark_pkey_circuit_check") SYM(pkey_circuit_check_file, "wsnark_pkey_circuit_check_file")
+    SYM(circuit_load, "wsnark_circuit_load") SYM(circuit_free, "wsnark_circuit_free") SYM(circuit_info, "wsnark_circuit_info")
+    SYM(witness_check, "wsnark_witness_check") SYM(circuit_witness_check, "wsnark_circuit_witness_check")
 #undef SYM
     return 0;
 }
@@ -158,7 +167,8 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
        OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
-       OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT };
+       OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
+       OP_CIRCUIT_WITNESS_CHECK };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -173,7 +183,8 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
 #define TAG_POINTS 0x77736e5054533031ull
 #define TAG_GROUP 0x77736e4752503031ull
 #define TAG_GKEY 0x77736e474b593031ull
-typedef struct { uint64_t tag; void* p; } handle_t;                 /* a key (wsnark_pkey_t*) or a point set (wsnark_points_t*) */
+#define TAG_CIRCUIT 0x77736e4349523031ull
+typedef struct { uint64_t tag; void* p; } handle_t;                 /* a key (wsnark_pkey_t*), a point set (wsnark_points_t*) or a resident circuit */
 typedef struct { uint64_t tag; wsnark_group_t* g; int live; int inflight; int refs; } group_ref_t;
 typedef struct { uint64_t tag; wsnark_group_pkey_t* k; group_ref_t* gr; } gkey_ref_t;
 static void* get_handle(napi_env env, napi_value v, uint64_t tag) {
@@ -211,6 +222,8 @@ typedef struct {
     gkey_ref_t* gk;
     group_ref_t* gr_used;       /* the group this job runs on (counted in its `inflight`), or NULL */
     wsnark_points_t* pts;
+    wsnark_circuit_res_t* circ;  /* OP_CIRCUIT_LOAD: the new handle; OP_CIRCUIT_WITNESS_CHECK: the one checked against */
+    uint64_t cap;               /* the witness checks: entries the two lists hold */
     uint8_t* out;
     size_t nout;
     char* path;                 /* key file (OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE): owned by the job */
@@ -285,6 +298,7 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
 #define PKEY_SETUP_REPORT_BYTES 192      /* sizeof(wsnark_pkey_setup_report_t) */
 #define POWERS_REPORT_BYTES 192          /* sizeof(wsnark_powers_report_t) */
 #define PKEY_CIRCUIT_VERDICT_BYTES 56    /* sizeof(wsnark_pkey_circuit_verdict_t) */
+#define WITNESS_REPORT_BYTES 80          /* sizeof(wsnark_witness_report_t) */
 /* wsnark_powers_t and wsnark_circuit_t (include/wsnark.h) */
 typedef struct {
     uint32_t domain;
@@ -371,6 +385,27 @@ static void job_execute(napi_env env, void* data) {
                         : L.pkey_circuit_check(j->a, j->na, &P, &K, j->b, j->nb, n_inputs, j->r32, j->out);
         break;
     }
+    case OP_CIRCUIT_LOAD: {
+        powers_t P;
+        circuit_t K;
+        job_structs(j, &P, &K);
+        j->rc = L.circuit_load(&K, &j->circ);
+        break;
+    }
+    case OP_WITNESS_CHECK:            /* out = the report (80 B), cap x u64 row indices, cap x 96 B values */
+    case OP_CIRCUIT_WITNESS_CHECK: {
+        uint64_t* rows = j->cap ? (uint64_t*)(j->out + WITNESS_REPORT_BYTES) : NULL;
+        uint8_t* vals = j->cap ? j->out + WITNESS_REPORT_BYTES + 8 * j->cap : NULL;
+        if (j->op == OP_WITNESS_CHECK) {
+            powers_t P;
+            circuit_t K;
+            job_structs(j, &P, &K);
+            j->rc = L.witness_check(&K, j->a, j->na, rows, vals, j->cap, j->out);
+        } else {
+            j->rc = L.circuit_witness_check(j->circ, j->a, j->na, rows, vals, j->cap, j->out);
+        }
+        break;
+    }
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
     case OP_GROUP_G1: j->rc = L.group_g1_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
     case OP_GROUP_G2: j->rc = L.group_g2_msm(j->gr->g, j->a, j->b, j->na / 32, j->out); break;
@@ -415,6 +450,11 @@ static void points_finalize(napi_env env, void* data, void* hint) {
     handle_t* h = (handle_t*)data;
     if (h) { if (h->p) L.points_free((wsnark_points_t*)h->p); h->tag = 0; free(h); }
 }
+static void circuit_finalize(napi_env env, void* data, void* hint) {
+    (void)env; (void)hint;
+    handle_t* h = (handle_t*)data;
+    if (h) { if (h->p) L.circuit_free((wsnark_circuit_res_t*)h->p); h->tag = 0; free(h); }
+}
 static void gkey_finalize(napi_env env, void* data, void* hint) {
     (void)env; (void)hint;
     gkey_ref_t* gk = (gkey_ref_t*)data;
@@ -447,6 +487,18 @@ static void job_complete(napi_env env, napi_status status, void* data) {
     } else if (j->op == OP_POINTS_LOAD) {
         napi_create_external(env, new_handle(TAG_POINTS, j->pts), points_finalize, NULL, &res);
         napi_resolve_deferred(env, j->deferred, res);
+    } else if (j->op == OP_CIRCUIT_LOAD) {
+        handle_t* h = new_handle(TAG_CIRCUIT, j->circ);
+        if (!h || napi_create_external(env, h, circuit_finalize, NULL, &res) != napi_ok) {      /* nothing would ever free the matrices */
+            napi_value msg, e;
+            L.circuit_free(j->circ);
+            free(h);
+            napi_create_string_utf8(env, "wsnark_napi: out of memory for the circuit handle", NAPI_AUTO_LENGTH, &msg);
+            napi_create_error(env, NULL, msg, &e);
+            napi_reject_deferred(env, j->deferred, e);
+        } else {
+            napi_resolve_deferred(env, j->deferred, res);
+        }
     } else if (j->op == OP_VERIFY) {
         napi_get_boolean(env, j->i0 != 0, &res);
         napi_resolve_deferred(env, j->deferred, res);
@@ -796,6 +848,91 @@ static napi_value js_check_key_circuit(napi_env env, napi_callback_info info) {
     if (j->b) keep(env, j, argv[5]);
     if (j->r32) keep(env, j, argv[6]);
     return start_job(env, j, "wsnark_pkey_circuit_check");
+}
+
+/* ---- a witness against its circuit (include/wsnark.h: wsnark_circuit_load, wsnark_witness_check, wsnark_circuit_witness_check) ----
+ * the circuit's (nVars, nPublic, domain, [polsA, polsB, polsC]) into u0, u1, u2 and in[5..7], where job_structs reads them */
+static int circuit_args(napi_env env, job_t* j, napi_value* argv) {
+    napi_value el;
+    bool is = false;
+    if (napi_get_value_uint32(env, argv[0], &j->u0) != napi_ok || napi_get_value_uint32(env, argv[1], &j->u1) != napi_ok ||
+        napi_get_value_uint32(env, argv[2], &j->u2) != napi_ok || napi_is_array(env, argv[3], &is) != napi_ok || !is)
+        return 0;
+    for (uint32_t k = 0; k < 3; k++)
+        if (napi_get_element(env, argv[3], k, &el) != napi_ok || !get_bytes(env, el, &j->in[5 + k], &j->nin[5 + k])) return 0;
+    return 1;
+}
+/* the report and the two lists of `cap` entries behind it; 0 if cap is no count in [0, 2^24] */
+static int witness_out(napi_env env, job_t* j, napi_value cap) {
+    uint32_t n = 0;
+    if (napi_get_value_uint32(env, cap, &n) != napi_ok || n > (1u << 24)) return 0;
+    j->cap = n;
+    j->nout = WITNESS_REPORT_BYTES + (size_t)n * (8 + 96);
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    return j->out != NULL;
+}
+/* loadCircuit(nVars, nPublic, domain, [polsA, polsB, polsC]) -> Promise<handle> */
+static napi_value js_circuit_load(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CIRCUIT_LOAD;
+    if (argc < 4 || !circuit_args(env, j, argv)) FAIL(env, j, "expected (nVars, nPublic, domain, [polsA, polsB, polsC])");
+    keep(env, j, argv[3]);      /* the array keeps its three buffers alive */
+    return start_job(env, j, "wsnark_circuit_load");
+}
+/* circuitInfo(handle) -> {nVars, nPublic, domain, nnz: [A, B, C], bytes} */
+static napi_value js_circuit_info(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1], o, v, a;
+    wsnark_circuit_res_t* c = NULL;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1 || !(c = (wsnark_circuit_res_t*)get_plain(env, argv[0], TAG_CIRCUIT))) { napi_throw_type_error(env, NULL, "expected a circuit handle"); return NULL; }
+    uint32_t nv = 0, np = 0, dom = 0;
+    uint64_t nnz[3] = {0, 0, 0}, bytes = 0;
+    L.circuit_info(c, &nv, &np, &dom, nnz, &bytes);
+    napi_create_object(env, &o);
+    napi_create_uint32(env, nv, &v); napi_set_named_property(env, o, "nVars", v);
+    napi_create_uint32(env, np, &v); napi_set_named_property(env, o, "nPublic", v);
+    napi_create_uint32(env, dom, &v); napi_set_named_property(env, o, "domain", v);
+    napi_create_array_with_length(env, 3, &a);
+    for (uint32_t k = 0; k < 3; k++) { napi_create_double(env, (double)nnz[k], &v); napi_set_element(env, a, k, v); }
+    napi_set_named_property(env, o, "nnz", a);
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "bytes", v);
+    return o;
+}
+/* circuitFree(handle): the matrices go back now instead of with the garbage collector; the handle is dead afterwards (index.js calls
+ * this only when no check on the handle is in flight) */
+static napi_value js_circuit_free(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_t* h = argc < 1 ? NULL : (handle_t*)get_handle(env, argv[0], TAG_CIRCUIT);
+    if (h && h->p) { L.circuit_free((wsnark_circuit_res_t*)h->p); h->p = NULL; }
+    return NULL;
+}
+/* circuitCheckWitness(handle, witness, cap) -> Promise<ArrayBuffer 80 + cap x 104>: the wsnark_witness_report_t, cap row indices (u64),
+ * cap x (a | b | c) */
+static napi_value js_circuit_check_witness(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CIRCUIT_WITNESS_CHECK;
+    if (argc < 3 || !(j->circ = (wsnark_circuit_res_t*)get_plain(env, argv[0], TAG_CIRCUIT)) || !get_bytes(env, argv[1], &j->a, &j->na))
+        FAIL(env, j, "expected (circuit handle, witness, maxRows)");
+    if (!witness_out(env, j, argv[2])) FAIL(env, j, "maxRows: a count of at most 2^24");
+    keep(env, j, argv[0]); keep(env, j, argv[1]);
+    return start_job(env, j, "wsnark_circuit_witness_check");
+}
+/* checkWitness(nVars, nPublic, domain, [polsA, polsB, polsC], witness, cap) -> Promise<ArrayBuffer>: the same, load and free included */
+static napi_value js_check_witness(napi_env env, napi_callback_info info) {
+    size_t argc = 6; napi_value argv[6];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_WITNESS_CHECK;
+    if (argc < 6 || !circuit_args(env, j, argv) || !get_bytes(env, argv[4], &j->a, &j->na))
+        FAIL(env, j, "expected (nVars, nPublic, domain, [polsA, polsB, polsC], witness, maxRows)");
+    if (!witness_out(env, j, argv[5])) FAIL(env, j, "maxRows: a count of at most 2^24");
+    keep(env, j, argv[3]); keep(env, j, argv[4]);
+    return start_job(env, j, "wsnark_witness_check");
 }
 
 /* mulPoints(group 1 | 2, points, scalars) -> Promise<ArrayBuffer>: scalars[i] * points[i] (wsnark_g{1,2}_mul_batch), out of place */
@@ -1191,6 +1328,11 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"contributePowers", NULL, js_contribute_powers, NULL, NULL, NULL, napi_default, NULL},
         {"checkPowers", NULL, js_check_powers, NULL, NULL, NULL, napi_default, NULL},
         {"checkKeyCircuit", NULL, js_check_key_circuit, NULL, NULL, NULL, napi_default, NULL},
+        {"loadCircuit", NULL, js_circuit_load, NULL, NULL, NULL, napi_default, NULL},
+        {"circuitInfo", NULL, js_circuit_info, NULL, NULL, NULL, napi_default, NULL},
+        {"circuitFree", NULL, js_circuit_free, NULL, NULL, NULL, napi_default, NULL},
+        {"circuitCheckWitness", NULL, js_circuit_check_witness, NULL, NULL, NULL, napi_default, NULL},
+        {"checkWitness", NULL, js_check_witness, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},
