@@ -7,6 +7,9 @@ Q = 2188824287183927522224640574525727508869631115729782366268903789464522620858
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 MONT = 1 << 256
 RINV = pow(MONT, Q - 2, Q)
+G1 = (1, 2)
+G2 = ((10857046999023057135944570762232829481370756359578518086990519993285655852781, 11559732032986387107991004021392285783925812861821192530917403151452391805634),
+      (8495653923123431417604973247489272438418190587263600148770280649306958101930, 4082367875863433681332203403145435568316851327593401208105741076214120093531))
 
 
 # ---- Fq2: pairs (c0, c1) = c0 + c1 u ----
@@ -23,7 +26,7 @@ def _f2_mul(a, b):
 
 
 def _f2_inv(a):
-    n = pow((a[0] * a[0] + a[1] * a[1]) % Q, Q - 2, Q)
+    n = pow((a[0] * a[0] + a[1] * a[1]) % Q, -1, Q)
     return (a[0] * n % Q, (-a[1]) * n % Q)
 
 
@@ -100,6 +103,23 @@ def g2_mul(pt, k):
     return times(g2_add, pt, k)
 
 
+class FixedBase:
+    """k * pt for many k: the doublings 2^i pt once, then one addition per set bit of k (the same affine additions as times)."""
+
+    def __init__(self, add, pt, bits=254):
+        self.add, self.pow2 = add, [pt]
+        for _ in range(bits - 1):
+            self.pow2.append(add(self.pow2[-1], self.pow2[-1]))
+
+    def mul(self, k):
+        assert 0 <= k < 1 << len(self.pow2)
+        acc = None
+        for i, p in enumerate(self.pow2):
+            if (k >> i) & 1:
+                acc = self.add(acc, p)
+        return acc
+
+
 def g2_times_r_is_infinity(pt):
     return g2_mul(pt, R) is None
 
@@ -121,6 +141,29 @@ def twist_point_outside_g2():
         if y is not None:
             return x, y
         k += 1
+
+
+def random_twist_point(rnd):
+    """A point of the whole twist group E'(Fq2) (order r (2q - r)) with x drawn from `rnd`; the y of the two that _f2_sqrt gives."""
+    while True:
+        x = (rnd.randrange(Q), rnd.randrange(Q))
+        y = _f2_sqrt(_f2_add(_f2_mul(_f2_mul(x, x), x), B2_TWIST))
+        if y is not None and y != (0, 0):
+            return x, y
+
+
+def twist_point_of_order(d, rnd):
+    """A twist point of exact order d, d a product of distinct primes of the cofactor 2q - r = 10069 * 5864401 * ...: the
+    multiple r (2q - r) / d of a random twist point, drawn again until no proper divisor of d kills it."""
+    n = R * (2 * Q - R)
+    assert n % d == 0
+    primes = [p for p in (10069, 5864401) if d % p == 0]
+    assert primes and d == (primes[0] if len(primes) == 1 else primes[0] * primes[1])
+    while True:
+        pt = g2_mul(random_twist_point(rnd), n // d)
+        if pt is not None and all(g2_mul(pt, d // p) is not None for p in primes):
+            assert g2_mul(pt, d) is None and g2_on_twist(*pt)
+            return pt
 
 
 # ---- integers <-> the 32-byte little-endian words of a key (Montgomery form, 2^256) ----

@@ -1,7 +1,8 @@
 """The batch verifier (wsnark_groth16_verify_batch, csrc/pairing.hip + fp12.h) on the CPU thread emulator: the kernel SOURCES
 compiled by g++ (tests/emul), every status compared with the pinned single-proof host verifier.  The checks themselves are in
 tests/verify_batch_common.py; tests/test_gpu_verify_batch.py runs them again on the device.  Batches are kept small: the
-emulator runs a wavefront's lanes one after the other (the whole file takes about 25 seconds on one core)."""
+emulator runs a wavefront's lanes one after the other (the whole file takes about a minute on one core, half of it the planted
+table of verify_batch_common.py section 7)."""
 import pytest
 
 import verify_batch_common as vb
@@ -41,3 +42,18 @@ def test_python_argument_errors(bn):
 @pytest.mark.parametrize("n_public", [1, 5])
 def test_forged_proofs_and_flipped_bits(bn, n_public):
     vb.check_forged(bn, n_public, 24)
+
+
+def test_mul_base_gives_the_reference_points(bn):
+    vb.check_mul_base_against_reference(bn)
+
+
+@pytest.mark.parametrize("what", ["rows", "alone", "host", "shuffled"])
+def test_planted_keys_inputs_and_proofs(bn, what):
+    vb.check_planted(bn, what=(what,))
+
+
+@pytest.mark.parametrize("plain", [1, 2])
+def test_planted_with_the_plain_exponents(bn, tune, plain):
+    # (each row in one call; the shuffled batches with their neighbours run under both exponents on the device, where they cost nothing)
+    vb.check_planted(bn, what=("rows",), plain=plain, tune=tune)

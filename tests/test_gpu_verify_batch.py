@@ -63,6 +63,38 @@ def test_plain_exponent_gives_the_same_statuses(bn, tune):
     split = vb.batch_status(bn.lib, F.vk_bytes(), 2, ib, tp)
     tune(bn.lib, "VERIFY_PLAIN_EXP", 1)
     assert vb.batch_status(bn.lib, F.vk_bytes(), 2, ib, tp) == split == [want.get(i, 1) for i in range(64)]
+    tune(bn.lib, "VERIFY_PLAIN_EXP", 2)         # the hard part by square-and-multiply
+    assert vb.batch_status(bn.lib, F.vk_bytes(), 2, ib, tp) == split
+
+
+def test_mul_base_gives_the_reference_points(bn):
+    vb.check_mul_base_against_reference(bn)
+
+
+@pytest.mark.parametrize("what", ["rows", "alone", "host", "shuffled"])
+def test_planted_keys_inputs_and_proofs(bn, what):
+    vb.check_planted(bn, what=(what,))
+
+
+@pytest.mark.parametrize("plain", [1, 2])
+def test_planted_with_the_plain_exponents(bn, tune, plain):
+    vb.check_planted(bn, what=("shuffled",), plain=plain, tune=tune)
+
+
+def test_planted_through_device_pointers(bn):
+    """Every key's shuffled batch again with inputs and proofs resident on the device (no inputs: a null pointer)."""
+    import torch
+    ones = 0
+    for F, mixed in vb.shuffled_key_batches():
+        vkb, n = F.vk_bytes(), len(mixed)
+        d_pr = torch.frombuffer(bytearray(b"".join(c["proof"] for c in mixed)), dtype=torch.uint8).cuda()
+        d_in = torch.frombuffer(bytearray(b"".join(vb._inputs_bytes(c["x"]) for c in mixed)), dtype=torch.uint8).cuda() if F.n_public else None
+        torch.cuda.synchronize()
+        st = (C.c_uint8 * n)(*([7] * n))
+        bn.lib.check(bn.lib.c.wsnark_groth16_verify_batch_dev(vkb, len(vkb), d_in.data_ptr() if F.n_public else None, F.n_public, d_pr.data_ptr(), n, st, None))
+        assert list(st) == [c["want"] for c in mixed], [(c["label"], g) for c, g in zip(mixed, st) if g != c["want"]]
+        ones += sum(st)
+    assert ones == vb.PLANTED_VALID + 3 * vb.PLANTED_SOUND_KEYS
 
 
 @pytest.fixture(scope="module")

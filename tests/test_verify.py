@@ -101,3 +101,10 @@ def test_input_count_cannot_wrap_the_size_check(lib):
     for n_inputs in (1 << 58, (1 << 58) - 1, (1 << 64) - 1, 2):
         rc = lib.c.wsnark_groth16_verify(vkb, len(vkb), bytes(64), C.c_uint64(n_inputs), bytes(384), C.byref(valid))
         assert rc == 1 and valid.value == 0, n_inputs      # WSNARK_ERR_SIZE, nothing read past the key
+
+
+def test_planted_keys_inputs_and_proofs(lib):
+    """The planted table of verify_batch_common.py (section 7) through wsnark_groth16_verify alone: IC sums that double, cancel
+    and pass through infinity, key points at infinity, B equal to a key point; every status is the table's integer predicate."""
+    import verify_batch_common as vb
+    vb.check_planted_host(lib)
