@@ -635,6 +635,50 @@ int wsnark_groth16_verify_batch(const void* vk, size_t vk_len, const void* input
 int wsnark_groth16_verify_batch_dev(const void* vk, size_t vk_len, const void* d_inputs, uint64_t n_inputs, const void* d_proofs384,
                                     uint64_t count, uint8_t* status_host, void* stream);
 
+/* ---- many witnesses of ONE key in one call (csrc/provebatch.hip): NO reference counterpart ----
+ * The reference's groth16GenProof takes one witness (src/bn128.js:580-720); a proving service holds one small circuit (2^10 .. 2^16
+ * constraints) and many witnesses, and a single proof of that size leaves most of the device idle.
+ * THE CONTRACT: out384s[i] (count x 384 bytes) is byte for byte what wsnark_groth16_prove(handle, witness_i, nVars*32, r_i, s_i, out)
+ * writes.  Every rule of the single call holds per proof: witness values are raw 256-bit and may be >= r; the key's points at
+ * infinity (x == 0) are honoured; infinity prints as (0, 1, 0).
+ *   witnesses      witness i starts at witnesses + i * witness_stride; only its first nVars signals are read.  witness_stride <
+ *                  nVars*32 is WSNARK_ERR_SIZE.  _dev: memory of the handle's device, pointer and stride multiples of 16, ready on
+ *                  `stream` (NULL: the lane's own queue)
+ *   r32s, s32s     count x 32 bytes each, HOST memory in both variants; either may be NULL: its values are then drawn from the OS
+ *                  CSPRNG, one independent draw per proof
+ *   out_rs64s      (may be NULL) count x 64 bytes, host: r_i | s_i as used -- the batch's counterpart of wsnark_last_blinding
+ *   rep            (may be NULL) see below
+ * count == 0 is WSNARK_OK and touches nothing; count > 2^16 is WSNARK_ERR_SIZE; a NULL handle, witnesses or out is
+ * WSNARK_ERR_ARG, as is a handle that holds a points shard or an interleaved hExps slice (whole keys only, no group handles);
+ * WSNARK_ERR_NOINIT before wsnark_init.  On every error the outputs and the report are left untouched.
+ * The batch path: per pass of `chunk` proofs (as many as keep the pass's scratch under a fixed budget; switch BATCH_CHUNK) one
+ * upload, a = A.w and b = B.w of all proofs in one launch, CALC_H over the stack of proofs, the five sums of every proof against
+ * row 0 of the key's resident sections (one workgroup per (proof, sum, window), windows of BATCH_WINDOW bits in [4, 8], default 8),
+ * the proof assembly on the device, one download of chunk x 384 bytes.  r, s and rs cross to the device in a buffer that is
+ * overwritten on the call's queue before the call returns, on every exit path.  It does not wait for the key's table build.
+ * Routing: a key whose domain is above BATCH_MAX_DOMAIN (at most 2^16), or a call with fewer than BATCH_MIN proofs, loops the single
+ * prover instead -- same contract, same outputs, report.batched = 0.  The switches are read per call (wsnark_tuning_set /
+ * WSNARK_<name>), so one process can run both paths.
+ * wsnark_last_blinding: the batch kernels leave the calling thread's record alone; the loop over the single prover overwrites it with
+ * the last proof's r | s, as that prover always does.  Callers of this entry point read out_rs64s, which is the same on both routes.
+ * _dev and the stride: every witness is read as 16-byte aligned field elements (the single prover's contract for a device witness,
+ * which the loop route hands witness i to as it is), hence pointer AND stride are multiples of 16.
+ * Memory: a pass's scratch (at most 2 GiB) belongs to the lane the call held and is kept, grow-only, until the context goes.
+ * Each call takes one lane of the key's context; two threads may run batches on one handle at once. */
+typedef struct {
+    uint64_t count;        /* proofs asked for */
+    uint64_t batched;      /* proofs that went through the batch kernels (0: the call looped the single prover) */
+    uint32_t chunk;        /* proofs per pass over the kernels */
+    uint32_t window_bits;  /* of the batch sums */
+    double   ms[5];        /* upload, CALC_H, the five sums, assembly (device time, summed over the passes); whole call (host clock) */
+} wsnark_prove_batch_report_t;
+int wsnark_groth16_prove_batch(wsnark_pkey_t* handle, const void* witnesses, size_t witness_stride, uint64_t count,
+                               const void* r32s, const void* s32s, void* out384s, void* out_rs64s,
+                               wsnark_prove_batch_report_t* rep);
+int wsnark_groth16_prove_batch_dev(wsnark_pkey_t* handle, const void* d_witnesses, size_t witness_stride, uint64_t count,
+                                   const void* r32s, const void* s32s, void* out384s_host, void* out_rs64s_host,
+                                   wsnark_prove_batch_report_t* rep, void* stream);
+
 /* The two 32-byte blinding values of the last proof assembled by the CALLING THREAD (wsnark_groth16_prove[_dev] or
  * _prove_finish), whether injected or drawn from the OS CSPRNG: the reference keeps them the same way, "for tests",
  * as this._pr / this._ps (src/bn128.js:662-664).  WSNARK_ERR_ARG if this thread has not proved yet. */

@@ -258,6 +258,37 @@ def _witness_lists(max_rows):
     return cap, ((C.c_uint64 * cap)() if cap else None), ((C.c_uint8 * (96 * cap))() if cap else None)
 
 
+class _ProveBatchReport(C.Structure):  # wsnark_prove_batch_report_t
+    _fields_ = [("count", C.c_uint64), ("batched", C.c_uint64), ("chunk", C.c_uint32), ("window_bits", C.c_uint32), ("ms", C.c_double * 5)]
+
+
+def _prove_batch_report_dict(r):
+    return {"count": int(r.count), "batched": int(r.batched), "chunk": int(r.chunk), "window_bits": int(r.window_bits),
+            "ms": {"upload": r.ms[0], "calc_h": r.ms[1], "sums": r.ms[2], "assembly": r.ms[3], "total": r.ms[4]}}
+
+
+def _blinding_array(v, count, name):
+    """None, count x 32 bytes, or a sequence of count 32-byte values -> what the C call takes (None: drawn per proof)"""
+    if v is None:
+        return None
+    b = bytes(v) if isinstance(v, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in v)
+    if len(b) != 32 * count or (not isinstance(v, (bytes, bytearray, memoryview)) and any(len(x) != 32 for x in v)):
+        raise ValueError("%s: one 32-byte value per proof" % name)
+    return b
+
+
+def _prove_batch_result(out, rs, count, rep, return_blinding, report):
+    if report is not None:
+        report.clear()
+        report.update(_prove_batch_report_dict(rep))
+    b = bytes(out)
+    proofs = [proof_from_bytes(b[384 * i:384 * i + 384]) for i in range(count)]
+    if not return_blinding:
+        return proofs
+    rsb = bytes(rs)
+    return proofs, [(rsb[64 * i:64 * i + 32], rsb[64 * i + 32:64 * i + 64]) for i in range(count)]
+
+
 class ResidentCircuit:
     """A circuit's three matrices resident on the device as row-major CSR (wsnark_circuit_load): witnesses are checked against it
     without transposing the record streams again.  Read-only after the load: threads may share one."""
@@ -637,6 +668,49 @@ class Bn128:
         sb = _ro(s)[0] if s is not None else None
         self.lib.check(self.lib.c.wsnark_groth16_prove_dev(key._h, d_witness, witness_len, rb, sb, out, stream))
         return proof_from_bytes(bytes(out))
+
+    # --- many witnesses of one key (wsnark_groth16_prove_batch; no reference counterpart) ---
+    def groth16GenProofBatch(self, witnesses, key, r=None, s=None, return_blinding=False, report=None):
+        """witnesses: a sequence of witness.bin byte strings (each at least nVars x 32 bytes), or ONE bytes-like object holding them
+        back to back, nVars x 32 bytes each; key: proving_key.bin bytes or a ProvingKey (a whole key).
+        r, s: None (drawn from the OS, one independent draw per proof) or one 32-byte value per proof (a sequence, or the
+        values back to back).  Returns the list of proofs, proof i being what groth16GenProof(witnesses[i], key, r[i], s[i])
+        returns; with return_blinding also the list of (r, s) as used.  report: a dict that receives the call's report
+        (count, batched -- 0 when the call looped the single prover --, chunk, window_bits, ms)."""
+        pk = key if isinstance(key, ProvingKey) else ProvingKey(self.lib, key)
+        try:
+            stride = 32 * pk.n_vars
+            if isinstance(witnesses, (bytes, bytearray, memoryview)):
+                blob = witnesses
+                if stride == 0 or len(blob) % stride:
+                    raise ValueError("witnesses: not a whole number of nVars x 32-byte witnesses")
+                count = len(blob) // stride
+            else:
+                ws = [bytes(w) for w in witnesses]
+                count = len(ws)
+                if any(len(w) < stride for w in ws):
+                    raise ValueError("a witness is shorter than nVars x 32 bytes")
+                blob = b"".join(w[:stride] for w in ws)
+            rb, sb = _blinding_array(r, count, "r"), _blinding_array(s, count, "s")
+            if count == 0:
+                return ([], []) if return_blinding else []
+            out, rs, rep = (C.c_uint8 * (384 * count))(), (C.c_uint8 * (64 * count))(), _ProveBatchReport()
+            self.lib.check(self.lib.c.wsnark_groth16_prove_batch(pk._h, _ro(blob)[0], stride, count, rb, sb, out, rs, C.byref(rep)))
+            return _prove_batch_result(out, rs, count, rep, return_blinding, report)
+        finally:
+            if pk is not key:
+                pk.free()
+
+    def groth16GenProofBatch_dev(self, d_witnesses, witness_stride, count, key, r=None, s=None, return_blinding=False, report=None, stream=None):
+        """The same for witnesses already on the key's device: d_witnesses is a raw device address (16-byte aligned), witness i
+        starts witness_stride bytes (a multiple of 16, at least nVars x 32) after witness i - 1; stream: the queue they are ready on."""
+        count = int(count)
+        rb, sb = _blinding_array(r, count, "r"), _blinding_array(s, count, "s")
+        if count == 0:
+            return ([], []) if return_blinding else []
+        out, rs, rep = (C.c_uint8 * (384 * count))(), (C.c_uint8 * (64 * count))(), _ProveBatchReport()
+        self.lib.check(self.lib.c.wsnark_groth16_prove_batch_dev(key._h, d_witnesses, witness_stride, count, rb, sb, out, rs, C.byref(rep), stream))
+        return _prove_batch_result(out, rs, count, rep, return_blinding, report)
 
     # --- src/bn128.js:569-578 (worker CALC_H :126-166) ---
     def calcH(self, signals, polsA, polsB, nSignals, domainSize):

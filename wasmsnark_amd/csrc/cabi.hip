@@ -17,6 +17,7 @@ static_assert(sizeof(wsnark_pkey_setup_report_t) == 192, "the bindings read this
 static_assert(sizeof(wsnark_powers_report_t) == 192, "the bindings read this by offset");
 static_assert(sizeof(wsnark_pkey_circuit_verdict_t) == 56, "the bindings read this by offset");
 static_assert(sizeof(wsnark_witness_report_t) == 80, "the bindings read this by offset");
+static_assert(sizeof(wsnark_prove_batch_report_t) == 64, "the bindings read this by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
 // addon runs on the libuv pool): select the context's device first.
@@ -275,6 +276,22 @@ int wsnark_groth16_prove_dev(wsnark_pkey_t* h, const void* d_witness, size_t wit
     if (!h || !d_witness || !out384_host) return WSNARK_ERR_ARG;
     return groth16_prove_dev_witness(reinterpret_cast<ProvingKey*>(h), (const Fe*)d_witness, witness_len,
                                      (const uint8_t*)r32, (const uint8_t*)s32, (uint8_t*)out384_host, (hipStream_t)stream);
+}
+
+// many witnesses of one key (provebatch.hip).  Before wsnark_init no handle can exist: that is said first
+int wsnark_groth16_prove_batch(wsnark_pkey_t* h, const void* witnesses, size_t witness_stride, uint64_t count, const void* r32s,
+                               const void* s32s, void* out384s, void* out_rs64s, wsnark_prove_batch_report_t* rep) {
+    if (!ctx()) { set_last_error("wsnark_init() has not been called"); return WSNARK_ERR_NOINIT; }
+    REQUIRE_KEY_CTX(h);
+    return groth16_prove_batch(reinterpret_cast<ProvingKey*>(h), witnesses, witness_stride, count, false, (const uint8_t*)r32s,
+                               (const uint8_t*)s32s, (uint8_t*)out384s, (uint8_t*)out_rs64s, rep, nullptr);
+}
+int wsnark_groth16_prove_batch_dev(wsnark_pkey_t* h, const void* d_witnesses, size_t witness_stride, uint64_t count, const void* r32s,
+                                   const void* s32s, void* out384s_host, void* out_rs64s_host, wsnark_prove_batch_report_t* rep, void* stream) {
+    if (!ctx()) { set_last_error("wsnark_init() has not been called"); return WSNARK_ERR_NOINIT; }
+    REQUIRE_KEY_CTX(h);
+    return groth16_prove_batch(reinterpret_cast<ProvingKey*>(h), d_witnesses, witness_stride, count, true, (const uint8_t*)r32s,
+                               (const uint8_t*)s32s, (uint8_t*)out384s_host, (uint8_t*)out_rs64s_host, rep, (hipStream_t)stream);
 }
 
 int wsnark_pkey_load_sections(const wsnark_key_sections_t* ks, wsnark_pkey_t** out_handle) {

@@ -221,6 +221,7 @@ void context_destroy(Context* C) {
         L.host_in[0].release(); L.host_in[1].release();
         L.witness.release(); L.h.release();
         L.verify_ws.release();
+        L.batch_ws.release();
         (void)hipStreamDestroy(L.stream);
         (void)hipStreamDestroy(L.stream2);
         (void)hipStreamDestroy(L.stream3);

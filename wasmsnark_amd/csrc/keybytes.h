@@ -264,6 +264,9 @@ int witness_check(const wsnark_circuit_t* K, const void* witness, size_t witness
 // base + i; the G2 one with the order-r subgroup test (PKCHECK_SUBGROUP picks its form), d_K: the pairing constants on the device
 int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s);
 int pkcheck_g2_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, const PairConsts* d_K, PkAcc* d_acc, hipStream_t s);
+// many witnesses of one resident key in one call (provebatch.hip); witnesses / outputs as include/wsnark.h: wsnark_groth16_prove_batch
+int groth16_prove_batch(ProvingKey* K, const void* witnesses, size_t witness_stride, uint64_t count, bool on_device, const uint8_t* r32s,
+                        const uint8_t* s32s, uint8_t* out384s, uint8_t* out_rs64s, wsnark_prove_batch_report_t* rep, hipStream_t stream);
 // powers of tau (pwtau.hip): a scalar per point, the phase-1 contribution, the transcript's audit
 int g1_mul_batch(const void* points, const void* scalars, uint64_t n, void* out);
 int g2_mul_batch(const void* points, const void* scalars, uint64_t n, void* out);

@@ -24,49 +24,7 @@
 
 namespace wsnark {
 
-struct ProvingKey {
-    Context* owner = nullptr;      // the context (device) the key is resident on: every call on the handle runs there
-    uint32_t n_vars = 0, n_public = 0, domain = 0;
-    Affine<Fq> alfa1, beta1, delta1;
-    Affine<Fq2> beta2, delta2;
-    CsrMatrix polsA, polsB;
-    DevBuf pointsA, pointsB1, pointsB2, pointsC, pointsH;
-    DevBuf maskA, maskB;        // 1 byte per signal: 0 where A (resp. B1 and B2) is infinity: the variable is not in that matrix
-    uint32_t infA = 0, infB = 0;   // how many of those there are
-    bool sparseA = false, sparseB = false;   // enough of them to give those sums a plan variant that leaves them out
-    // Fixed-base window tables: the key's points never change, so each section is kept as rows x n points, row w =
-    // 2^(c w) * (the section) -- 13 rows at c = 20 for 2^20 pairs, 5.2 GB for the five sections.  Every window of a scalar
-    // then adds into ONE bucket set: fewer, wider windows (13 instead of 16 passes over the points at 2^20), one
-    // reduction tail per sum instead of one per window, no doubling chain on the host.  0 = plain sections.
-    uint32_t table_cw = 0, table_ch = 0;     // window width of the A/B1/B2/C tables (n_local pairs) and of the H table (h_local pairs)
-    // Points shard (multi-GPU, SURVEY.md section 8e split (i) = the reference's own worker split, src/bn128.js:353-361):
-    // this handle holds the points of signals [lo, lo + n_local) of every section and h_local of the hExps -- 1/world
-    // of the memory and of the additions, all table rows, uniform work whatever the window count.  world 1 = whole key.
-    // The hExps slice is the contiguous range [hlo, hlo + h_local) (h computed in full on this rank), or -- h_log_m != 0
-    // -- the rank's rows of the m-interleaved layout the distributed CALC_H leaves its slice of h in (element (row r, j)
-    // = hExps[(rank*m/world + r) + m*j]).  The two sparse matrices are always complete (CALC_H needs every row).
-    uint32_t shard_rank = 0, shard_world = 1;
-    uint32_t lo = 0, n_local = 0, hlo = 0, h_local = 0, h_log_m = 0;
-    // wall-clock of the load, by phase (ms): pols -> CSR, point sections host -> device, masks + conversion to the device
-    // field's domain, fixed-base table build, whole call (what a cold caller pays before its first proof)
-    double load_ms[5] = {0, 0, 0, 0, 0};
-    // Round 4: the table rows 1.. are built IN THE BACKGROUND (the context's queue `build_q`): the load returns once the sections are resident
-    // and converted (row 0 of every table = the plain section), proofs that arrive before `ev_tables` has fired run on the
-    // plain sections (per-window plans: the round-1 / 2 path; 10 % slower by itself, about twice the time beside the build), later ones on the tables.  `tables_ready` only ever
-    // goes 0 -> 1.  WSNARK_TABLE_ASYNC=0: the load waits for the build as in round 3.
-    hipEvent_t ev_build0 = nullptr, ev_tables = nullptr;      // (timing events: their distance is the build's duration)
-    // 1 = rows built (or no tables at all), 0 = build queued, `ev_tables` recorded behind it, -1 = the build could not be queued
-    // (plain sections for good)
-    std::atomic<int> tables_ready{1};
-    // Otherwise read-only after load: any number of proofs may use one handle at once (each on its own lane, which holds the
-    // per-proof buffers and events).
-    ~ProvingKey() {
-        // the build writes this key's buffers: it must be over before they go (the queue is the context's; the event is this key's build)
-        if (ev_tables && tables_ready.load() == 0 && hipEventSynchronize(ev_tables) != hipSuccess) (void)hipGetLastError();
-        if (ev_build0) (void)hipEventDestroy(ev_build0);
-        if (ev_tables) (void)hipEventDestroy(ev_tables);
-    }
-};
+// (struct ProvingKey: internal.h -- provebatch.hip reads the same resident key)
 
 // which window width a call that starts NOW may plan with: the tables' once they are built (wait = block until they are: calls
 // whose partial results must mean the same on every rank), 0 = the plain sections

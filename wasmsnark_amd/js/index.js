@@ -528,6 +528,63 @@ class Bn128 {
         }
         return proof;
     }
+    /* Many witnesses of ONE key in one call (wsnark_groth16_prove_batch; no reference counterpart).  witnesses: an array of witness
+     * buffers (each at least nVars x 32 bytes), or ONE buffer holding them back to back, nVars x 32 bytes each; pkey: key bytes, a
+     * handle or a key file, as groth16GenProof takes them (a whole key on one device: not with {devices}).  opts.r / opts.s: one
+     * 32-byte value per proof (an array, or the values back to back); absent: drawn per proof.  Resolves to the array of proofs,
+     * proof i being what groth16GenProof(witnesses[i], pkey, {r: r[i], s: s[i]}) resolves to.  opts.blinding (an array) receives
+     * {r, s} of every proof as used, opts.report (an object) the call's report: count, batched (0: the call looped the single
+     * prover), chunk, windowBits, ms. */
+    async groth16GenProofBatch(witnesses, pkey, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: groth16GenProofBatch needs a whole key on one device (not buildBn128({devices}))");
+        const h = await this.loadKey(pkey, opts);
+        const stride = 32 * addon.keyInfo(h).nVars;
+        let blob, count;
+        if (Array.isArray(witnesses)) {
+            const ws = witnesses.map(asBytes);
+            if (ws.some((w) => w.byteLength < stride)) throw new Error("wsnark: a witness is shorter than nVars x 32 bytes");
+            count = ws.length;
+            blob = new Uint8Array(stride * count);
+            ws.forEach((w, i) => blob.set(w.subarray(0, stride), stride * i));
+        } else {
+            blob = asBytes(witnesses);
+            if (stride === 0 || blob.byteLength % stride) throw new Error("wsnark: not a whole number of nVars x 32-byte witnesses");
+            count = blob.byteLength / stride;
+        }
+        const values = (v, name) => {
+            if (v === undefined || v === null) return null;
+            const parts = Array.isArray(v) ? v.map(asBytes) : [asBytes(v)];
+            const out = new Uint8Array(32 * count);
+            let off = 0;
+            for (const p of parts) {
+                if ((Array.isArray(v) && p.byteLength !== 32) || off + p.byteLength > out.byteLength) throw new Error("wsnark: " + name + ": one 32-byte value per proof");
+                out.set(p, off);
+                off += p.byteLength;
+            }
+            if (off !== out.byteLength) throw new Error("wsnark: " + name + ": one 32-byte value per proof");
+            return out;
+        };
+        const r = values(opts && opts.r, "r"), s = values(opts && opts.s, "s");
+        if (count === 0) return [];
+        const out = await addon.proveBatch(h, blob, count, r, s);
+        if (opts && Array.isArray(opts.blinding)) {
+            opts.blinding.length = 0;
+            for (let i = 0; i < count; i++) {
+                const o = 384 * count + 64 * i;
+                opts.blinding.push({ r: new Uint8Array(out.slice(o, o + 32)), s: new Uint8Array(out.slice(o + 32, o + 64)) });
+            }
+        }
+        if (opts && opts.report && typeof opts.report === "object") {
+            const dv = new DataView(out, 448 * count, 64);
+            const ms = [0, 1, 2, 3, 4].map((k) => dv.getFloat64(24 + 8 * k, true));
+            Object.assign(opts.report, { count: Number(dv.getBigUint64(0, true)), batched: Number(dv.getBigUint64(8, true)), chunk: dv.getUint32(16, true),
+                windowBits: dv.getUint32(20, true), ms: { upload: ms[0], calcH: ms[1], sums: ms[2], assembly: ms[3], total: ms[4] } });
+        }
+        const proofs = [];
+        for (let i = 0; i < count; i++) proofs.push(proofFromBytes(out.slice(384 * i, 384 * i + 384)));
+        return proofs;
+    }
     /* src/bn128.js:722-791: verificationKey = snarkjs "groth" verification_key.json object, input = public signals
      * (one value is wrapped like the reference does), proof = {pi_a, pi_b, pi_c}.  Native host arithmetic, no GPU. */
     async groth16Verify(verificationKey, input, proof) {
@@ -616,6 +673,16 @@ function groth16GenProof(witness, provingKey, cb) {   // main_bn128.js:26-39
     return p;
 }
 
+function groth16GenProofBatch(witnesses, provingKey, opts, cb) {
+    if (typeof opts === "function") { cb = opts; opts = undefined; }
+    const p = (async () => {
+        if (!singleton) singleton = await buildBn128();
+        return singleton.groth16GenProofBatch(witnesses, provingKey, opts);
+    })();
+    if (cb) { p.then((proofs) => cb(null, proofs), (err) => cb(err)); return undefined; }
+    return p;
+}
+
 function groth16Verify(verificationKey, input, proof, cb) {   // main_bn128.js:41-55
     const p = (async () => {
         if (!singleton) singleton = await buildBn128();
@@ -635,6 +702,6 @@ function groth16VerifyBatch(verificationKey, inputs, proofs, cb) {
 }
 
 const formats = require("./formats.js");     // snarkjs JSON -> proving_key.bin / witness.bin (reference tools/build*.js)
-module.exports = { buildBn128, groth16GenProof, genZKSnarkProof: groth16GenProof, groth16Verify, groth16VerifyBatch, terminate, Bn128, proofFromBytes,
+module.exports = { buildBn128, groth16GenProof, groth16GenProofBatch, genZKSnarkProof: groth16GenProof, groth16Verify, groth16VerifyBatch, terminate, Bn128, proofFromBytes,
     pkeyJsonToBin: formats.pkeyJsonToBin, witnessJsonToBin: formats.witnessJsonToBin,
     pkeyBinSections: formats.pkeyBinSections, writeKeyContainer: formats.writeKeyContainer, pkeyBinToContainer: formats.pkeyBinToContainer };

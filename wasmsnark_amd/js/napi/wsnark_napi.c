@@ -38,6 +38,7 @@ static struct {
     void (*pkey_free)(wsnark_pkey_t*);
     int (*pkey_info)(const wsnark_pkey_t*, uint32_t*, uint32_t*, uint32_t*);
     int (*prove)(wsnark_pkey_t*, const void*, size_t, const void*, const void*, void*);
+    int (*prove_batch)(wsnark_pkey_t*, const void*, size_t, uint64_t, const void*, const void*, void*, void*, void*);
     int (*last_blinding)(void*, void*);
     int (*verify)(const void*, size_t, const void*, uint64_t, const void*, int*);
     int (*verify_batch)(const void*, size_t, const void*, uint64_t, const void*, uint64_t, uint8_t*);
@@ -122,7 +123,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(fr_ntt, "wsnark_fr_ntt") SYM(calc_h, "wsnark_calc_h") SYM(pkey_load, "wsnark_pkey_load")
     SYM(pkey_free, "wsnark_pkey_free") SYM(pkey_info, "wsnark_pkey_info") SYM(prove, "wsnark_groth16_prove")
     SYM(last_blinding, "wsnark_last_blinding") SYM(verify, "wsnark_groth16_verify")
-    SYM(verify_batch, "wsnark_groth16_verify_batch")
+    SYM(verify_batch, "wsnark_groth16_verify_batch") SYM(prove_batch, "wsnark_groth16_prove_batch")
     SYM(host_alloc, "wsnark_host_alloc") SYM(host_free, "wsnark_host_free")
     SYM(pkey_load_stats, "wsnark_pkey_load_stats") SYM(pkey_wait_tables, "wsnark_pkey_wait_tables")
     SYM(points_load, "wsnark_points_load") SYM(points_free, "wsnark_points_free") SYM(points_info, "wsnark_points_info") SYM(points_msm, "wsnark_points_msm")
@@ -168,7 +169,7 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
        OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
        OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
-       OP_CIRCUIT_WITNESS_CHECK };
+       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -335,6 +336,11 @@ static void job_execute(napi_env env, void* data) {
         j->rc = L.prove(j->key, j->a, j->na, j->r32, j->s32, j->out);
         if (!j->rc) j->rc = L.last_blinding(j->out + 384, j->out + 416);
         break;
+    case OP_PROVE_BATCH: {   /* out = count proofs (384 B each) | count x (r | s) as used | the report (64 B) */
+        const size_t n = j->u0;
+        j->rc = L.prove_batch(j->key, j->a, j->na / n, n, j->r32, j->s32, j->out, j->out + 384 * n, j->out + 448 * n);
+        break;
+    }
     case OP_LOADKEY: j->rc = L.pkey_load(j->a, j->na, &j->key); break;
     case OP_LOADKEY_FILE: j->rc = L.pkey_load_file(j->path, 0, 1, 0, &j->key); break;
     case OP_GROUP_LOADKEY_FILE: j->rc = L.group_pkey_load_file(j->gr->g, j->path, &j->gk->k); break;
@@ -680,6 +686,35 @@ static napi_value js_prove(napi_env env, napi_callback_info info) {
         keep(env, j, argv[3]);
     }
     return start_job(env, j, "wsnark_groth16_prove");
+}
+
+/* proveBatch(keyHandle, witnesses (count witnesses back to back, equal lengths), count, r32s|null, s32s|null) ->
+ * Promise<ArrayBuffer count x 448 + 64>: the proofs (384 B each), then r | s of every proof as used, then wsnark_prove_batch_report_t
+ * (include/wsnark.h, wsnark_groth16_prove_batch) */
+#define PROVE_BATCH_REPORT_BYTES 64
+static napi_value js_prove_batch(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_PROVE_BATCH;
+    if (argc < 3 || !(j->key = (wsnark_pkey_t*)get_plain(env, argv[0], TAG_KEY)) || !get_bytes(env, argv[1], &j->a, &j->na) ||
+        napi_get_value_uint32(env, argv[2], &j->u0) != napi_ok || j->u0 == 0 || j->u0 > (1u << 16) || j->na % j->u0)
+        FAIL(env, j, "expected (keyHandle, witnesses (count x bytes), count in [1, 2^16][, r32s, s32s])");
+    keep(env, j, argv[0]); keep(env, j, argv[1]);
+    size_t n;
+    napi_valuetype t;
+    if (argc > 3 && napi_typeof(env, argv[3], &t) == napi_ok && t != napi_null && t != napi_undefined) {
+        if (!get_bytes(env, argv[3], &j->r32, &n) || n != 32 * (size_t)j->u0) FAIL(env, j, "r: 32 bytes per proof");
+        keep(env, j, argv[3]);
+    }
+    if (argc > 4 && napi_typeof(env, argv[4], &t) == napi_ok && t != napi_null && t != napi_undefined) {
+        if (!get_bytes(env, argv[4], &j->s32, &n) || n != 32 * (size_t)j->u0) FAIL(env, j, "s: 32 bytes per proof");
+        keep(env, j, argv[4]);
+    }
+    j->nout = 448 * (size_t)j->u0 + PROVE_BATCH_REPORT_BYTES;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    return start_job(env, j, "wsnark_groth16_prove_batch");
 }
 
 /* verify(vkBytes, inputBytes, proof384) -> Promise<boolean>   (layouts: include/wsnark.h, wsnark_groth16_verify) */
@@ -1319,6 +1354,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"waitTables", NULL, js_wait_tables, NULL, NULL, NULL, napi_default, NULL},
         {"verify", NULL, js_verify, NULL, NULL, NULL, napi_default, NULL},
         {"verifyBatch", NULL, js_verify_batch, NULL, NULL, NULL, napi_default, NULL},
+        {"proveBatch", NULL, js_prove_batch, NULL, NULL, NULL, napi_default, NULL},
         {"checkKey", NULL, js_check_key, NULL, NULL, NULL, napi_default, NULL},
         {"contributeKey", NULL, js_contribute_key, NULL, NULL, NULL, napi_default, NULL},
         {"deltaVerify", NULL, js_delta_verify, NULL, NULL, NULL, napi_default, NULL},
