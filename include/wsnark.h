@@ -918,6 +918,30 @@ int wsnark_selftest_field29(int which, int impl, int op, const uint32_t* operand
  * impl 0 = the device Fp12 of pairing.hip, 2 = the host Fp12 of the single-proof verifier (ops 2-5 there by plain exponentiation:
  * the yardstick).  a, b, out: n x 384 bytes, twelve PLAIN little-endian Fq values, coefficient i of w^i = (c0, c1); n <= 2^16. */
 int wsnark_selftest_fp12(int impl, int op, const void* a, const void* b, void* out, uint64_t n);
+/* What the MSM's grouping pass and task planner (csrc/msm.hip: presort_*, msm_plan_emit*) write for a scalar vector, read back without
+ * running a point kernel (tests/grouping_patterns.py holds the model it is compared with).
+ *   scalars : n x 32 bytes, raw 256-bit little-endian values (host)
+ *   table_c : 0 = a per-window plan; else a flat fixed-base table plan of that window width (4 .. 22)
+ *   w_off, w_stride : the window shard (rank, world of the *_msm_windows entry points); 0, 1 = every window
+ *   mask    : optional, n bytes (host): the plain plan is built first, then its masked variant as the prover builds one -- pairs with
+ *             mask[i] == 0 left out -- and the variant is what is returned
+ *   info    : WSNARK_MSM_PLAN_INFO_WORDS words, always written on WSNARK_OK and on WSNARK_ERR_SIZE: [0] c, [1] windows of the whole
+ *             scalar, [2] owned windows, [3] w_off, [4] w_stride, [5] NB = 2^(c-1), [6] buckets, [7] flat, [8] task cap lmax,
+ *             [9] hot-bucket threshold, [10] low bucket bits per bin, [11] index bits of a 4-byte entry, [12] bins, [13] 4-byte entries,
+ *             [14] the one-pass scatter ran, [15] partial slots, [16] multi-task buckets, [17] tasks, [18] hot buckets, [19] hot slices,
+ *             [20] length of vals (the end of the last bin), [21] threads per workgroup of the per-bin sort, [22] n, [23] 0.
+ *             All zero for n == 0 and for a shard that owns no window.
+ *   bstart, bend : info[6] words each (cap_buckets);  vals : info[20] words (cap_vals): index | sign << 31, table plans: window * n + i;
+ *   tasks : info[17] x (dst, start, len), dst = bucket or 0x80000000 | partial slot (cap_tasks);
+ *   multi : info[16] x (bucket, first_partial, ntasks) (cap_multi);
+ *   hot   : info[18] x (bucket, first_partial, ntasks, task_base, rem_index, start, rem, slice_base) (cap_hot).
+ * Capacities count records.  An array passed as NULL is not written: a first call with every array NULL returns the sizes.  An array
+ * whose capacity is too small fails the call with WSNARK_ERR_SIZE before any array is written.  The call waits for the queue; it
+ * leaves nothing behind that a later sum reads (every sum builds its own plan). */
+#define WSNARK_MSM_PLAN_INFO_WORDS 24
+int wsnark_selftest_msm_plan(const void* scalars, uint64_t n, uint32_t table_c, uint32_t w_off, uint32_t w_stride, const void* mask,
+                             uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
+                             uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot);
 
 /* ---- measurement hooks (bench.py) ---- */
 /* A/B switches of the library (queue arrangement of a proof, reduction-tail geometry, ...; the names are the WSNARK_<name>

@@ -157,10 +157,10 @@ def test_msm_all_same_point(bn, orc):
 
 
 @pytest.mark.parametrize("cfg", [{"MSM_ENTRY64": 1}, {"MSM_HOT_MIN": 2}, {"MSM_LMAX": 6}, {"MSM_C": 12, "MSM_HOT_MIN": 2, "MSM_LMAX": 4}])
-def test_msm_grouping_variants_agree(bn, tune, cfg):
+def test_msm_grouping_variants_agree(bn, orc, tune, cfg):
     """Entry width, hot-bucket threshold, task cap and window width only change how the pairs are grouped and how the partial sums of
     split buckets are folded (the three roles of the one combine launch): the sum must not move by a bit (G1 and G2, 60 000 pairs
-    with 30 % ones)."""
+    with 30 % ones).  The default run is also the closed form (sum s_i k_i mod r) G by the oracle's double-and-add."""
     import numpy as np
     n = 60000
     rng = np.random.default_rng(42)
@@ -174,6 +174,9 @@ def test_msm_grouping_variants_agree(bn, tune, cfg):
         pts = bn.mul_base(g, ks.tobytes())
         msm = bn.g1_multiexp if g == 1 else bn.g2_multiexp
         base = msm(sc.tobytes(), pts)
+        e = sum(int.from_bytes(sc[i].tobytes(), "little") * int.from_bytes(ks[i].tobytes(), "little") for i in range(n)) % orc.R
+        gen = H(load_golden("groups.json")["g%d" % g]["gen"])
+        assert base == orc.g_affine(g, orc.g_times_scalar(g, gen, e.to_bytes(32, "little")))
         for k, v in cfg.items():
             tune(bn.lib, k, v)
         assert msm(sc.tobytes(), pts) == base

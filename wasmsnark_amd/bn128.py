@@ -751,6 +751,44 @@ class Bn128:
         self.lib.check(fn(b, s, n, out))
         return bytes(out)[: n * sz]
 
+    # --- test hook (no reference counterpart): what the MSM's grouping pass and task planner write for a scalar vector ---
+    MSM_PLAN_INFO = ("c", "Wall", "W", "w_off", "w_stride", "NB", "nbuckets", "flat", "lmax", "hot_min", "lo_bits", "idx_bits", "nbins",
+                     "e32", "once", "partial_slots", "multi_buckets", "tasks", "hot_buckets", "hot_slices", "nvals", "bthr", "n")
+
+    def msm_plan(self, scalars, table_c=0, shard=None, mask=None, capacity=None):
+        """wsnark_selftest_msm_plan: {"info": {name: word}, "bstart", "bend", "vals": lists of words, "tasks": [(dst, start, len)],
+        "multi": [(bucket, first_partial, ntasks)], "hot": [(bucket, first_partial, ntasks, task_base, rem_index, start, rem,
+        slice_base)]}.  shard=(rank, world); mask: n bytes, the plan's masked variant.  capacity: (buckets, vals, tasks) a caller that
+        knows the geometry allows for -- one call, and WsnarkError (WSNARK_ERR_SIZE) if the plan is larger; None: the hook's two calls,
+        sizes first, then the arrays."""
+        s, ns = _ro(scalars)
+        n = ns // 32
+        m = None
+        if mask is not None:
+            m, nm = _ro(mask)
+            if nm != n:
+                raise ValueError("mask: one byte per scalar")
+        off, stride = shard or (0, 1)
+        fn = self.lib.c.wsnark_selftest_msm_plan
+        info = (C.c_uint32 * 24)()
+        if capacity is None:
+            self.lib.check(fn(s, n, table_c, off, stride, m, info, None, None, 0, None, 0, None, 0, None, 0, None, 0))
+            w = dict(zip(self.MSM_PLAN_INFO, info[:]))
+            cap = {"b": w["nbuckets"], "v": w["nvals"], "t": w["tasks"], "m": w["multi_buckets"], "h": w["hot_buckets"]}
+        else:
+            w = None
+            cap = {"b": capacity[0], "v": capacity[1], "t": capacity[2], "m": capacity[0], "h": capacity[0]}      # (one record per bucket at most)
+        bs, be = (C.c_uint32 * max(cap["b"], 1))(), (C.c_uint32 * max(cap["b"], 1))()
+        vals = (C.c_uint32 * max(cap["v"], 1))()
+        tasks, multi, hot = (C.c_uint32 * max(3 * cap["t"], 1))(), (C.c_uint32 * max(3 * cap["m"], 1))(), (C.c_uint32 * max(8 * cap["h"], 1))()
+        self.lib.check(fn(s, n, table_c, off, stride, m, info, bs, be, cap["b"], vals, cap["v"], tasks, cap["t"], multi, cap["m"], hot, cap["h"]))
+        w2 = dict(zip(self.MSM_PLAN_INFO, info[:]))
+        if w is not None and w2 != w:
+            raise RuntimeError("msm_plan: the two calls disagree on the plan's sizes: %r / %r" % (w, w2))
+        rec = lambda a, k, cnt: [tuple(x[i * k:(i + 1) * k]) for x in (a[:k * cnt],) for i in range(cnt)]
+        return {"info": w2, "bstart": bs[:w2["nbuckets"]], "bend": be[:w2["nbuckets"]], "vals": vals[:w2["nvals"]],
+                "tasks": rec(tasks, 3, w2["tasks"]), "multi": rec(multi, 3, w2["multi_buckets"]), "hot": rec(hot, 8, w2["hot_buckets"])}
+
     def load_points(self, g, points):
         """Make a point set resident as fixed-base tables (no reference counterpart): see ResidentPoints."""
         return ResidentPoints(self.lib, g, points)

@@ -626,6 +626,19 @@ int wsnark_selftest_fp12(int impl, int op, const void* a, const void* b, void* o
     return selftest_fp12(impl, op, (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)out, n);
 }
 
+int wsnark_selftest_msm_plan(const void* scalars, uint64_t n, uint32_t table_c, uint32_t w_off, uint32_t w_stride, const void* mask,
+                             uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
+                             uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot) {
+    static_assert(WSNARK_MSM_PLAN_INFO_WORDS == kMsmPlanInfoWords, "info words of the plan hook");
+    REQUIRE_CTX();
+    if (!info || (n && !scalars) || !shard_ok(w_off, w_stride)) return WSNARK_ERR_ARG;
+    if (n > ((uint64_t)1 << 28)) return WSNARK_ERR_SIZE;
+    if (table_c && (table_c < 4 || table_c > 22)) return WSNARK_ERR_ARG;
+    LaneLock L = acquire_lane(C);
+    return selftest_msm_plan(*L, scalars, n, table_c, WindowShard{w_off, w_stride}, (const uint8_t*)mask, info, bstart, bend, cap_buckets,
+                             vals, cap_vals, tasks, cap_tasks, multi, cap_multi, hot, cap_hot);
+}
+
 int wsnark_selftest_field29(int which, int impl, int op, const uint32_t* operands, uint32_t* out, uint64_t n) {
     REQUIRE_CTX();
     if (n && (!operands || !out)) return WSNARK_ERR_ARG;

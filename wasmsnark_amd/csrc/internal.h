@@ -282,6 +282,12 @@ void msm_select_plan(Lane& L, int id);      // id in [0, 4)
 // (which must just have been built by msm_plan_dev): only the per-bin counting sort and the task list are redone,
 // the digit extraction and the coarse scatter are shared.  Becomes plan `dst_id`.
 int msm_plan_variant(Lane& L, int src_id, int dst_id, const uint8_t* d_mask, hipStream_t s);
+// test hook (wsnark_selftest_msm_plan): builds the plan as msm_plan_dev does (h_mask: then its variant, as the prover does) and
+// copies back what the grouping pass and the planner wrote; capacities in records; no point kernel runs
+static const uint32_t kMsmPlanInfoWords = 24;
+int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table_c, WindowShard sh, const uint8_t* h_mask,
+                      uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
+                      uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot);
 bool msm_ready(Lane& L, int slot);     // the launch's window sums have reached the host (finish will not block)
 int msm_g1_finish(Lane& L, int slot, XYZZ<Fq>* out_host);
 int msm_g2_finish(Lane& L, int slot, XYZZ<Fq2>* out_host);

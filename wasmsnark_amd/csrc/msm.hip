@@ -2149,6 +2149,67 @@ int msm_g2_host(Lane& L, const void* h_scalars, const void* h_points, uint64_t n
     return msm_host_t<G2, Jac<Fq2>>(L, 1, h_scalars, h_points, n, sh, out_host);
 }
 
+// ---- test hook (wsnark_selftest_msm_plan): what the grouping pass and the task planner wrote for a scalar vector ----
+// The plan is built on lane L exactly as msm_plan_dev builds it (with a mask: the plain plan as plan 0, then its variant as plan 2, as
+// prove.hip does, and the variant is what is read); no point kernel runs.  The queue is waited for, then the info words are written
+// and every array the caller gave is copied back -- one whose capacity (in records) is too small fails the call before anything is
+// written.  Nothing a later sum depends on is changed: the next msm_plan_begin rebuilds the plan.
+int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table_c, WindowShard sh, const uint8_t* h_mask,
+                      uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
+                      uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot) {
+    static_assert(sizeof(Task) == 12 && sizeof(MultiBucket) == 12 && sizeof(HotBucket) == 32, "record layouts of the hook");
+    if (!ctx()) return WS_ERR_NOINIT;
+    if (!info || (n && !h_scalars)) return WS_ERR_ARG;
+    memset(info, 0, kMsmPlanInfoWords * sizeof(uint32_t));
+    hipStream_t s = L.stream;
+    MsmWorkspace& M = ws(L);
+    int rc;
+    if (n) {
+        WS_HIP_CHECK(L.host_in[0].reserve((size_t)n * 32));
+        if ((rc = upload_staged(L.host_in[0].p, h_scalars, (size_t)n * 32, s))) return rc;
+    }
+    msm_select_plan(L, 0);
+    if ((rc = msm_plan_dev(L, L.host_in[0].as<Fe>(), n, sh, s, table_c))) return rc;
+    int id = 0;
+    if (h_mask && M.plan[0].info.n) {
+        WS_HIP_CHECK(L.host_in[1].reserve((size_t)n));
+        if ((rc = upload_staged(L.host_in[1].p, h_mask, (size_t)n, s))) return rc;
+        if ((rc = msm_plan_variant(L, 0, 2, L.host_in[1].as<uint8_t>(), s))) return rc;
+        id = 2;
+    }
+    WS_HIP_CHECK(hipStreamSynchronize(s));
+    const MsmPlanInfo& I = M.plan[id].info;
+    const MsmPlanInfo& I0 = M.plan[0].info;          // (the variant shares the plain plan's coarse bins)
+    if (I.n == 0) return WS_OK;                      // (no pair, or a shard that owns no window: all words zero)
+    const MsmScratch& S = M.plan[id].S;
+    uint32_t cnt[8], nvals = 0;
+    WS_HIP_CHECK(hipMemcpy(cnt, S.counters.p, sizeof cnt, hipMemcpyDeviceToHost));
+    WS_HIP_CHECK(hipMemcpy(&nvals, M.plan[0].S.counters.as<uint32_t>() + CNT_BINS + (I0.ps_nbins + 1) + I0.ps_nbins, 4, hipMemcpyDeviceToHost));
+    const uint32_t words[kMsmPlanInfoWords] = {
+        I.c, I.Wall, I.W, I.w_off, I.w_stride, I.NB, I.nbuckets, I.flat ? 1u : 0u, I.lmax, I.hot_min,
+        I0.ps_lo_bits, I0.ps_idx_bits, I0.ps_nbins, I0.ps_e32 ? 1u : 0u, (I.Wall <= PRESORT_ONCE_W && I0.ps_tile == I0.ps_thr) ? 1u : 0u,
+        cnt[0], cnt[1], cnt[3], cnt[4], cnt[5], nvals, I0.ps_bthr, (uint32_t)I.n, 0u};
+    // every size against what the plan's buffers hold, then against the caller's capacities
+    if (cnt[3] > I.hot_cap || cnt[1] > I.hot_cap || cnt[4] > I.hot_cap / I.hot_min + 16 || (uint64_t)nvals > I.n * I.W) {
+        set_last_error("selftest_msm_plan: the plan's counters exceed its buffers");
+        return WS_ERR_SIZE;
+    }
+    if (((bstart || bend) && cap_buckets < I.nbuckets) || (vals && cap_vals < nvals) || (tasks && cap_tasks < cnt[3]) ||
+        (multi && cap_multi < cnt[1]) || (hot && cap_hot < cnt[4])) {
+        memcpy(info, words, sizeof words);           // (the sizes the caller needs)
+        set_last_error("selftest_msm_plan: an output array is too small");
+        return WS_ERR_SIZE;
+    }
+    if (bstart) WS_HIP_CHECK(hipMemcpy(bstart, S.bstart.p, (size_t)I.nbuckets * 4, hipMemcpyDeviceToHost));
+    if (bend) WS_HIP_CHECK(hipMemcpy(bend, S.bend.p, (size_t)I.nbuckets * 4, hipMemcpyDeviceToHost));
+    if (vals && nvals) WS_HIP_CHECK(hipMemcpy(vals, S.vals_out.p, (size_t)nvals * 4, hipMemcpyDeviceToHost));
+    if (tasks && cnt[3]) WS_HIP_CHECK(hipMemcpy(tasks, S.tasks.p, (size_t)cnt[3] * sizeof(Task), hipMemcpyDeviceToHost));
+    if (multi && cnt[1]) WS_HIP_CHECK(hipMemcpy(multi, S.multi.p, (size_t)cnt[1] * sizeof(MultiBucket), hipMemcpyDeviceToHost));
+    if (hot && cnt[4]) WS_HIP_CHECK(hipMemcpy(hot, S.hot.p, (size_t)cnt[4] * sizeof(HotBucket), hipMemcpyDeviceToHost));
+    memcpy(info, words, sizeof words);
+    return WS_OK;
+}
+
 WS_DEFINE_WARM(msm)
 
 }  // namespace wsnark
