@@ -499,6 +499,56 @@ int wsnark_circuit_witness_check(wsnark_circuit_res_t* h, const void* witness, s
 int wsnark_circuit_witness_check_dev(wsnark_circuit_res_t* h, const void* d_witness, size_t witness_len,
                                      uint64_t* bad_rows_host, void* bad_values_host, uint64_t cap,
                                      wsnark_witness_report_t* rep, void* stream);
+/* ---- many witnesses against ONE resident circuit in one call (csrc/witcheck.hip) ----
+ * The batch counterpart of wsnark_circuit_witness_check, beside wsnark_groth16_prove_batch: N calls of the single check are N memsets,
+ * 2 N launches of a handful of workgroups and N synchronising downloads; this is one memset, two launches and one download per pass.
+ * THE CONTRACT: for every i, verdicts[i] and witness i's lists are field for field what
+ *   wsnark_circuit_witness_check(h, witnesses + i * witness_stride, nVars * 32, rows_i, values_i, cap, &r)
+ * reports: bad, first_bad, unreduced, first_unreduced, listed, one_ok, ok; bad_rows[i * cap .. i * cap + listed_i) ascending, the
+ * SMALLEST bad indices of witness i; bad_values[(i * cap) * 96 ..) a | b | c of those rows, plain LE and canonical.  Signals >= r are
+ * reduced for the check and counted.  List entries beyond listed_i are left as they were.  Nothing in a result depends on the launch
+ * geometry or on the pass size.
+ *   witnesses     count witnesses, witness i at witnesses + i * witness_stride; only its first nVars signals are read.
+ *                 witness_stride < nVars * 32: WSNARK_ERR_SIZE.  count == 0: WSNARK_OK, nothing is touched.  count > 2^16:
+ *                 WSNARK_ERR_SIZE.
+ *   lists         bad_rows: count x cap u64; bad_values: count x cap x 96 B.  cap == 0: both may be NULL.
+ *   rep           may be NULL.
+ *   _dev          the witnesses are memory of the handle's device, ready on `stream` (NULL = the lane's own queue), and are read in
+ *                 place; pointer and stride are multiples of 16, else WSNARK_ERR_ARG.  The verdicts, lists and report are host
+ *                 memory; the call returns when they are written.
+ *   passes        a host batch goes through the staging ring in passes of `chunk` witnesses under a fixed byte budget
+ *                 (WITCHECK_BATCH_CHUNK, through wsnark_tuning_set or the environment, read per call); a device batch is read in place
+ *                 and the chunk only bounds the masks, the counters and the lists.  A pass costs one memset, two launches and one
+ *                 download of chunk x 48 B; with cap > 0 and bad witnesses in it, one gather of THEIR bitmasks (one launch, one
+ *                 download) and one launch and one download for all listed rows of the pass -- whatever the number of bad witnesses.
+ *                 count == 1 is handed to the single check (chunk = 1): the one shape a pass of its own lost to it.
+ *   domains < 64  every witness takes one whole wavefront of lc_check_batch_kernel, lanes domain .. 63 idle: no ballot word and no
+ *                 counter is shared by two witnesses.
+ *   A bad witness is a RESULT: WSNARK_OK with ok = 0 in its verdict.
+ *   errors        a NULL handle, witnesses or verdicts, or cap > 0 with a NULL list: WSNARK_ERR_ARG; before wsnark_init
+ *                 WSNARK_ERR_NOINIT.  On every error the verdicts, the lists and the report are left untouched (they are written last).
+ *   threads       everything a call writes on the device belongs to the lane it holds: two threads may run batches on one handle at
+ *                 once.  Each path waits for its queue before the lane goes back.
+ *   Out of scope: group handles; whether the circuit is a given key's (bit 0 of wsnark_pkey_circuit_check). */
+typedef struct {                    /* one per witness: the fields of wsnark_witness_report_t that belong to a witness */
+    uint64_t bad, first_bad;        /* first_bad: UINT64_MAX if none */
+    uint64_t unreduced, first_unreduced;
+    uint64_t listed;                /* min(bad, cap) */
+    uint32_t one_ok, ok;
+} wsnark_witness_verdict_t;
+typedef struct {
+    uint64_t count, rows;           /* rows = domain */
+    uint64_t good;                  /* witnesses with ok = 1 */
+    uint64_t first_not_ok;          /* smallest i with ok = 0, UINT64_MAX if none */
+    uint32_t chunk, reserved;       /* witnesses per pass */
+    double   ms[3];                 /* 0 (the circuit is resident), device (upload + kernels + download), whole call */
+} wsnark_witness_batch_report_t;
+int wsnark_circuit_witness_check_batch(wsnark_circuit_res_t* h, const void* witnesses, size_t witness_stride, uint64_t count,
+                                       wsnark_witness_verdict_t* verdicts, uint64_t* bad_rows, void* bad_values, uint64_t cap,
+                                       wsnark_witness_batch_report_t* rep);
+int wsnark_circuit_witness_check_batch_dev(wsnark_circuit_res_t* h, const void* d_witnesses, size_t witness_stride, uint64_t count,
+                                           wsnark_witness_verdict_t* verdicts_host, uint64_t* bad_rows_host, void* bad_values_host,
+                                           uint64_t cap, wsnark_witness_batch_report_t* rep, void* stream);
 /* ---- powers of tau: contribute to a transcript, audit one (csrc/pwtau.hip; snarkjs: `powersoftau contribute` / `powersoftau verify`) ----
  * Phase 1 itself: the transcript wsnark_pkey_setup builds a key on.  A contribution by secrets t, a, b (non-zero mod r) turns the
  * transcript of (tau, alpha, beta) into the one of (t tau, a alpha, b beta):

@@ -258,6 +258,81 @@ def _witness_lists(max_rows):
     return cap, ((C.c_uint64 * cap)() if cap else None), ((C.c_uint8 * (96 * cap))() if cap else None)
 
 
+class _WitnessVerdict(C.Structure):  # wsnark_witness_verdict_t
+    _fields_ = [("bad", C.c_uint64), ("first_bad", C.c_uint64), ("unreduced", C.c_uint64), ("first_unreduced", C.c_uint64),
+                ("listed", C.c_uint64), ("one_ok", C.c_uint32), ("ok", C.c_uint32)]
+
+
+class _WitnessBatchReport(C.Structure):  # wsnark_witness_batch_report_t
+    _fields_ = [("count", C.c_uint64), ("rows", C.c_uint64), ("good", C.c_uint64), ("first_not_ok", C.c_uint64), ("chunk", C.c_uint32),
+                ("reserved", C.c_uint32), ("ms", C.c_double * 3)]
+
+
+def _witness_batch_result(verdicts, rows, values, count, cap, rep, report):
+    """the verdicts and the two lists of wsnark_circuit_witness_check_batch as a list of check_witness's dicts (without rows and ms,
+    which go to `report` with the call's other counts)"""
+    if report is not None:
+        report.clear()
+        report.update({"count": int(rep.count), "rows": int(rep.rows), "good": int(rep.good), "first_not_ok": int(rep.first_not_ok),
+                       "chunk": int(rep.chunk), "ms": {"matrices": rep.ms[0], "device": rep.ms[1], "total": rep.ms[2]}})
+    vb = bytes(values) if values is not None else b""
+    val = lambda k: int.from_bytes(vb[32 * k:32 * k + 32], "little")
+    out = []
+    for i in range(count):
+        v, n, at = verdicts[i], int(verdicts[i].listed), i * cap
+        out.append({"bad": int(v.bad), "first_bad": int(v.first_bad), "listed": n, "unreduced": int(v.unreduced),
+                    "first_unreduced": int(v.first_unreduced), "one_ok": int(v.one_ok), "ok": int(v.ok),
+                    "bad_rows": [int(rows[at + j]) for j in range(n)],
+                    "bad_values": [(val(3 * (at + j)), val(3 * (at + j) + 1), val(3 * (at + j) + 2)) for j in range(n)]})
+    return out
+
+
+def _witness_batch_blob(witnesses, stride):
+    """a sequence of witness byte strings (each at least `stride` bytes), or ONE bytes-like object holding them back to back, `stride`
+    bytes each -> (the witnesses back to back, how many)"""
+    if isinstance(witnesses, (bytes, bytearray, memoryview)):
+        if stride == 0 or len(witnesses) % stride:
+            raise ValueError("witnesses: not a whole number of nVars x 32-byte witnesses")
+        return witnesses, len(witnesses) // stride
+    ws = [bytes(w) for w in witnesses]
+    if any(len(w) < stride for w in ws):
+        raise ValueError("a witness is shorter than nVars x 32 bytes")
+    return b"".join(w[:stride] for w in ws), len(ws)
+
+
+def _empty_prove_batch_report():
+    return _prove_batch_report_dict(_ProveBatchReport())
+
+
+def _merge_prove_batch_reports(reports):
+    """the reports of several calls as one: counts and times added up, the largest chunk"""
+    out = _empty_prove_batch_report()
+    for r in reports:
+        out["count"] += r["count"]
+        out["batched"] += r["batched"]
+        out["chunk"] = max(out["chunk"], r["chunk"])
+        out["window_bits"] = r["window_bits"]
+        for k in out["ms"]:
+            out["ms"][k] += r["ms"][k]
+    return out
+
+
+def _pick32(b, which):
+    return None if b is None else b"".join(b[32 * i:32 * i + 32] for i in which)
+
+
+def _good_runs(verdicts):
+    """[(first, count)] of every run of consecutive witnesses with ok = 1"""
+    runs = []
+    for i, v in enumerate(verdicts):
+        if v["ok"]:
+            if runs and runs[-1][0] + runs[-1][1] == i:
+                runs[-1][1] += 1
+            else:
+                runs.append([i, 1])
+    return [tuple(r) for r in runs]
+
+
 class _ProveBatchReport(C.Structure):  # wsnark_prove_batch_report_t
     _fields_ = [("count", C.c_uint64), ("batched", C.c_uint64), ("chunk", C.c_uint32), ("window_bits", C.c_uint32), ("ms", C.c_double * 5)]
 
@@ -323,6 +398,39 @@ class ResidentCircuit:
         rep = _WitnessReport()
         self._lib.check(self._lib.c.wsnark_circuit_witness_check_dev(self._h, d_witness, witness_len, rows, values, cap, C.byref(rep), stream))
         return _witness_report_dict(rep, rows, values)
+
+    def check_witnesses(self, witnesses, max_rows=16, report=None):
+        """Many witnesses in ONE call (wsnark_circuit_witness_check_batch).  witnesses: a sequence of witness byte strings (each at
+        least nVars x 32 bytes), or one bytes-like object holding them back to back, nVars x 32 bytes each.  Returns a list with,
+        per witness, the dict check_witness returns for it -- bad, first_bad, listed, unreduced, first_unreduced, one_ok, ok,
+        "bad_rows" (at most max_rows), "bad_values" -- without rows and ms.  report: a dict that receives the call's own
+        {count, rows, good, first_not_ok (2^64 - 1: none), chunk, ms}.  A bad witness is a result."""
+        stride = 32 * self.n_vars
+        blob, count = _witness_batch_blob(witnesses, stride)
+        return self._check_batch(_ro(blob)[0] if count else None, stride, count, max_rows, report, None, False)
+
+    def check_witnesses_dev(self, d_witnesses, witness_stride, count, max_rows=16, report=None, stream=None):
+        """The same for witnesses already on the circuit's device: d_witnesses is a raw device address (16-byte aligned), witness i
+        starts witness_stride bytes (a multiple of 16, at least nVars x 32) after witness i - 1; stream: the queue they are ready on."""
+        return self._check_batch(d_witnesses, witness_stride, int(count), max_rows, report, stream, True)
+
+    def _check_batch(self, w, stride, count, max_rows, report, stream, dev):
+        cap = int(max_rows)
+        if cap < 0:
+            raise ValueError("max_rows must not be negative")
+        rep = _WitnessBatchReport()
+        if count == 0:
+            rep.rows, rep.first_not_ok = self.domain, (1 << 64) - 1
+            return _witness_batch_result(None, None, None, 0, cap, rep, report)
+        verdicts = (_WitnessVerdict * count)()
+        rows = (C.c_uint64 * (cap * count))() if cap else None
+        values = (C.c_uint8 * (96 * cap * count))() if cap else None
+        c = self._lib.c
+        if dev:
+            self._lib.check(c.wsnark_circuit_witness_check_batch_dev(self._h, w, stride, count, verdicts, rows, values, cap, C.byref(rep), stream))
+        else:
+            self._lib.check(c.wsnark_circuit_witness_check_batch(self._h, w, stride, count, verdicts, rows, values, cap, C.byref(rep)))
+        return _witness_batch_result(verdicts, rows, values, count, cap, rep, report)
 
     def free(self):
         if self._h:
@@ -670,47 +778,84 @@ class Bn128:
         return proof_from_bytes(bytes(out))
 
     # --- many witnesses of one key (wsnark_groth16_prove_batch; no reference counterpart) ---
-    def groth16GenProofBatch(self, witnesses, key, r=None, s=None, return_blinding=False, report=None):
+    def groth16GenProofBatch(self, witnesses, key, r=None, s=None, return_blinding=False, report=None, circuit=None):
         """witnesses: a sequence of witness.bin byte strings (each at least nVars x 32 bytes), or ONE bytes-like object holding them
         back to back, nVars x 32 bytes each; key: proving_key.bin bytes or a ProvingKey (a whole key).
         r, s: None (drawn from the OS, one independent draw per proof) or one 32-byte value per proof (a sequence, or the
         values back to back).  Returns the list of proofs, proof i being what groth16GenProof(witnesses[i], key, r[i], s[i])
         returns; with return_blinding also the list of (r, s) as used.  report: a dict that receives the call's report
-        (count, batched -- 0 when the call looped the single prover --, chunk, window_bits, ms)."""
+        (count, batched -- 0 when the call looped the single prover --, chunk, window_bits, ms).
+        circuit: a ResidentCircuit (load_circuit) whose nVars, nPublic and domain are the key's, else ValueError before anything
+        runs.  All witnesses are checked against it in one call (check_witnesses, max_rows=1); those with ok = 1 are proved in
+        one call, each with its own r[i], s[i], to the proof the call without circuit= gives for it; a bad witness gives None in
+        the list of proofs and in the list of blinding pairs -- no proof is computed and no blinding drawn for it.  The report is
+        then that of the good witnesses' call and report["verdicts"] holds every witness's verdict.  None: nothing is checked."""
         pk = key if isinstance(key, ProvingKey) else ProvingKey(self.lib, key)
         try:
             stride = 32 * pk.n_vars
-            if isinstance(witnesses, (bytes, bytearray, memoryview)):
-                blob = witnesses
-                if stride == 0 or len(blob) % stride:
-                    raise ValueError("witnesses: not a whole number of nVars x 32-byte witnesses")
-                count = len(blob) // stride
-            else:
-                ws = [bytes(w) for w in witnesses]
-                count = len(ws)
-                if any(len(w) < stride for w in ws):
-                    raise ValueError("a witness is shorter than nVars x 32 bytes")
-                blob = b"".join(w[:stride] for w in ws)
+            if circuit is not None:
+                _same_shape(circuit, pk)
+            blob, count = _witness_batch_blob(witnesses, stride)
             rb, sb = _blinding_array(r, count, "r"), _blinding_array(s, count, "s")
-            if count == 0:
-                return ([], []) if return_blinding else []
-            out, rs, rep = (C.c_uint8 * (384 * count))(), (C.c_uint8 * (64 * count))(), _ProveBatchReport()
-            self.lib.check(self.lib.c.wsnark_groth16_prove_batch(pk._h, _ro(blob)[0], stride, count, rb, sb, out, rs, C.byref(rep)))
-            return _prove_batch_result(out, rs, count, rep, return_blinding, report)
+            if circuit is not None:
+                verdicts = circuit.check_witnesses(blob, max_rows=1)
+                good = [i for i, v in enumerate(verdicts) if v["ok"]]
+                inner = {}
+                proofs, used = self._prove_batch_host(pk, b"".join(bytes(blob[stride * i:stride * (i + 1)]) for i in good) if len(good) < count else blob,
+                                                      stride, len(good), _pick32(rb, good), _pick32(sb, good), inner)
+                all_proofs, all_used = [None] * count, [None] * count
+                for k, i in enumerate(good):
+                    all_proofs[i], all_used[i] = proofs[k], used[k]
+                if report is not None:
+                    report.clear()
+                    report.update(inner or _empty_prove_batch_report())
+                    report["verdicts"] = verdicts
+                return (all_proofs, all_used) if return_blinding else all_proofs
+            proofs, used = self._prove_batch_host(pk, blob, stride, count, rb, sb, report)
+            return (proofs, used) if return_blinding else proofs
         finally:
             if pk is not key:
                 pk.free()
 
-    def groth16GenProofBatch_dev(self, d_witnesses, witness_stride, count, key, r=None, s=None, return_blinding=False, report=None, stream=None):
+    def _prove_batch_host(self, pk, blob, stride, count, rb, sb, report):
+        if count == 0:
+            return [], []
+        out, rs, rep = (C.c_uint8 * (384 * count))(), (C.c_uint8 * (64 * count))(), _ProveBatchReport()
+        self.lib.check(self.lib.c.wsnark_groth16_prove_batch(pk._h, _ro(blob)[0], stride, count, rb, sb, out, rs, C.byref(rep)))
+        return _prove_batch_result(out, rs, count, rep, True, report)
+
+    def groth16GenProofBatch_dev(self, d_witnesses, witness_stride, count, key, r=None, s=None, return_blinding=False, report=None, stream=None,
+                                 circuit=None):
         """The same for witnesses already on the key's device: d_witnesses is a raw device address (16-byte aligned), witness i
-        starts witness_stride bytes (a multiple of 16, at least nVars x 32) after witness i - 1; stream: the queue they are ready on."""
+        starts witness_stride bytes (a multiple of 16, at least nVars x 32) after witness i - 1; stream: the queue they are ready on.
+        circuit: as in groth16GenProofBatch; the witnesses stay where they are, so every run of consecutive good witnesses is one
+        call, and the report adds those calls up."""
         count = int(count)
+        if circuit is not None:
+            _same_shape(circuit, key)
         rb, sb = _blinding_array(r, count, "r"), _blinding_array(s, count, "s")
         if count == 0:
             return ([], []) if return_blinding else []
+        if circuit is None:
+            proofs, used = self._prove_batch_dev(key, d_witnesses, witness_stride, count, rb, sb, report, stream)
+            return (proofs, used) if return_blinding else proofs
+        verdicts = circuit.check_witnesses_dev(d_witnesses, witness_stride, count, max_rows=1, stream=stream)
+        proofs, used, reports = [None] * count, [None] * count, []
+        for first, n in _good_runs(verdicts):
+            inner, which = {}, range(first, first + n)
+            proofs[first:first + n], used[first:first + n] = self._prove_batch_dev(key, int(d_witnesses) + first * int(witness_stride), witness_stride, n,
+                                                                                   _pick32(rb, which), _pick32(sb, which), inner, stream)
+            reports.append(inner)
+        if report is not None:
+            report.clear()
+            report.update(_merge_prove_batch_reports(reports))
+            report["verdicts"] = verdicts
+        return (proofs, used) if return_blinding else proofs
+
+    def _prove_batch_dev(self, key, d_witnesses, witness_stride, count, rb, sb, report, stream):
         out, rs, rep = (C.c_uint8 * (384 * count))(), (C.c_uint8 * (64 * count))(), _ProveBatchReport()
         self.lib.check(self.lib.c.wsnark_groth16_prove_batch_dev(key._h, d_witnesses, witness_stride, count, rb, sb, out, rs, C.byref(rep), stream))
-        return _prove_batch_result(out, rs, count, rep, return_blinding, report)
+        return _prove_batch_result(out, rs, count, rep, True, report)
 
     # --- src/bn128.js:569-578 (worker CALC_H :126-166) ---
     def calcH(self, signals, polsA, polsB, nSignals, domainSize):
@@ -1075,7 +1220,8 @@ class Bn128:
     # --- a witness against its circuit (csrc/witcheck.hip; no reference counterpart -- snarkjs: wtns check) ---
     def load_circuit(self, circuit):
         """circuit: the dict of setup_key ({"n_vars", "n_public", "domain", "polsA", "polsB", "polsC"}).  Returns a ResidentCircuit:
-        .check_witness(witness, max_rows=16), .check_witness_dev(d_witness, witness_len, max_rows=16, stream=None), .info(), .free()."""
+        .check_witness(witness, max_rows=16), .check_witness_dev(d_witness, witness_len, max_rows=16, stream=None), .check_witnesses(witnesses,
+        max_rows=16, report=None), .check_witnesses_dev(d_witnesses, witness_stride, count, ...), .info(), .free()."""
         return ResidentCircuit(self.lib, circuit)
 
     def check_witness(self, circuit, witness, max_rows=16):

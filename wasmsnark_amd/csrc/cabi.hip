@@ -17,6 +17,7 @@ static_assert(sizeof(wsnark_pkey_setup_report_t) == 192, "the bindings read this
 static_assert(sizeof(wsnark_powers_report_t) == 192, "the bindings read this by offset");
 static_assert(sizeof(wsnark_pkey_circuit_verdict_t) == 56, "the bindings read this by offset");
 static_assert(sizeof(wsnark_witness_report_t) == 80, "the bindings read this by offset");
+static_assert(sizeof(wsnark_witness_verdict_t) == 48 && sizeof(wsnark_witness_batch_report_t) == 64, "the bindings read these by offset");
 static_assert(sizeof(wsnark_prove_batch_report_t) == 64, "the bindings read this by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
@@ -513,6 +514,25 @@ int wsnark_circuit_witness_check_dev(wsnark_circuit_res_t* h, const void* d_witn
     CtxScope scope(circuit_context(reinterpret_cast<const CircuitRes*>(h)));
     return circuit_witness_check(reinterpret_cast<CircuitRes*>(h), d_witness, witness_len, true, bad_rows_host, bad_values_host, cap, rep,
                                  (hipStream_t)stream);
+}
+// many witnesses of one resident circuit (witcheck.hip)
+int wsnark_circuit_witness_check_batch(wsnark_circuit_res_t* h, const void* witnesses, size_t witness_stride, uint64_t count,
+                                       wsnark_witness_verdict_t* verdicts, uint64_t* bad_rows, void* bad_values, uint64_t cap,
+                                       wsnark_witness_batch_report_t* rep) {
+    REQUIRE_CTX();
+    if (!h) return WSNARK_ERR_ARG;
+    CtxScope scope(circuit_context(reinterpret_cast<const CircuitRes*>(h)));
+    return circuit_witness_check_batch(reinterpret_cast<CircuitRes*>(h), witnesses, witness_stride, count, false, verdicts, bad_rows, bad_values,
+                                       cap, rep, nullptr);
+}
+int wsnark_circuit_witness_check_batch_dev(wsnark_circuit_res_t* h, const void* d_witnesses, size_t witness_stride, uint64_t count,
+                                           wsnark_witness_verdict_t* verdicts_host, uint64_t* bad_rows_host, void* bad_values_host, uint64_t cap,
+                                           wsnark_witness_batch_report_t* rep, void* stream) {
+    REQUIRE_CTX();
+    if (!h) return WSNARK_ERR_ARG;
+    CtxScope scope(circuit_context(reinterpret_cast<const CircuitRes*>(h)));
+    return circuit_witness_check_batch(reinterpret_cast<CircuitRes*>(h), d_witnesses, witness_stride, count, true, verdicts_host, bad_rows_host,
+                                       bad_values_host, cap, rep, (hipStream_t)stream);
 }
 int wsnark_pkey_shard_info(const wsnark_pkey_t* h, uint32_t* rank, uint32_t* world, uint64_t* first_signal, uint64_t* n_signals,
                            uint64_t* n_hexps, uint32_t* h_interleave_log) {

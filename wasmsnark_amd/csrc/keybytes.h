@@ -260,6 +260,10 @@ int circuit_witness_check(CircuitRes* H, const void* witness, size_t witness_len
                           uint64_t cap, wsnark_witness_report_t* rep, hipStream_t s);
 int witness_check(const wsnark_circuit_t* K, const void* witness, size_t witness_len, uint64_t* bad_rows, void* bad_values, uint64_t cap,
                   wsnark_witness_report_t* rep);
+// many witnesses against one resident circuit in one call; witnesses / outputs as include/wsnark.h: wsnark_circuit_witness_check_batch
+int circuit_witness_check_batch(CircuitRes* H, const void* witnesses, size_t witness_stride, uint64_t count, bool on_device,
+                                wsnark_witness_verdict_t* verdicts, uint64_t* bad_rows, void* bad_values, uint64_t cap,
+                                wsnark_witness_batch_report_t* rep, hipStream_t stream);
 // the audit's per-point kernels on device-resident points in reference format (pkeycheck.hip): counts into d_acc with the global index
 // base + i; the G2 one with the order-r subgroup test (PKCHECK_SUBGROUP picks its form), d_K: the pairing constants on the device
 int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s);

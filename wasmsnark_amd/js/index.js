@@ -176,6 +176,44 @@ function witnessReport(ab, cap) {
     }
     return out;
 }
+/* the buffer of addon.circuitCheckWitnesses -- wsnark_witness_batch_report_t (64 bytes), count wsnark_witness_verdict_t (48 bytes each),
+ * count x cap row indices, count x cap x 96 bytes of values -- -> {verdicts: per witness the object of checkWitness() without rows and
+ * ms, report: {count, rows, good, firstNotOk (null: none), chunk, ms}} */
+function witnessVerdicts(ab, count, cap) {
+    const v = new DataView(ab);
+    const u64 = (o) => Number(v.getBigUint64(o, true));
+    const big = (o) => { let x = 0n; for (let i = 3; i >= 0; i--) x = (x << 64n) | v.getBigUint64(o + 8 * i, true); return x; };
+    const good = u64(16);
+    const report = { count: u64(0), rows: u64(8), good, firstNotOk: good === count ? null : u64(24), chunk: v.getUint32(32, true),
+                     ms: { matrices: v.getFloat64(40, true), device: v.getFloat64(48, true), total: v.getFloat64(56, true) } };
+    const rowsAt = 64 + 48 * count, valuesAt = rowsAt + 8 * count * cap;
+    const verdicts = [];
+    for (let i = 0; i < count; i++) {
+        const o = 64 + 48 * i, bad = u64(o), unreduced = u64(o + 16), listed = u64(o + 32);
+        const one = { bad, firstBad: bad ? u64(o + 8) : null, listed, unreduced, firstUnreduced: unreduced ? u64(o + 24) : null,
+                      oneOk: v.getUint32(o + 40, true) === 1, ok: v.getUint32(o + 44, true) === 1, badRows: [], badValues: [] };
+        for (let j = 0; j < listed; j++) {
+            one.badRows.push(u64(rowsAt + 8 * (i * cap + j)));
+            const q = valuesAt + 96 * (i * cap + j);
+            one.badValues.push([big(q), big(q + 32), big(q + 64)]);
+        }
+        verdicts.push(one);
+    }
+    return { verdicts, report };
+}
+/* an array of witness buffers (each at least `stride` bytes), or ONE buffer holding them back to back -> {blob, count} */
+function witnessBlob(witnesses, stride) {
+    if (Array.isArray(witnesses)) {
+        const ws = witnesses.map(asBytes);
+        if (ws.some((w) => w.byteLength < stride)) throw new Error("wsnark: a witness is shorter than nVars x 32 bytes");
+        const blob = new Uint8Array(stride * ws.length);
+        ws.forEach((w, i) => blob.set(w.subarray(0, stride), stride * i));
+        return { blob, count: ws.length };
+    }
+    const blob = asBytes(witnesses);
+    if (stride === 0 || blob.byteLength % stride) throw new Error("wsnark: not a whole number of nVars x 32-byte witnesses");
+    return { blob, count: blob.byteLength / stride };
+}
 function witnessFinding(rep) {
     if (rep.bad) {
         let text = `constraint ${rep.firstBad}: (A.w)(B.w) != C.w`;
@@ -418,8 +456,10 @@ class Bn128 {
         const cap = maxRowsOf(opts);
         return witnessReport(await addon.checkWitness(circuit.nVars, circuit.nPublic, circuit.domain, bufs, witness, cap), cap);
     }
-    /* The circuit's three matrices made RESIDENT once (wsnark_circuit_load): resolves to {checkWitness(witness, {maxRows}), info(),
-     * free()}.  Checks on one loaded circuit may run side by side; free() hands the device memory back once those in flight are done
+    /* The circuit's three matrices made RESIDENT once (wsnark_circuit_load): resolves to {checkWitness(witness, {maxRows}),
+     * checkWitnesses(witnesses, {maxRows, report}), info(), free()}.  checkWitnesses checks many witnesses in ONE call
+     * (wsnark_circuit_witness_check_batch): an array of witness buffers, or one buffer holding them back to back; it resolves to the
+     * array of what checkWitness resolves to for each, without rows and ms, which go to opts.report with count, good, firstNotOk, chunk.  Checks on one loaded circuit may run side by side; free() hands the device memory back once those in flight are done
      * (the garbage collector does it otherwise).  Pass the object to groth16GenProof as opts.circuit to have every witness checked
      * before it is proved. */
     async loadCircuit(circuit) {
@@ -437,6 +477,18 @@ class Bn128 {
                 const cap = maxRowsOf(opts);
                 inflight++;
                 try { return witnessReport(await addon.circuitCheckWitness(handle, witness, cap), cap); } finally { inflight--; release(); }
+            },
+            async checkWitnesses(witnesses, opts) {
+                if (freed) throw new Error("wsnark: this circuit has been freed");
+                const { blob, count } = witnessBlob(witnesses, 32 * circuit.nVars);
+                const cap = maxRowsOf(opts);
+                let res = { verdicts: [], report: { count: 0, rows: circuit.domain, good: 0, firstNotOk: null, chunk: 0, ms: { matrices: 0, device: 0, total: 0 } } };
+                if (count) {
+                    inflight++;
+                    try { res = witnessVerdicts(await addon.circuitCheckWitnesses(handle, blob, count, cap), count, cap); } finally { inflight--; release(); }
+                }
+                if (opts && opts.report && typeof opts.report === "object") Object.assign(opts.report, res.report);
+                return res.verdicts;
             },
             info() {
                 if (freed) throw new Error("wsnark: this circuit has been freed");
@@ -534,24 +586,24 @@ class Bn128 {
      * 32-byte value per proof (an array, or the values back to back); absent: drawn per proof.  Resolves to the array of proofs,
      * proof i being what groth16GenProof(witnesses[i], pkey, {r: r[i], s: s[i]}) resolves to.  opts.blinding (an array) receives
      * {r, s} of every proof as used, opts.report (an object) the call's report: count, batched (0: the call looped the single
-     * prover), chunk, windowBits, ms. */
+     * prover), chunk, windowBits, ms.
+     * opts.circuit: an object from loadCircuit() whose nVars, nPublic and domain are the key's (else the call rejects before anything
+     * runs).  All witnesses are checked against it in one call (checkWitnesses, maxRows 1); those that are ok are proved in one call,
+     * each with its own r[i], s[i], to the proof the call without opts.circuit gives for it; a bad witness gives null in the array of
+     * proofs and in opts.blinding -- no proof is computed and no blinding drawn for it.  The resolved array then carries the
+     * verdicts of all witnesses as its property `verdicts` (and opts.report.verdicts), the report being the good witnesses' call's. */
     async groth16GenProofBatch(witnesses, pkey, opts) {
         if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
         if (this._group) throw new Error("wsnark: groth16GenProofBatch needs a whole key on one device (not buildBn128({devices}))");
         const h = await this.loadKey(pkey, opts);
-        const stride = 32 * addon.keyInfo(h).nVars;
-        let blob, count;
-        if (Array.isArray(witnesses)) {
-            const ws = witnesses.map(asBytes);
-            if (ws.some((w) => w.byteLength < stride)) throw new Error("wsnark: a witness is shorter than nVars x 32 bytes");
-            count = ws.length;
-            blob = new Uint8Array(stride * count);
-            ws.forEach((w, i) => blob.set(w.subarray(0, stride), stride * i));
-        } else {
-            blob = asBytes(witnesses);
-            if (stride === 0 || blob.byteLength % stride) throw new Error("wsnark: not a whole number of nVars x 32-byte witnesses");
-            count = blob.byteLength / stride;
+        const ki = addon.keyInfo(h);
+        const stride = 32 * ki.nVars;
+        if (opts && opts.circuit) {
+            const ci = opts.circuit.info();
+            if (ci.nVars !== ki.nVars || ci.nPublic !== ki.nPublic || ci.domain !== ki.domainSize)
+                throw new Error(`wsnark: the circuit (nVars ${ci.nVars}, nPublic ${ci.nPublic}, domain ${ci.domain}) is not the key's (${ki.nVars}, ${ki.nPublic}, ${ki.domainSize})`);
         }
+        const { blob, count } = witnessBlob(witnesses, stride);
         const values = (v, name) => {
             if (v === undefined || v === null) return null;
             const parts = Array.isArray(v) ? v.map(asBytes) : [asBytes(v)];
@@ -567,22 +619,40 @@ class Bn128 {
         };
         const r = values(opts && opts.r, "r"), s = values(opts && opts.s, "s");
         if (count === 0) return [];
-        const out = await addon.proveBatch(h, blob, count, r, s);
+        // which witnesses are proved: all of them, or those the circuit passes
+        let which = null, verdicts = null;
+        if (opts && opts.circuit) {
+            verdicts = await opts.circuit.checkWitnesses(blob, { maxRows: 1 });
+            which = [];
+            verdicts.forEach((v, i) => { if (v.ok) which.push(i); });
+        }
+        const pick = (buf, width) => {
+            if (!buf || !which || which.length === count) return buf;
+            const out = new Uint8Array(width * which.length);
+            which.forEach((i, k) => out.set(buf.subarray(width * i, width * i + width), width * k));
+            return out;
+        };
+        const n = which ? which.length : count;
+        const out = n ? await addon.proveBatch(h, pick(blob, stride), n, pick(r, 32), pick(s, 32)) : new ArrayBuffer(64);
+        const at = (k) => (which ? which[k] : k);
         if (opts && Array.isArray(opts.blinding)) {
             opts.blinding.length = 0;
-            for (let i = 0; i < count; i++) {
-                const o = 384 * count + 64 * i;
-                opts.blinding.push({ r: new Uint8Array(out.slice(o, o + 32)), s: new Uint8Array(out.slice(o + 32, o + 64)) });
+            for (let i = 0; i < count; i++) opts.blinding.push(null);
+            for (let k = 0; k < n; k++) {
+                const o = 384 * n + 64 * k;
+                opts.blinding[at(k)] = { r: new Uint8Array(out.slice(o, o + 32)), s: new Uint8Array(out.slice(o + 32, o + 64)) };
             }
         }
         if (opts && opts.report && typeof opts.report === "object") {
-            const dv = new DataView(out, 448 * count, 64);
+            const dv = new DataView(out, 448 * n, 64);
             const ms = [0, 1, 2, 3, 4].map((k) => dv.getFloat64(24 + 8 * k, true));
             Object.assign(opts.report, { count: Number(dv.getBigUint64(0, true)), batched: Number(dv.getBigUint64(8, true)), chunk: dv.getUint32(16, true),
                 windowBits: dv.getUint32(20, true), ms: { upload: ms[0], calcH: ms[1], sums: ms[2], assembly: ms[3], total: ms[4] } });
+            if (verdicts) opts.report.verdicts = verdicts;
         }
-        const proofs = [];
-        for (let i = 0; i < count; i++) proofs.push(proofFromBytes(out.slice(384 * i, 384 * i + 384)));
+        const proofs = new Array(count).fill(null);
+        for (let k = 0; k < n; k++) proofs[at(k)] = proofFromBytes(out.slice(384 * k, 384 * k + 384));
+        if (verdicts) proofs.verdicts = verdicts;
         return proofs;
     }
     /* src/bn128.js:722-791: verificationKey = snarkjs "groth" verification_key.json object, input = public signals

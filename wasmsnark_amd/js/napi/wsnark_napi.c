@@ -92,6 +92,7 @@ static struct {
     int (*circuit_info)(const wsnark_circuit_res_t*, uint32_t*, uint32_t*, uint32_t*, uint64_t*, uint64_t*);
     int (*witness_check)(const void*, const void*, size_t, uint64_t*, void*, uint64_t, void*);
     int (*circuit_witness_check)(wsnark_circuit_res_t*, const void*, size_t, uint64_t*, void*, uint64_t, void*);
+    int (*circuit_witness_check_batch)(wsnark_circuit_res_t*, const void*, size_t, uint64_t, void*, uint64_t*, void*, uint64_t, void*);
     char dir[4096];
 } L;
 
@@ -140,6 +141,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(pkey_circuit_check, "wsnark_pkey_circuit_check") SYM(pkey_circuit_check_file, "wsnark_pkey_circuit_check_file")
     SYM(circuit_load, "wsnark_circuit_load") SYM(circuit_free, "wsnark_circuit_free") SYM(circuit_info, "wsnark_circuit_info")
     SYM(witness_check, "wsnark_witness_check") SYM(circuit_witness_check, "wsnark_circuit_witness_check")
+    SYM(circuit_witness_check_batch, "wsnark_circuit_witness_check_batch")
 #undef SYM
     return 0;
 }
@@ -169,7 +171,7 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
        OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
        OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
-       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH };
+       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -300,6 +302,8 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
 #define POWERS_REPORT_BYTES 192          /* sizeof(wsnark_powers_report_t) */
 #define PKEY_CIRCUIT_VERDICT_BYTES 56    /* sizeof(wsnark_pkey_circuit_verdict_t) */
 #define WITNESS_REPORT_BYTES 80          /* sizeof(wsnark_witness_report_t) */
+#define WITNESS_VERDICT_BYTES 48         /* sizeof(wsnark_witness_verdict_t) */
+#define WITNESS_BATCH_REPORT_BYTES 64    /* sizeof(wsnark_witness_batch_report_t) */
 /* wsnark_powers_t and wsnark_circuit_t (include/wsnark.h) */
 typedef struct {
     uint32_t domain;
@@ -410,6 +414,14 @@ static void job_execute(napi_env env, void* data) {
         } else {
             j->rc = L.circuit_witness_check(j->circ, j->a, j->na, rows, vals, j->cap, j->out);
         }
+        break;
+    }
+    case OP_CIRCUIT_WITNESS_CHECK_BATCH: {   /* out = the report (64 B), count verdicts (48 B each), count x cap u64, count x cap x 96 B */
+        const size_t n = j->u0;
+        uint8_t* ver = j->out + WITNESS_BATCH_REPORT_BYTES;
+        uint64_t* rows = j->cap ? (uint64_t*)(ver + WITNESS_VERDICT_BYTES * n) : NULL;
+        uint8_t* vals = j->cap ? ver + WITNESS_VERDICT_BYTES * n + 8 * n * j->cap : NULL;
+        j->rc = L.circuit_witness_check_batch(j->circ, j->a, j->na / n, n, ver, rows, vals, j->cap, j->out);
         break;
     }
     case OP_WAIT_TABLES: j->rc = L.pkey_wait_tables(j->key); break;
@@ -957,6 +969,26 @@ static napi_value js_circuit_check_witness(napi_env env, napi_callback_info info
     keep(env, j, argv[0]); keep(env, j, argv[1]);
     return start_job(env, j, "wsnark_circuit_witness_check");
 }
+/* circuitCheckWitnesses(handle, witnesses (count witnesses back to back, equal lengths), count, cap) -> Promise<ArrayBuffer 64 + count x
+ * (48 + cap x 104)>: the wsnark_witness_batch_report_t, the verdicts, count x cap row indices (u64), count x cap x (a | b | c)
+ * (include/wsnark.h, wsnark_circuit_witness_check_batch) */
+static napi_value js_circuit_check_witnesses(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CIRCUIT_WITNESS_CHECK_BATCH;
+    uint32_t cap = 0;
+    if (argc < 4 || !(j->circ = (wsnark_circuit_res_t*)get_plain(env, argv[0], TAG_CIRCUIT)) || !get_bytes(env, argv[1], &j->a, &j->na) ||
+        napi_get_value_uint32(env, argv[2], &j->u0) != napi_ok || j->u0 == 0 || j->u0 > (1u << 16) || j->na % j->u0)
+        FAIL(env, j, "expected (circuit handle, witnesses (count x bytes), count in [1, 2^16], maxRows)");
+    if (napi_get_value_uint32(env, argv[3], &cap) != napi_ok || cap > (1u << 24)) FAIL(env, j, "maxRows: a count of at most 2^24");
+    j->cap = cap;
+    j->nout = WITNESS_BATCH_REPORT_BYTES + (size_t)j->u0 * (WITNESS_VERDICT_BYTES + (size_t)cap * (8 + 96));
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[0]); keep(env, j, argv[1]);
+    return start_job(env, j, "wsnark_circuit_witness_check_batch");
+}
 /* checkWitness(nVars, nPublic, domain, [polsA, polsB, polsC], witness, cap) -> Promise<ArrayBuffer>: the same, load and free included */
 static napi_value js_check_witness(napi_env env, napi_callback_info info) {
     size_t argc = 6; napi_value argv[6];
@@ -1368,6 +1400,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"circuitInfo", NULL, js_circuit_info, NULL, NULL, NULL, napi_default, NULL},
         {"circuitFree", NULL, js_circuit_free, NULL, NULL, NULL, napi_default, NULL},
         {"circuitCheckWitness", NULL, js_circuit_check_witness, NULL, NULL, NULL, napi_default, NULL},
+        {"circuitCheckWitnesses", NULL, js_circuit_check_witnesses, NULL, NULL, NULL, napi_default, NULL},
         {"checkWitness", NULL, js_check_witness, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
