@@ -1,4 +1,5 @@
-"""Per-kernel times of the grouping pass (presort_* / msm_plan_*), every kernel ALONE (one queue), over tuning combos "A=1,B=2;A=3".  2^20 proofs."""
+"""Per-kernel times of the grouping pass (presort_* / msm_plan_*), every kernel ALONE (one queue), over tuning combos "A=1,B=2;A=3",
+alternated for [rounds] rounds (default 2) in one process.  2^20 proofs."""
 import json, os, sys, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "."))
 import torch, wasmsnark_amd
@@ -16,7 +17,7 @@ f = lambda: bn.groth16GenProof_dev(d_w.data_ptr(), len(wit), key, r=r, s=s)
 combos = [dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in c.split(",") if kv) for c in sys.argv[1].split(";")]
 names = sorted({k for c in combos for k in c})
 bn.lib.tune("PROVE_OVERLAP", 0)
-for rd in range(2):
+for rd in range(int(sys.argv[2]) if len(sys.argv) > 2 else 2):
     for c in combos:
         for k in names: bn.lib.tune(k, c.get(k))
         for _ in range(3): out = f()

@@ -11,9 +11,11 @@
 // uses the same scalars -- the prover's A, B1, B2 and C sums):
 //   plan  1 presort_count/scan/scatter  scalar (32 B coalesced) -> reduced mod r -> signed c-bit digits on the
 //                      fly -> ONE scatter of (index | sign | low bucket bits) entries into coarse bins
-//                      (window x top bucket bits), block-reserved ranges, ranks from LDS atomics
+//                      (window x top bucket bits), block-reserved ranges, ranks from LDS atomics; 4-byte entries
+//                      leave a workgroup through an LDS stage in bin order, a bin's run from neighbouring lanes
 //         2 presort_bins   one workgroup per bin: LDS counting sort over the low bucket bits, bucket bounds,
-//                      task-length histogram (wavefront-aggregated counters for hot buckets)
+//                      task-length histogram (wavefront-aggregated counters for hot buckets); a bin of <= 4096
+//                      4-byte entries is read once, sorted in LDS and written linearly
 //         3 msm_plan_*     buckets cut into tasks of <= lmax entries, ordered longest-first (255-level
 //                      counting sort); very hot buckets get their task list from a workgroup each
 //   exec  4 msm_accumulate  one lane per task: mixed additions (XYZZ += affine, 8M+2S) of the task's points,
@@ -208,7 +210,19 @@ __global__ __launch_bounds__(1024) void presort_scatter(PresortArgs A, uint32_t*
 // the workgroup's bin reservations.  The exclusive scan of the bin counts is taken by every workgroup for itself (4096 counters,
 // a few microseconds beside the digit work; one launch and one dependency less than a scan kernel in between); workgroup 0
 // leaves the starts behind for presort_bins.  bin_cursor: zero at launch, counts RELATIVE to the bin's start.
+//
+// STAGED (4-byte entries, WSNARK_PRESORT_STAGE): the stores above go to as many bins as a wavefront has lanes (4096 bins, 3.25 entries
+// per workgroup and bin at 2^20), a memory transaction per entry.  The staged form takes the exclusive scan of the workgroup's own bin
+// counts, puts every entry at local_offset[bin] + rank of an LDS stage -- the workgroup's entries in bin order, a 16-bit plane of bin
+// ids beside them -- and lets consecutive lanes write consecutive stage positions: the lanes of one bin write neighbouring addresses.
+// The stage position j of bin b goes to gbase[b] + j, where gbase[b] = start of the bin + this workgroup's reservation - local offset.
 static const uint32_t PRESORT_ONCE_W = 16;
+static const uint32_t PRESORT_LDS_BYTES = 160u << 10;        // per CU, and what one workgroup may declare
+// LDS of the staged scatter at `rows` windows of 1024 scalars: counters and bases, the stage, the plane of bin ids, the scan's words
+constexpr uint32_t presort_stage_lds(uint32_t rows) { return 2 * PRESORT_MAX_BINS * 4 + rows * 1024 * (4 + 2) + 17 * 4; }
+constexpr bool presort_stage_fits(uint32_t rows) { return rows == 0 || (presort_stage_lds(rows) <= PRESORT_LDS_BYTES && presort_stage_fits(rows - 1)); }
+static_assert(presort_stage_fits(PRESORT_ONCE_W), "the staged scatter's LDS exceeds a CU's for some row count up to PRESORT_ONCE_W");
+static_assert(PRESORT_MAX_BINS <= 1u << 12 && PRESORT_ONCE_W * 1024 <= 1u << 20, "where[]: 12 bits of bin, 20 of rank");
 // exclusive scan of one value per thread over a workgroup of up to 1024 threads; *total = the sum.  wsum: 17 words of LDS.
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
     const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
@@ -233,7 +247,7 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* w
     *total = wsum[16];
     return wsum[wid] + x - v;
 }
-template <class E>
+template <class E, bool STAGED>
 __global__ __launch_bounds__(1024) void presort_scatter_once(PresortArgs A, const uint32_t* __restrict__ bin_count,
                                                                uint32_t* __restrict__ bin_start, uint32_t* __restrict__ bin_cursor,
                                                                E* __restrict__ entries) {
@@ -290,14 +304,41 @@ __global__ __launch_bounds__(1024) void presort_scatter_once(PresortArgs A, cons
         }
     }
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < A.nbins; b += blockDim.x) {
-        const uint32_t c0 = cnt[b];
-        if (c0) gbase[b] += atomicAdd(&bin_cursor[b], c0);
-    }
-    __syncthreads();
+    if constexpr (STAGED) {
+        static_assert(sizeof(E) == 4, "the stage holds 4-byte entries");
+        __shared__ uint32_t stage[PRESORT_ONCE_W * 1024];
+        __shared__ uint16_t stage_bin[PRESORT_ONCE_W * 1024];
+        // cnt[b] becomes the bin's offset in the stage, gbase[b] the difference between a stage position and its destination
+        const uint32_t per = (A.nbins + blockDim.x - 1) / blockDim.x, b0 = threadIdx.x * per;
+        uint32_t mine = 0, staged;
+        for (uint32_t b = b0; b < b0 + per && b < A.nbins; b++) mine += cnt[b];
+        uint32_t run = block_exclusive_scan(mine, wsum, &staged);
+        for (uint32_t b = b0; b < b0 + per && b < A.nbins; b++) {
+            const uint32_t c0 = cnt[b];
+            if (c0) gbase[b] += atomicAdd(&bin_cursor[b], c0) - run;
+            cnt[b] = run;
+            run += c0;
+        }
+        __syncthreads();
 #pragma unroll
-    for (uint32_t w = 0; w < PRESORT_ONCE_W; w++)
-        if (where[w] != NONE) entries[gbase[where[w] & 0xFFFu] + (where[w] >> 12)] = ent[w];
+        for (uint32_t w = 0; w < PRESORT_ONCE_W; w++)
+            if (where[w] != NONE) {
+                const uint32_t b = where[w] & 0xFFFu, j = cnt[b] + (where[w] >> 12);
+                stage[j] = ent[w];
+                stage_bin[j] = (uint16_t)b;
+            }
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < staged; j += blockDim.x) entries[gbase[stage_bin[j]] + j] = stage[j];
+    } else {
+        for (uint32_t b = threadIdx.x; b < A.nbins; b += blockDim.x) {
+            const uint32_t c0 = cnt[b];
+            if (c0) gbase[b] += atomicAdd(&bin_cursor[b], c0);
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t w = 0; w < PRESORT_ONCE_W; w++)
+            if (where[w] != NONE) entries[gbase[where[w] & 0xFFFu] + (where[w] >> 12)] = ent[w];
+    }
 }
 
 // 1..255, monotone in len: the task planner's length key (see msm_plan_* below)
@@ -331,44 +372,12 @@ __device__ __forceinline__ uint32_t wave_rank_add(uint32_t* counters, uint32_t k
     return r;
 }
 
-template <class E>
-__global__ __launch_bounds__(1024) void presort_bins(const E* __restrict__ entries, const uint32_t* __restrict__ bin_start,
-                                                       uint32_t lo_bits, uint32_t idx_bits, uint32_t* __restrict__ vals_out,
-                                                       uint32_t* __restrict__ bstart, uint32_t* __restrict__ bend,
-                                                       uint32_t lmax, uint32_t* __restrict__ hist,
-                                                       const uint8_t* __restrict__ mask, uint32_t mask_mod) {
-    __shared__ uint32_t sub[1u << PRESORT_MAX_LO];
-    __shared__ uint32_t off[1u << PRESORT_MAX_LO];
-    __shared__ uint32_t wsum[17];
-    __shared__ uint32_t lhist[256];
-    const uint32_t bin = blockIdx.x, SUB = 1u << lo_bits;
-    const uint32_t s = bin_start[bin], e = bin_start[bin + 1];
-    for (uint32_t t = threadIdx.x; t < SUB; t += blockDim.x) sub[t] = 0;
-    for (uint32_t t = threadIdx.x; t < 256; t += blockDim.x) lhist[t] = 0;
-    __syncthreads();
-    // four independent loads in flight per thread (the bin loops are latency-bound otherwise); the trip count is
-    // uniform over the workgroup because the counter updates are wavefront-cooperative
-    const uint32_t stride = 4 * blockDim.x;
-    const uint32_t iters = (e - s + stride - 1) / stride;
-    for (uint32_t it = 0; it < iters; it++) {
-        const uint32_t i = s + threadIdx.x + it * stride;
-        E v[4];
-#pragma unroll
-        for (uint32_t u = 0; u < 4; u++) {
-            const uint32_t j = i + u * blockDim.x;
-            v[u] = j < e ? entries[j] : (E)0;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 4; u++) {
-            bool active = i + u * blockDim.x < e;
-            if (mask && active) {                                                                           // plan variant: pair left out
-                const uint32_t idx = PresortEntry<E>::val(v[u], idx_bits) & 0x7FFFFFFFu;
-                active = mask[mask_mod ? idx % mask_mod : idx] != 0;                                        // (table plans: idx = window * n + i)
-            }
-            (void)wave_rank_add(sub, PresortEntry<E>::lo(v[u], idx_bits), active);
-        }
-    }
-    __syncthreads();
+// the middle of presort_bins: sub[] holds the bin's bucket counts; the buckets' bounds from their exclusive scan (off[t] = start of
+// bucket t, sub[t] = 0: the placement cursor), the task-length histogram.  Returns the entries the bin keeps.  Ends behind a barrier.
+__device__ __forceinline__ uint32_t presort_bins_bounds(uint32_t bin, uint32_t s, uint32_t lo_bits, uint32_t lmax, uint32_t* sub, uint32_t* off,
+                                                        uint32_t* wsum, uint32_t* lhist, uint32_t* __restrict__ bstart,
+                                                        uint32_t* __restrict__ bend, uint32_t* __restrict__ hist) {
+    const uint32_t SUB = 1u << lo_bits;
     // exclusive scan of sub[0..SUB): thread t owns `per` consecutive counters
     const uint32_t per = (SUB + blockDim.x - 1) / blockDim.x, t0 = threadIdx.x * per;
     uint32_t mine = 0, bin_total;
@@ -391,6 +400,99 @@ __global__ __launch_bounds__(1024) void presort_bins(const E* __restrict__ entri
     __syncthreads();
     for (uint32_t t = threadIdx.x; t < 256; t += blockDim.x)
         if (lhist[t]) atomicAdd(&hist[t], lhist[t]);
+    return bin_total;
+}
+
+// STAGED (4-byte entries, WSNARK_PRESORT_STAGE): a bin of at most PRESORT_BINS_CAP entries is read ONCE, into LDS, with the rank the
+// counting pass gave each entry; after the scan the entries are placed in bucket order in a second LDS plane and written to
+// vals_out[s .. s + kept) linearly.  A larger bin (a boolean-heavy witness puts several hundred thousand entries into one) takes the two
+// loops over global memory; the choice is uniform over the workgroup.  48.1 KiB of LDS beside sub / off / lhist: three workgroups per CU.
+static const uint32_t PRESORT_BINS_CAP = 4096;
+static_assert(PRESORT_BINS_CAP < 0xFFFFu, "ranks are kept in 16 bits, 0xFFFF marks a masked entry");
+static_assert(PRESORT_BINS_CAP * (4 + 4 + 2) + (2u << PRESORT_MAX_LO) * 4 + (17 + 256) * 4 <= PRESORT_LDS_BYTES / 3, "staged presort_bins: three workgroups per CU");
+template <class E, bool STAGED>
+__global__ __launch_bounds__(1024) void presort_bins(const E* __restrict__ entries, const uint32_t* __restrict__ bin_start,
+                                                       uint32_t lo_bits, uint32_t idx_bits, uint32_t* __restrict__ vals_out,
+                                                       uint32_t* __restrict__ bstart, uint32_t* __restrict__ bend,
+                                                       uint32_t lmax, uint32_t* __restrict__ hist,
+                                                       const uint8_t* __restrict__ mask, uint32_t mask_mod) {
+    __shared__ uint32_t sub[1u << PRESORT_MAX_LO];
+    __shared__ uint32_t off[1u << PRESORT_MAX_LO];
+    __shared__ uint32_t wsum[17];
+    __shared__ uint32_t lhist[256];
+    const uint32_t bin = blockIdx.x, SUB = 1u << lo_bits;
+    const uint32_t s = bin_start[bin], e = bin_start[bin + 1];
+    for (uint32_t t = threadIdx.x; t < SUB; t += blockDim.x) sub[t] = 0;
+    for (uint32_t t = threadIdx.x; t < 256; t += blockDim.x) lhist[t] = 0;
+    __syncthreads();
+    // four independent loads in flight per thread (the bin loops are latency-bound otherwise); the trip count is
+    // uniform over the workgroup because the counter updates are wavefront-cooperative
+    const uint32_t stride = 4 * blockDim.x;
+    const uint32_t iters = (e - s + stride - 1) / stride;
+    const bool staged = STAGED && e - s <= PRESORT_BINS_CAP;
+    (void)staged;
+    if constexpr (STAGED) {
+        __shared__ uint32_t st_in[PRESORT_BINS_CAP];
+        __shared__ uint32_t st_out[PRESORT_BINS_CAP];
+        __shared__ uint16_t st_rank[PRESORT_BINS_CAP];
+        if (staged) {
+            for (uint32_t it = 0; it < iters; it++) {
+                const uint32_t i = s + threadIdx.x + it * stride;
+                E v[4];
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) {
+                    const uint32_t j = i + u * blockDim.x;
+                    v[u] = j < e ? entries[j] : (E)0;
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) {
+                    const uint32_t j = i + u * blockDim.x;
+                    bool active = j < e;
+                    if (mask && active) {
+                        const uint32_t idx = PresortEntry<E>::val(v[u], idx_bits) & 0x7FFFFFFFu;
+                        active = mask[mask_mod ? idx % mask_mod : idx] != 0;
+                    }
+                    const uint32_t r = wave_rank_add(sub, PresortEntry<E>::lo(v[u], idx_bits), active);
+                    if (j < e) {
+                        st_in[j - s] = (uint32_t)v[u];
+                        st_rank[j - s] = active ? (uint16_t)r : (uint16_t)0xFFFFu;
+                    }
+                }
+            }
+            __syncthreads();
+            const uint32_t kept = presort_bins_bounds(bin, s, lo_bits, lmax, sub, off, wsum, lhist, bstart, bend, hist);
+            for (uint32_t j = threadIdx.x; j < e - s; j += blockDim.x) {
+                const uint32_t r = st_rank[j];
+                if (r != 0xFFFFu) {
+                    const E v = (E)st_in[j];
+                    st_out[off[PresortEntry<E>::lo(v, idx_bits)] - s + r] = PresortEntry<E>::val(v, idx_bits);
+                }
+            }
+            __syncthreads();
+            for (uint32_t j = threadIdx.x; j < kept; j += blockDim.x) vals_out[s + j] = st_out[j];
+            return;
+        }
+    }
+    for (uint32_t it = 0; it < iters; it++) {
+        const uint32_t i = s + threadIdx.x + it * stride;
+        E v[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++) {
+            const uint32_t j = i + u * blockDim.x;
+            v[u] = j < e ? entries[j] : (E)0;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++) {
+            bool active = i + u * blockDim.x < e;
+            if (mask && active) {                                                                           // plan variant: pair left out
+                const uint32_t idx = PresortEntry<E>::val(v[u], idx_bits) & 0x7FFFFFFFu;
+                active = mask[mask_mod ? idx % mask_mod : idx] != 0;                                        // (table plans: idx = window * n + i)
+            }
+            (void)wave_rank_add(sub, PresortEntry<E>::lo(v[u], idx_bits), active);
+        }
+    }
+    __syncthreads();
+    (void)presort_bins_bounds(bin, s, lo_bits, lmax, sub, off, wsum, lhist, bstart, bend, hist);
     for (uint32_t it = 0; it < iters; it++) {
         const uint32_t i = s + threadIdx.x + it * stride;
         E v[4];
@@ -1359,7 +1461,9 @@ int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t 
     uint32_t* d_cnt = S.counters.as<uint32_t>();
     // grouping-pass geometry (swept in rounds 1-2, profiles/r01_sweep_presort_*.txt, r02_sweep_presort_geometry.txt): 1024 scalars per
     // workgroup of 1024 threads, 8 low bucket bits sorted per bin
-    const uint32_t env_lo = 8, env_tile = 1024, env_thr = 1024;
+    uint32_t env_lo = 8;
+    const uint32_t env_tile = 1024, env_thr = 1024;
+    { const long v = tuning_get("MSM_LO_BITS", 0); if (v >= 1 && v <= (long)PRESORT_MAX_LO) env_lo = (uint32_t)v; }   // (tests: the 4096 bins of 7 low bits of a 2^20 table plan, at small sizes)
     const bool env_e64 = tuning_get("MSM_ENTRY64", 0) != 0;      // (tests: the 8-byte grouping entries a 2^24 table key needs, at small sizes)
     uint32_t lo_bits = env_lo > PRESORT_MAX_LO ? PRESORT_MAX_LO : env_lo;
     if (lo_bits > c - 1) lo_bits = c - 1;
@@ -1386,6 +1490,29 @@ int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t 
     (void)d_cnt; (void)hot_min; (void)lmax; (void)nbuckets;
     I.building = true;
     return WS_OK;
+}
+
+// WSNARK_PRESORT_STAGE: 1 (default) = the staged scatter and the staged per-bin sort for 4-byte entries, 0 = neither; 2 / 3 = the scatter /
+// the per-bin sort alone (measurements)
+static bool presort_stage_scatter() { const long v = tuning_get("PRESORT_STAGE", 1); return v == 1 || v == 2; }
+static bool presort_stage_bins() { const long v = tuning_get("PRESORT_STAGE", 1); return v == 1 || v == 3; }
+
+// the per-bin sort of a plan (mask: of its variant)
+static void launch_presort_bins(const MsmPlanInfo& I, uint32_t bthr, const MsmScratch& src, const uint32_t* bin_start, MsmScratch& S, uint32_t* hist,
+                                const uint8_t* mask, uint32_t mask_mod, hipStream_t s) {
+    const dim3 grid(I.ps_nbins), blk(bthr);
+    uint32_t* vals = S.vals_out.as<uint32_t>();
+    uint32_t* bs = S.bstart.as<uint32_t>();
+    uint32_t* be = S.bend.as<uint32_t>();
+    if (I.ps_e32 && presort_stage_bins())
+        hipLaunchKernelGGL((presort_bins<uint32_t, true>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, I.ps_lo_bits, I.ps_idx_bits, vals, bs, be,
+                           I.lmax, hist, mask, mask_mod);
+    else if (I.ps_e32)
+        hipLaunchKernelGGL((presort_bins<uint32_t, false>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, I.ps_lo_bits, I.ps_idx_bits, vals, bs, be,
+                           I.lmax, hist, mask, mask_mod);
+    else
+        hipLaunchKernelGGL((presort_bins<uint64_t, false>), grid, blk, 0, s, src.entries.as<uint64_t>(), bin_start, I.ps_lo_bits, I.ps_idx_bits, vals, bs, be,
+                           I.lmax, hist, mask, mask_mod);
 }
 
 static PresortArgs plan_presort_args(const MsmPlanInfo& I, const Fe* d_scalars, uint32_t i0, uint32_t i_end) {
@@ -1429,7 +1556,7 @@ int msm_plan_finish(Lane& L, const Fe* d_scalars, hipStream_t s) {
     const uint32_t nbuckets = I.nbuckets, lmax = I.lmax, hot_min = I.hot_min;
     uint32_t* d_cnt = S.counters.as<uint32_t>();
     if (I.ps_valid) {
-        const uint32_t nbins = I.ps_nbins, lo_bits = I.ps_lo_bits, idx_bits = I.ps_idx_bits;
+        const uint32_t nbins = I.ps_nbins;
         const bool e32 = I.ps_e32;
         uint32_t* bin_count = d_cnt + CNT_BINS;
         uint32_t* bin_start = bin_count + (nbins + 1);
@@ -1443,22 +1570,18 @@ int msm_plan_finish(Lane& L, const Fe* d_scalars, hipStream_t s) {
             T.end(s);
         }
         T.begin("msm_presort_scatter", s);
-        if (once && e32) hipLaunchKernelGGL(presort_scatter_once<uint32_t>, grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint32_t>());
-        else if (once) hipLaunchKernelGGL(presort_scatter_once<uint64_t>, grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint64_t>());
+        if (once && e32 && presort_stage_scatter())
+            hipLaunchKernelGGL((presort_scatter_once<uint32_t, true>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint32_t>());
+        else if (once && e32) hipLaunchKernelGGL((presort_scatter_once<uint32_t, false>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint32_t>());
+        else if (once) hipLaunchKernelGGL((presort_scatter_once<uint64_t, false>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint64_t>());
         else if (e32) hipLaunchKernelGGL(presort_scatter<uint32_t>, grid, blk, 0, s, PA, bin_cursor, S.entries.as<uint32_t>());
         else hipLaunchKernelGGL(presort_scatter<uint64_t>, grid, blk, 0, s, PA, bin_cursor, S.entries.as<uint64_t>());
         T.end(s);
         // one workgroup per bin, about eight entries per thread (two rounds of four loads in flight)
         uint32_t bthr = (uint32_t)((total / nbins / 8 + 63) / 64 * 64);
         bthr = bthr < 64 ? 64 : bthr > 1024 ? 1024 : bthr;
-        const dim3 bblk(bthr);
         T.begin("msm_presort_bins", s);
-        if (e32)
-            hipLaunchKernelGGL(presort_bins<uint32_t>, dim3(nbins), bblk, 0, s, S.entries.as<uint32_t>(), bin_start, lo_bits,
-                               idx_bits, S.vals_out.as<uint32_t>(), S.bstart.as<uint32_t>(), S.bend.as<uint32_t>(), lmax, d_cnt + CNT_HIST, nullptr, 0u);
-        else
-            hipLaunchKernelGGL(presort_bins<uint64_t>, dim3(nbins), bblk, 0, s, S.entries.as<uint64_t>(), bin_start, lo_bits,
-                               idx_bits, S.vals_out.as<uint32_t>(), S.bstart.as<uint32_t>(), S.bend.as<uint32_t>(), lmax, d_cnt + CNT_HIST, nullptr, 0u);
+        launch_presort_bins(I, bthr, S, bin_start, S, d_cnt + CNT_HIST, nullptr, 0u, s);
         T.end(s);
         WS_HIP_CHECK(hipGetLastError());
         I.ps_bthr = bthr;
@@ -1519,14 +1642,7 @@ int msm_plan_variant(Lane& L, int src_id, int dst_id, const uint8_t* d_mask, hip
     const uint32_t* bin_start = SS.counters.as<uint32_t>() + CNT_BINS + (src.ps_nbins + 1);
     KernelTimer& T = X->timer;
     T.begin("msm_presort_bins", s);
-    if (src.ps_e32)
-        hipLaunchKernelGGL(presort_bins<uint32_t>, dim3(src.ps_nbins), dim3(src.ps_bthr), 0, s, SS.entries.as<uint32_t>(), bin_start,
-                           src.ps_lo_bits, src.ps_idx_bits, S.vals_out.as<uint32_t>(), S.bstart.as<uint32_t>(), S.bend.as<uint32_t>(),
-                           src.lmax, d_cnt + CNT_HIST, d_mask, src.flat ? (uint32_t)src.n : 0u);
-    else
-        hipLaunchKernelGGL(presort_bins<uint64_t>, dim3(src.ps_nbins), dim3(src.ps_bthr), 0, s, SS.entries.as<uint64_t>(), bin_start,
-                           src.ps_lo_bits, src.ps_idx_bits, S.vals_out.as<uint32_t>(), S.bstart.as<uint32_t>(), S.bend.as<uint32_t>(),
-                           src.lmax, d_cnt + CNT_HIST, d_mask, src.flat ? (uint32_t)src.n : 0u);
+    launch_presort_bins(src, src.ps_bthr, SS, bin_start, S, d_cnt + CNT_HIST, d_mask, src.flat ? (uint32_t)src.n : 0u, s);
     T.end(s);
     T.begin("msm_plan", s);
     hipLaunchKernelGGL(msm_plan_emit, dim3(ceil_div_u64(src.nbuckets, 256)), dim3(256), 0, s, S.bstart.as<uint32_t>(),
