@@ -549,6 +549,62 @@ int wsnark_circuit_witness_check_batch(wsnark_circuit_res_t* h, const void* witn
 int wsnark_circuit_witness_check_batch_dev(wsnark_circuit_res_t* h, const void* d_witnesses, size_t witness_stride, uint64_t count,
                                            wsnark_witness_verdict_t* verdicts_host, uint64_t* bad_rows_host, void* bad_values_host,
                                            uint64_t cap, wsnark_witness_batch_report_t* rep, void* stream);
+/* ---- circuits in ROW form: column streams and the resident CSR from constraints (csrc/circuitrows.hip) ----
+ * wsnark_circuit_t holds a circuit in the proving key's own column form, which only a key (A and B) or wasmsnark_amd/synth.py emits.
+ * Every front end produces constraints row by row: this is the way in.  A matrix is CSR over the constraints as given.
+ *   wsnark_circuit_from_rows_size   host work only (no wsnark_init needed): *domain and lens[M] = 4 * n_vars + 36 * (nnz_M [+ n_public
+ *                                 + 1 for A with WSNARK_ROWS_PUBLIC_ROWS]).  Records are kept as given -- nothing is merged or dropped.
+ *   wsnark_circuit_from_rows      the three record streams of wsnark_circuit_t.  THE CONTRACT, byte for byte: for every signal in index
+ *                                 order `u32 ncoefs`, then its records (u32 row, 32 B coefficient) with ASCENDING row; equal rows (a
+ *                                 signal listed twice in one constraint) keep the order in which the input lists them.  The coefficient
+ *                                 is (c mod r) R mod r, canonical; a coefficient that is 0 mod r stays as a record with zero bytes.
+ *                                 Nothing in the output depends on launch geometry, tile size or the arrival order of atomics.
+ *   the scheme                    entries go up through the staging ring; per matrix a STABLE least-significant-digit radix sort of
+ *                                 (signal, entry index) pairs by signal, 6 bits per pass and as many passes as n_vars has bits / 6:
+ *                                 a pass ranks a tile's entries in LDS (one run of consecutive entries per lane, counters per (digit,
+ *                                 lane), one scan in digit-major order) and adds the scanned per-(digit, tile) bases.  No order comes
+ *                                 from an atomic, and a column with 10^6 records costs what 10^6 columns with one record cost.  The
+ *                                 emit stages 256 sorted records of 9 words in LDS and stores them with 32-bit stores in output order;
+ *                                 a signal's header comes from two binary searches in the sorted pairs (the position IS the offset).
+ *                                 ROWS_TILE (wsnark_tuning_set or WSNARK_ROWS_TILE, read per call): entries per tile, a multiple of
+ *                                 256 in [256, 4096], default 2048; any other value is WSNARK_ERR_ARG.  No byte depends on it.
+ *   wsnark_circuit_load_rows      the handle wsnark_circuit_load returns, built directly: row_ptr / col / coef go up, one kernel puts
+ *                                 the coefficients into the resident form (c R^2) and appends the public rows; no transposition.  Every
+ *                                 wsnark_circuit_witness_check* and wsnark_circuit_info result on it is field for field that of the
+ *                                 handle loaded from the streams wsnark_circuit_from_rows writes.
+ *   rep                           nnz: records written per matrix (the public rows included); unreduced: input coefficients >= r;
+ *                                 zero: input coefficients that reduce to 0; empty_signals: signals without a record; max_column: the
+ *                                 longest column; ms: upload, kernels, download, whole call, by the host clock between waits for
+ *                                 the queue (whole call: with the one device allocation the call makes and frees; the download goes
+ *                                 into the caller's memory as it is, pageable or pinned).
+ *   errors      nothing is written on any of them, the report is left untouched: a NULL struct, array or output WSNARK_ERR_ARG (also
+ *               unknown flag bits); n_public + 1 > n_vars, row_ptr[0] != 0 or decreasing, a col >= n_vars WSNARK_ERR_FORMAT (the last
+ *               one found on the device by a min-reduction: wsnark_last_error names the matrix and the smallest entry index); a domain
+ *               that is no power of two, below the total rows or outside [2, 2^24], a matrix of 2^32 records or more, n_vars > 2^30, a
+ *               capacity below lens[M] WSNARK_ERR_SIZE; before wsnark_init WSNARK_ERR_NOINIT.
+ *   threads     each call takes one lane; scratch belongs to the call.
+ *   Out of scope: readers of .r1cs / .wtns / snarkjs JSON files (a front end packs its constraints into wsnark_rows_t:
+ *   wasmsnark_amd/formats.py rows_from_constraints); merging repeated signals of a row; group (multi-GPU) handles; no other entry
+ *   point changes. */
+typedef struct {                      /* one matrix, CSR over the constraints as given */
+    const uint64_t* row_ptr;          /* n_constraints + 1 entries, row_ptr[0] == 0, non-decreasing */
+    const uint32_t* col;              /* row_ptr[n_constraints] signal indices */
+    const void*     coef;             /* as many x 32 B, PLAIN little-endian, any 256-bit value: reduced mod r */
+} wsnark_rows_matrix_t;
+typedef struct {
+    uint32_t n_vars, n_public, n_constraints;
+    uint32_t domain;                  /* 0 = the smallest power of two >= max(total rows, 2); else a power of two >= total rows */
+    wsnark_rows_matrix_t A, B, C;
+} wsnark_rows_t;
+#define WSNARK_ROWS_PUBLIC_ROWS 1u    /* append the nPublic + 1 input-binding rows: row n_constraints + i of A = {signal i: 1}, B and C empty */
+typedef struct {
+    uint64_t nnz[3], unreduced[3], zero[3], empty_signals[3], max_column[3];
+    double   ms[4];                   /* upload, kernels, download, whole call */
+} wsnark_rows_report_t;
+int wsnark_circuit_from_rows_size(const wsnark_rows_t* rows, uint32_t flags, uint32_t* domain, uint64_t lens[3]);
+int wsnark_circuit_from_rows(const wsnark_rows_t* rows, uint32_t flags, void* out_polsA, uint64_t capA, void* out_polsB, uint64_t capB,
+                             void* out_polsC, uint64_t capC, uint32_t* domain, wsnark_rows_report_t* rep);
+int wsnark_circuit_load_rows(const wsnark_rows_t* rows, uint32_t flags, wsnark_circuit_res_t** out_handle);
 /* ---- powers of tau: contribute to a transcript, audit one (csrc/pwtau.hip; snarkjs: `powersoftau contribute` / `powersoftau verify`) ----
  * Phase 1 itself: the transcript wsnark_pkey_setup builds a key on.  A contribution by secrets t, a, b (non-zero mod r) turns the
  * transcript of (tau, alpha, beta) into the one of (t tau, a alpha, b beta):

@@ -192,6 +192,61 @@ def _circuit_struct(circuit):
     return cs, keep
 
 
+class _RowsMatrix(C.Structure):    # wsnark_rows_matrix_t
+    _fields_ = [("row_ptr", C.c_void_p), ("col", C.c_void_p), ("coef", C.c_void_p)]
+
+
+class _Rows(C.Structure):          # wsnark_rows_t
+    _fields_ = [("n_vars", C.c_uint32), ("n_public", C.c_uint32), ("n_constraints", C.c_uint32), ("domain", C.c_uint32),
+                ("A", _RowsMatrix), ("B", _RowsMatrix), ("C", _RowsMatrix)]
+
+
+class _RowsReport(C.Structure):    # wsnark_rows_report_t
+    _fields_ = [("nnz", C.c_uint64 * 3), ("unreduced", C.c_uint64 * 3), ("zero", C.c_uint64 * 3), ("empty_signals", C.c_uint64 * 3),
+                ("max_column", C.c_uint64 * 3), ("ms", C.c_double * 4)]
+
+
+ROWS_PUBLIC_ROWS = 1               # WSNARK_ROWS_PUBLIC_ROWS
+
+
+def _ro_buffer(b):
+    """_ro for anything with the buffer protocol (numpy arrays): C-contiguous, borrowed where it is writable, else copied"""
+    if isinstance(b, (bytes, bytearray)):
+        return _ro(b)
+    mv = memoryview(b)
+    if not mv.c_contiguous:
+        raise ValueError("expected a C-contiguous buffer")
+    if mv.nbytes == 0:
+        return C.c_char_p(b"\0"), 0
+    if mv.readonly:
+        return _ro(mv.tobytes())
+    return (C.c_uint8 * mv.nbytes).from_buffer(mv.cast("B")), mv.nbytes
+
+
+def _rows_struct(rows):
+    """wsnark_rows_t over the caller's buffers, their lengths checked against n_constraints and row_ptr's last entry (the C side has
+    only the pointers)"""
+    nc = int(rows["n_constraints"])
+    rs, keep = _Rows(rows["n_vars"], rows["n_public"], nc, int(rows.get("domain") or 0)), []
+    for name in ("A", "B", "C"):
+        row_ptr, col, coef = rows[name]
+        (rp, n_rp), (cl, n_cl), (cf, n_cf) = _ro_buffer(row_ptr), _ro_buffer(col), _ro_buffer(coef)
+        if n_rp != 8 * (nc + 1):
+            raise ValueError("rows[%r]: row_ptr must hold n_constraints + 1 u64 entries" % name)
+        nnz = int.from_bytes(memoryview(row_ptr).cast("B")[8 * nc:8 * nc + 8], "little")
+        if n_cl != 4 * nnz or n_cf != 32 * nnz:
+            raise ValueError("rows[%r]: col must hold row_ptr[n_constraints] u32 entries and coef as many x 32 bytes" % name)
+        keep += [rp, cl, cf]
+        setattr(rs, name, _RowsMatrix(C.cast(rp, C.c_void_p), C.cast(cl, C.c_void_p), C.cast(cf, C.c_void_p)))
+    return rs, keep
+
+
+def _rows_report_dict(r):
+    return {"nnz": tuple(int(x) for x in r.nnz), "unreduced": tuple(int(x) for x in r.unreduced), "zero": tuple(int(x) for x in r.zero),
+            "empty_signals": tuple(int(x) for x in r.empty_signals), "max_column": tuple(int(x) for x in r.max_column),
+            "ms": {"upload": r.ms[0], "kernels": r.ms[1], "download": r.ms[2], "total": r.ms[3]}}
+
+
 DELTA_CHECKS = ("unchanged", "delta1~delta2", "C", "H", "delta_changed")    # bits 0..4 of wsnark_pkey_delta_verdict_t
 
 
@@ -368,11 +423,17 @@ class ResidentCircuit:
     """A circuit's three matrices resident on the device as row-major CSR (wsnark_circuit_load): witnesses are checked against it
     without transposing the record streams again.  Read-only after the load: threads may share one."""
 
-    def __init__(self, lib, circuit):
+    def __init__(self, lib, circuit=None, rows=None, public_rows=True):
+        if (circuit is None) == (rows is None):
+            raise ValueError("load_circuit: exactly one of circuit, rows")
         self._lib = lib
         self._h = C.c_void_p()
-        cs, keep = _circuit_struct(circuit)
-        lib.check(lib.c.wsnark_circuit_load(C.byref(cs), C.byref(self._h)))
+        if rows is not None:      # wsnark_circuit_load_rows: the CSR built directly, no transposition
+            rs, keep = _rows_struct(rows)
+            lib.check(lib.c.wsnark_circuit_load_rows(C.byref(rs), ROWS_PUBLIC_ROWS if public_rows else 0, C.byref(self._h)))
+        else:
+            cs, keep = _circuit_struct(circuit)
+            lib.check(lib.c.wsnark_circuit_load(C.byref(cs), C.byref(self._h)))
         inf = self.info()
         self.n_vars, self.n_public, self.domain = inf["n_vars"], inf["n_public"], inf["domain"]
 
@@ -1218,11 +1279,36 @@ class Bn128:
         return bytes(pub)[:size], bytes(prv)[:size]
 
     # --- a witness against its circuit (csrc/witcheck.hip; no reference counterpart -- snarkjs: wtns check) ---
-    def load_circuit(self, circuit):
-        """circuit: the dict of setup_key ({"n_vars", "n_public", "domain", "polsA", "polsB", "polsC"}).  Returns a ResidentCircuit:
+    def load_circuit(self, circuit=None, rows=None, public_rows=True):
+        """circuit: the dict of setup_key ({"n_vars", "n_public", "domain", "polsA", "polsB", "polsC"}); or rows=: the circuit row by
+        row, the dict of circuit_from_rows (wsnark_circuit_load_rows: the same handle without a transposition).  Returns a ResidentCircuit:
         .check_witness(witness, max_rows=16), .check_witness_dev(d_witness, witness_len, max_rows=16, stream=None), .check_witnesses(witnesses,
         max_rows=16, report=None), .check_witnesses_dev(d_witnesses, witness_stride, count, ...), .info(), .free()."""
-        return ResidentCircuit(self.lib, circuit)
+        return ResidentCircuit(self.lib, circuit, rows=rows, public_rows=public_rows)
+
+    # --- a circuit given row by row (csrc/circuitrows.hip; no reference counterpart) ---
+    def circuit_from_rows(self, rows, public_rows=True, report=None):
+        """The circuit dict of setup_key, check_key_circuit, circuit_row_sums and load_circuit from constraints given ROW BY ROW
+        (wsnark_circuit_from_rows).  rows: {"n_vars", "n_public", "n_constraints", "domain" (optional: the smallest power of two that
+        holds every row), "A", "B", "C"}, each matrix (row_ptr, col, coef) as buffers (bytes or numpy arrays): row_ptr n_constraints + 1
+        u64, col u32 signal indices, coef 32 bytes plain little-endian each, any 256-bit value (formats.rows_from_constraints packs
+        them).  public_rows: append the nPublic + 1 input-binding rows old snarkjs and synth.make_circuit use.  Every signal's records
+        come out with ascending row, a signal listed twice in a row in the input's order; nothing is merged or dropped.  report: a
+        dict that receives {nnz, unreduced, zero, empty_signals, max_column: (A, B, C), ms}."""
+        rs, keep = _rows_struct(rows)
+        flags = ROWS_PUBLIC_ROWS if public_rows else 0
+        dom, lens = C.c_uint32(), (C.c_uint64 * 3)()
+        self.lib.check(self.lib.c.wsnark_circuit_from_rows_size(C.byref(rs), flags, C.byref(dom), lens))
+        out = [bytearray(max(int(n), 1)) for n in lens]
+        ptr = [(C.c_uint8 * len(b)).from_buffer(b) for b in out]
+        rep = _RowsReport()
+        self.lib.check(self.lib.c.wsnark_circuit_from_rows(C.byref(rs), flags, ptr[0], lens[0], ptr[1], lens[1], ptr[2], lens[2],
+                                                          C.byref(dom), C.byref(rep)))
+        if report is not None:
+            report.update(_rows_report_dict(rep))
+        del ptr
+        return {"n_vars": rows["n_vars"], "n_public": rows["n_public"], "domain": dom.value,
+                "polsA": bytes(out[0][:lens[0]]), "polsB": bytes(out[1][:lens[1]]), "polsC": bytes(out[2][:lens[2]])}
 
     def check_witness(self, circuit, witness, max_rows=16):
         """Load, check and free in one call (wsnark_witness_check): ResidentCircuit.check_witness's report and lists, with the

@@ -19,6 +19,7 @@ static_assert(sizeof(wsnark_pkey_circuit_verdict_t) == 56, "the bindings read th
 static_assert(sizeof(wsnark_witness_report_t) == 80, "the bindings read this by offset");
 static_assert(sizeof(wsnark_witness_verdict_t) == 48 && sizeof(wsnark_witness_batch_report_t) == 64, "the bindings read these by offset");
 static_assert(sizeof(wsnark_prove_batch_report_t) == 64, "the bindings read this by offset");
+static_assert(sizeof(wsnark_rows_report_t) == 152 && sizeof(wsnark_rows_matrix_t) == 24 && sizeof(wsnark_rows_t) == 88, "the bindings read these by offset");
 
 // HIP's current device is per host thread (default 0) and every entry point may be called from any thread (the Node
 // addon runs on the libuv pool): select the context's device first.
@@ -533,6 +534,26 @@ int wsnark_circuit_witness_check_batch_dev(wsnark_circuit_res_t* h, const void* 
     CtxScope scope(circuit_context(reinterpret_cast<const CircuitRes*>(h)));
     return circuit_witness_check_batch(reinterpret_cast<CircuitRes*>(h), d_witnesses, witness_stride, count, true, verdicts_host, bad_rows_host,
                                        bad_values_host, cap, rep, (hipStream_t)stream);
+}
+// ---- a circuit in row form (circuitrows.hip) ----
+int wsnark_circuit_from_rows_size(const wsnark_rows_t* rows, uint32_t flags, uint32_t* domain, uint64_t lens[3]) {
+    return circuit_from_rows_size(rows, flags, domain, lens);
+}
+int wsnark_circuit_from_rows(const wsnark_rows_t* rows, uint32_t flags, void* out_polsA, uint64_t capA, void* out_polsB, uint64_t capB,
+                             void* out_polsC, uint64_t capC, uint32_t* domain, wsnark_rows_report_t* rep) {
+    REQUIRE_CTX();
+    void* const out[3] = {out_polsA, out_polsB, out_polsC};
+    const uint64_t cap[3] = {capA, capB, capC};
+    return circuit_from_rows(rows, flags, out, cap, domain, rep);
+}
+int wsnark_circuit_load_rows(const wsnark_rows_t* rows, uint32_t flags, wsnark_circuit_res_t** out_handle) {
+    REQUIRE_CTX();
+    if (!out_handle) return WSNARK_ERR_ARG;
+    CircuitRes* H = nullptr;
+    int rc = circuit_load_rows(rows, flags, &H);
+    if (rc) return rc;
+    *out_handle = reinterpret_cast<wsnark_circuit_res_t*>(H);
+    return WSNARK_OK;
 }
 int wsnark_pkey_shard_info(const wsnark_pkey_t* h, uint32_t* rank, uint32_t* world, uint64_t* first_signal, uint64_t* n_signals,
                            uint64_t* n_hexps, uint32_t* h_interleave_log) {

@@ -241,6 +241,16 @@ __global__ __launch_bounds__(256) void csr_fill_kernel(const uint8_t* __restrict
     coef[k] = Fr::to_mont(c);
 }
 
+int scan_exclusive_dev(const uint32_t* d_in, uint32_t n, uint32_t* d_tiles, uint32_t* d_out, uint32_t* d_cursor, hipStream_t s) {
+    if (n == 0) return WS_OK;
+    const uint32_t ntiles = ceil_div_u64(n, 1024);
+    hipLaunchKernelGGL(scan_tile_sums, dim3(ntiles), dim3(256), 0, s, d_in, n, d_tiles);
+    hipLaunchKernelGGL(scan_tile_bases, dim3(1), dim3(256), 0, s, d_tiles, ntiles);
+    hipLaunchKernelGGL(scan_tiles, dim3(ntiles), dim3(256), 0, s, d_in, n, d_tiles, d_out, d_cursor);
+    WS_HIP_CHECK(hipGetLastError());
+    return WS_OK;
+}
+
 struct SlabPiece {      // a part of one device allocation, with DevBuf's accessor
     void* p = nullptr;
     template <class T> T* as() const { return (T*)p; }
@@ -320,22 +330,35 @@ int pols_to_csr(const uint8_t* pols, size_t len, uint32_t n_signals, uint32_t do
     if ((rc = upload_staged(d_base.p, rec_base.data(), rec_base.size() * 4, s))) return rc;
     WS_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, ((size_t)domain + 1) * 4, s));
     WS_HIP_CHECK(hipMemsetAsync(d_bad.p, 0, 4, s));
+    // (per-kernel times for wsnark_timing_enable: the yardstick of the opposite transposition, circuitrows.hip)
+    struct Bracket {
+        Context* X;
+        hipStream_t q;
+        void begin(const char* name) { if (X) X->timer.begin(name, q); }
+        void end() { if (X) X->timer.end(q); }
+    } T{ctx(), s};
+    T.begin("csr_count");
     if (nnz)
         hipLaunchKernelGGL(csr_count_kernel, dim3(ceil_div_u64(nnz, 256)), dim3(256), 0, s, d_blob.as<uint8_t>(), d_start.as<uint64_t>(), d_base.as<uint32_t>(),
                            n_signals, (uint32_t)nnz, domain, d_sig.as<uint32_t>(), d_row.as<uint32_t>(), d_cnt.as<uint32_t>(), d_bad.as<uint32_t>());
+    T.end();
     // (domain + 1 counters, the last one zero: the exclusive scan's last entry is the total, i.e. row_ptr[domain])
+    T.begin("csr_scan");
     hipLaunchKernelGGL(scan_tile_sums, dim3(ntiles), dim3(256), 0, s, d_cnt.as<uint32_t>(), domain + 1, d_tiles.as<uint32_t>());
     hipLaunchKernelGGL(scan_tile_bases, dim3(1), dim3(256), 0, s, d_tiles.as<uint32_t>(), ntiles);
     hipLaunchKernelGGL(scan_tiles, dim3(ntiles), dim3(256), 0, s, d_cnt.as<uint32_t>(), domain + 1, d_tiles.as<uint32_t>(), out->row_ptr.as<uint32_t>(), d_cursor.as<uint32_t>());
+    T.end();
     WS_HIP_CHECK(hipGetLastError());
     uint32_t bad = 0;
     WS_HIP_CHECK(hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, s));
     WS_HIP_CHECK(hipStreamSynchronize(s));
     at("records uploaded, counted, scanned");
     if (bad) { set_last_error("pols: coefficient index >= domainSize"); return WS_ERR_FORMAT; }
+    T.begin("csr_fill");
     if (nnz)
         hipLaunchKernelGGL(csr_fill_kernel, dim3(ceil_div_u64(nnz, 256)), dim3(256), 0, s, d_blob.as<uint8_t>(), d_start.as<uint64_t>(), d_base.as<uint32_t>(),
                            (uint32_t)nnz, d_sig.as<uint32_t>(), d_row.as<uint32_t>(), d_cursor.as<uint32_t>(), out->col.as<uint32_t>(), out->coef.as<Fe>());
+    T.end();
     WS_HIP_CHECK(hipGetLastError());
     WS_HIP_CHECK(hipStreamSynchronize(s));
     at("filled");

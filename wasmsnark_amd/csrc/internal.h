@@ -321,6 +321,9 @@ struct CsrMatrix {            // row-major transpose of the reference's column-m
 // release: see KeySections::release (nullptr: the records are walked, then uploaded in one piece)
 int pols_to_csr(const uint8_t* pols, size_t len, uint32_t n_signals, uint32_t domain, CsrMatrix* out,
                 size_t* consumed, hipStream_t s, void (*release)(const void* p, size_t n) = nullptr);
+// exclusive scan of n u32 counters on queue s (the three kernels of pols_to_csr, tiles of 1024): out[i] = cursor[i] = in[0] + .. + in[i - 1];
+// d_tiles: ceil(n / 1024) words of scratch
+int scan_exclusive_dev(const uint32_t* d_in, uint32_t n, uint32_t* d_tiles, uint32_t* d_out, uint32_t* d_cursor, hipStream_t s);
 // d_h_out[domain] (plain form) from a device-resident plain witness; work arrays of lane L
 int calc_h_dev(Lane& L, const Fe* d_signals_plain, uint32_t n_signals, const CsrMatrix& A, const CsrMatrix& B,
                uint32_t domain, Fe* d_h_out, hipStream_t s);

@@ -251,7 +251,12 @@ int circuit_shape_check(const wsnark_circuit_t* K);
 int circuit_to_csr(const wsnark_circuit_t* K, CsrMatrix M[3], hipStream_t s);
 // a witness against its circuit (witcheck.hip): a circuit's three matrices resident as row-major CSR; which rows fail for a witness on
 // the host or (on_device) already resident, on queue s (nullptr: the lane's own)
-struct CircuitRes;
+struct CircuitRes {
+    Context* owner = nullptr;
+    uint32_t n_vars = 0, n_public = 0, domain = 0;
+    CsrMatrix M[3];
+    double load_ms = 0;
+};
 Context* circuit_context(const CircuitRes* H);
 int circuit_load(const wsnark_circuit_t* K, CircuitRes** out);
 void circuit_free(CircuitRes* H);
@@ -264,6 +269,10 @@ int witness_check(const wsnark_circuit_t* K, const void* witness, size_t witness
 int circuit_witness_check_batch(CircuitRes* H, const void* witnesses, size_t witness_stride, uint64_t count, bool on_device,
                                 wsnark_witness_verdict_t* verdicts, uint64_t* bad_rows, void* bad_values, uint64_t cap,
                                 wsnark_witness_batch_report_t* rep, hipStream_t stream);
+// a circuit in row form (circuitrows.hip): the sizes, the three record streams, the resident handle built directly
+int circuit_from_rows_size(const wsnark_rows_t* R, uint32_t flags, uint32_t* domain, uint64_t lens[3]);
+int circuit_from_rows(const wsnark_rows_t* R, uint32_t flags, void* const out[3], const uint64_t cap[3], uint32_t* domain, wsnark_rows_report_t* rep);
+int circuit_load_rows(const wsnark_rows_t* R, uint32_t flags, CircuitRes** out);
 // the audit's per-point kernels on device-resident points in reference format (pkeycheck.hip): counts into d_acc with the global index
 // base + i; the G2 one with the order-r subgroup test (PKCHECK_SUBGROUP picks its form), d_K: the pairing constants on the device
 int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s);

@@ -197,12 +197,6 @@ __global__ __launch_bounds__(256) void lc_row_values_batch_kernel(CheckTriple M,
 }
 
 // ---- host ----
-struct CircuitRes {
-    Context* owner = nullptr;
-    uint32_t n_vars = 0, n_public = 0, domain = 0;
-    CsrMatrix M[3];
-    double load_ms = 0;
-};
 Context* circuit_context(const CircuitRes* H) { return H ? H->owner : nullptr; }
 
 int circuit_load(const wsnark_circuit_t* K, CircuitRes** out) {

@@ -57,6 +57,26 @@ def _le32(v: int) -> bytes:
     return (v & ((1 << 256) - 1)).to_bytes(32, "little")
 
 
+def rows_from_constraints(constraints, n_vars, n_public):
+    """Constraints as a front end holds them -- a list of (A, B, C), each a dict {signal: coefficient} or a list of (signal,
+    coefficient) pairs -- packed into the `rows` dict of Bn128.circuit_from_rows / load_circuit(rows=...) (wsnark_rows_t): per matrix
+    row_ptr (u64), col (u32) and coef (32 bytes plain little-endian) as bytes.  Format-agnostic on purpose: there is no reader of
+    .r1cs, .wtns or snarkjs' JSON export here; whatever parses those hands its constraints to this.  Terms keep their order;
+    coefficients are taken mod 2^256 when non-negative (the device reduces them mod r) and mod r when negative."""
+    out = {"n_vars": int(n_vars), "n_public": int(n_public), "n_constraints": len(constraints)}
+    for k, name in enumerate("ABC"):
+        row_ptr, col, coef = [0], [], bytearray()
+        for cons in constraints:
+            terms = cons[k].items() if hasattr(cons[k], "items") else cons[k]
+            for sig, c in terms:
+                c = _int(c) if not isinstance(c, int) else c
+                col.append(int(sig))
+                coef += _le32(c % R if c < 0 else c)
+            row_ptr.append(len(col))
+        out[name] = (struct.pack("<%dQ" % len(row_ptr), *row_ptr), struct.pack("<%dI" % len(col), *col), bytes(coef))
+    return out
+
+
 def _mont_q(v) -> bytes:
     return _le32(_int(v) * _MONT % Q)
 

@@ -110,6 +110,18 @@ function deltaVerdict(ab) {
 }
 /* wsnark_pkey_circuit_verdict_t (56 bytes) -> the object of checkKeyCircuit() */
 const CIRCUIT_CHECKS = ["shape_and_streams", "fixed_points", "delta1~delta2", "A", "B1", "B2", "C", "H", "vk_fixed_points", "IC"];
+/* the addon's arguments for a circuit in row form: the counts, the flags (bit 0: append the public rows) and the nine arrays */
+function rowsArgs(rows, publicRows) {
+    const bufs = [];
+    for (const name of ["A", "B", "C"]) {
+        const m = rows[name];
+        if (!m || !(m.rowPtr instanceof BigUint64Array) || !(m.col instanceof Uint32Array))
+            throw new TypeError("wsnark: rows." + name + " must be {rowPtr: BigUint64Array, col: Uint32Array, coef: bytes}");
+        asBytes(m.coef);
+        bufs.push(Buffer.from(m.rowPtr.buffer, m.rowPtr.byteOffset, m.rowPtr.byteLength), Buffer.from(m.col.buffer, m.col.byteOffset, m.col.byteLength), m.coef);
+    }
+    return [rows.nVars, rows.nPublic, rows.nConstraints, rows.domain || 0, publicRows === false ? 0 : 1, bufs];
+}
 function circuitVerdict(ab) {
     const v = new DataView(ab);
     const run = v.getUint32(0, true), bad = v.getUint32(4, true);
@@ -462,12 +474,21 @@ class Bn128 {
      * array of what checkWitness resolves to for each, without rows and ms, which go to opts.report with count, good, firstNotOk, chunk.  Checks on one loaded circuit may run side by side; free() hands the device memory back once those in flight are done
      * (the garbage collector does it otherwise).  Pass the object to groth16GenProof as opts.circuit to have every witness checked
      * before it is proved. */
+    /* loadCircuit({rows, publicRows}): the same object from a circuit given ROW BY ROW (wsnark_circuit_load_rows: the CSR is built
+     * directly, no transposition); rows as circuitFromRows takes them. */
     async loadCircuit(circuit) {
         if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
         if (this._group) throw new Error("wsnark: loadCircuit runs on a single GPU (build a Bn128 without {devices})");
-        const bufs = [circuit.polsA, circuit.polsB, circuit.polsC];
-        bufs.forEach(asBytes);
-        const handle = await addon.loadCircuit(circuit.nVars, circuit.nPublic, circuit.domain, bufs);
+        let handle;
+        if (circuit.rows) {
+            handle = await addon.loadCircuitRows(...rowsArgs(circuit.rows, circuit.publicRows));
+            const inf = addon.circuitInfo(handle);
+            circuit = { nVars: inf.nVars, nPublic: inf.nPublic, domain: inf.domain };
+        } else {
+            const bufs = [circuit.polsA, circuit.polsB, circuit.polsC];
+            bufs.forEach(asBytes);
+            handle = await addon.loadCircuit(circuit.nVars, circuit.nPublic, circuit.domain, bufs);
+        }
         let inflight = 0, freed = false;
         const release = () => { if (freed && inflight === 0) addon.circuitFree(handle); };
         return {
@@ -496,6 +517,25 @@ class Bn128 {
             },
             free() { freed = true; release(); },
         };
+    }
+    /* No counterpart in the reference: the circuit object of newKey(), checkKeyCircuit(), checkWitness() and loadCircuit() --
+     * {nVars, nPublic, domain, polsA, polsB, polsC} -- from constraints given ROW BY ROW (include/wsnark.h: wsnark_circuit_from_rows).
+     * rows: {nVars, nPublic, nConstraints, domain (optional), A, B, C}, each matrix {rowPtr, col, coef}: a BigUint64Array of
+     * nConstraints + 1 entries, a Uint32Array of signal indices and 32 bytes per entry, plain little-endian, any 256-bit value.
+     * opts.publicRows (default true): append the nPublic + 1 input-binding rows.  Every signal's records come out with ascending
+     * row; nothing is merged or dropped.  The object also carries .report: {nnz, unreduced, zero, emptySignals, maxColumn, ms}. */
+    async circuitFromRows(rows, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: circuitFromRows runs on a single GPU (build a Bn128 without {devices})");
+        const ab = await addon.circuitFromRows(...rowsArgs(rows, opts ? opts.publicRows : undefined));
+        const v = new DataView(ab);
+        const lens = [0, 1, 2].map((k) => Number(v.getBigUint64(8 + 8 * k, true)));
+        const triple = (off) => [0, 1, 2].map((k) => Number(v.getBigUint64(32 + off + 8 * k, true)));
+        const report = { nnz: triple(0), unreduced: triple(24), zero: triple(48), emptySignals: triple(72), maxColumn: triple(96),
+                         ms: { upload: v.getFloat64(152, true), kernels: v.getFloat64(160, true), download: v.getFloat64(168, true), total: v.getFloat64(176, true) } };
+        let off = 184;
+        const pols = lens.map((n) => { const b = Buffer.from(ab, off, n); off += n; return b; });
+        return { nVars: rows.nVars, nPublic: rows.nPublic, domain: v.getUint32(0, true), polsA: pols[0], polsB: pols[1], polsC: pols[2], report };
     }
     /* A key FILE -- the reference's proving_key.bin or the WSNARK64 container for keys beyond its 4 GiB (js/formats.js:
      * writeKeyContainer; 2^24 constraints = 7.8 GB, more than one Buffer holds).  The library maps the file and reads only what it makes

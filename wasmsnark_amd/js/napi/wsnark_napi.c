@@ -93,6 +93,10 @@ static struct {
     int (*witness_check)(const void*, const void*, size_t, uint64_t*, void*, uint64_t, void*);
     int (*circuit_witness_check)(wsnark_circuit_res_t*, const void*, size_t, uint64_t*, void*, uint64_t, void*);
     int (*circuit_witness_check_batch)(wsnark_circuit_res_t*, const void*, size_t, uint64_t, void*, uint64_t*, void*, uint64_t, void*);
+    /* a circuit in row form (include/wsnark.h: wsnark_circuit_from_rows_size, wsnark_circuit_from_rows, wsnark_circuit_load_rows) */
+    int (*circuit_from_rows_size)(const void*, uint32_t, uint32_t*, uint64_t*);
+    int (*circuit_from_rows)(const void*, uint32_t, void*, uint64_t, void*, uint64_t, void*, uint64_t, uint32_t*, void*);
+    int (*circuit_load_rows)(const void*, uint32_t, wsnark_circuit_res_t**);
     char dir[4096];
 } L;
 
@@ -142,6 +146,8 @@ static int load_lib(char* err, size_t errlen) {
     SYM(circuit_load, "wsnark_circuit_load") SYM(circuit_free, "wsnark_circuit_free") SYM(circuit_info, "wsnark_circuit_info")
     SYM(witness_check, "wsnark_witness_check") SYM(circuit_witness_check, "wsnark_circuit_witness_check")
     SYM(circuit_witness_check_batch, "wsnark_circuit_witness_check_batch")
+    SYM(circuit_from_rows_size, "wsnark_circuit_from_rows_size") SYM(circuit_from_rows, "wsnark_circuit_from_rows")
+    SYM(circuit_load_rows, "wsnark_circuit_load_rows")
 #undef SYM
     return 0;
 }
@@ -171,7 +177,7 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
        OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
        OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
-       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH };
+       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH, OP_CIRCUIT_FROM_ROWS, OP_CIRCUIT_LOAD_ROWS };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -215,8 +221,8 @@ typedef struct {
     int nrefs;
     uint8_t *a, *b, *c, *r32, *s32;
     size_t na, nb, nc;
-    uint8_t* in[8];             /* OP_NEW_KEY: tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, polsA, polsB, polsC */
-    size_t nin[8];
+    uint8_t* in[9];             /* OP_NEW_KEY: tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, polsA, polsB, polsC; the rows: 3 x (row_ptr, col, coef) */
+    size_t nin[9];
     uint32_t u2;
     uint32_t u0, u1;
     int i0, i1;
@@ -304,6 +310,8 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
 #define WITNESS_REPORT_BYTES 80          /* sizeof(wsnark_witness_report_t) */
 #define WITNESS_VERDICT_BYTES 48         /* sizeof(wsnark_witness_verdict_t) */
 #define WITNESS_BATCH_REPORT_BYTES 64    /* sizeof(wsnark_witness_batch_report_t) */
+#define ROWS_REPORT_BYTES 152            /* sizeof(wsnark_rows_report_t) */
+#define ROWS_HEAD_BYTES (8 + 24 + ROWS_REPORT_BYTES)      /* circuitFromRows: u32 domain, u32 0, lens[3], the report; then the three streams */
 /* wsnark_powers_t and wsnark_circuit_t (include/wsnark.h) */
 typedef struct {
     uint32_t domain;
@@ -319,6 +327,12 @@ typedef struct {
     const void* polsB; uint64_t polsB_len;
     const void* polsC; uint64_t polsC_len;
 } circuit_t;
+/* wsnark_rows_t: the rows' (nVars, nPublic, nConstraints, domain) in u0, u1, i0, u2, flags in i1, the nine arrays in in[0..8] */
+typedef struct { const void *row_ptr, *col, *coef; } rows_matrix_t;
+typedef struct { uint32_t n_vars, n_public, n_constraints, domain; rows_matrix_t M[3]; } rows_t;
+static void job_rows(const job_t* j, rows_t* R) {
+    *R = (rows_t){j->u0, j->u1, (uint32_t)j->i0, j->u2, {{j->in[0], j->in[1], j->in[2]}, {j->in[3], j->in[4], j->in[5]}, {j->in[6], j->in[7], j->in[8]}}};
+}
 static void job_structs(const job_t* j, powers_t* P, circuit_t* K) {
     *P = (powers_t){j->u2, j->in[0], j->nin[0], j->in[1], j->nin[1], j->in[2], j->nin[2], j->in[3], j->nin[3], j->in[4]};
     *K = (circuit_t){j->u0, j->u1, j->u2, j->in[5], j->nin[5], j->in[6], j->nin[6], j->in[7], j->nin[7]};
@@ -400,6 +414,28 @@ static void job_execute(napi_env env, void* data) {
         circuit_t K;
         job_structs(j, &P, &K);
         j->rc = L.circuit_load(&K, &j->circ);
+        break;
+    }
+    case OP_CIRCUIT_FROM_ROWS: {      /* out = ROWS_HEAD_BYTES, then polsA | polsB | polsC at their lengths */
+        rows_t R;
+        uint32_t dom = 0;
+        uint64_t lens[3];
+        job_rows(j, &R);
+        if ((j->rc = L.circuit_from_rows_size(&R, (uint32_t)j->i1, &dom, lens))) break;
+        j->nout = ROWS_HEAD_BYTES + (size_t)(lens[0] + lens[1] + lens[2]);
+        j->out = (uint8_t*)calloc(j->nout, 1);
+        if (!j->out) { j->rc = -1; snprintf(j->err, sizeof j->err, "circuitFromRows: out of memory"); return; }
+        uint8_t* pols = j->out + ROWS_HEAD_BYTES;
+        j->rc = L.circuit_from_rows(&R, (uint32_t)j->i1, pols, lens[0], pols + lens[0], lens[1], pols + lens[0] + lens[1], lens[2], &dom,
+                                    j->out + 8 + 24);
+        memcpy(j->out, &dom, 4);
+        memcpy(j->out + 8, lens, 24);
+        break;
+    }
+    case OP_CIRCUIT_LOAD_ROWS: {
+        rows_t R;
+        job_rows(j, &R);
+        j->rc = L.circuit_load_rows(&R, (uint32_t)j->i1, &j->circ);
         break;
     }
     case OP_WITNESS_CHECK:            /* out = the report (80 B), cap x u64 row indices, cap x 96 B values */
@@ -505,7 +541,7 @@ static void job_complete(napi_env env, napi_status status, void* data) {
     } else if (j->op == OP_POINTS_LOAD) {
         napi_create_external(env, new_handle(TAG_POINTS, j->pts), points_finalize, NULL, &res);
         napi_resolve_deferred(env, j->deferred, res);
-    } else if (j->op == OP_CIRCUIT_LOAD) {
+    } else if (j->op == OP_CIRCUIT_LOAD || j->op == OP_CIRCUIT_LOAD_ROWS) {
         handle_t* h = new_handle(TAG_CIRCUIT, j->circ);
         if (!h || napi_create_external(env, h, circuit_finalize, NULL, &res) != napi_ok) {      /* nothing would ever free the matrices */
             napi_value msg, e;
@@ -927,6 +963,49 @@ static napi_value js_circuit_load(napi_env env, napi_callback_info info) {
     if (argc < 4 || !circuit_args(env, j, argv)) FAIL(env, j, "expected (nVars, nPublic, domain, [polsA, polsB, polsC])");
     keep(env, j, argv[3]);      /* the array keeps its three buffers alive */
     return start_job(env, j, "wsnark_circuit_load");
+}
+/* ---- a circuit in row form (include/wsnark.h: wsnark_circuit_from_rows, wsnark_circuit_load_rows) ----
+ * (nVars, nPublic, nConstraints, domain, flags, [rowPtrA, colA, coefA, rowPtrB, ..., coefC]); the library has only the pointers, so
+ * the arrays' lengths are checked here: row_ptr nConstraints + 1 u64, col row_ptr[nConstraints] u32, coef as many x 32 bytes */
+static int rows_args(napi_env env, job_t* j, napi_value* argv) {
+    napi_value el;
+    bool is = false;
+    uint32_t nc = 0, flags = 0;
+    if (napi_get_value_uint32(env, argv[0], &j->u0) != napi_ok || napi_get_value_uint32(env, argv[1], &j->u1) != napi_ok ||
+        napi_get_value_uint32(env, argv[2], &nc) != napi_ok || nc > 0x7fffffffu || napi_get_value_uint32(env, argv[3], &j->u2) != napi_ok ||
+        napi_get_value_uint32(env, argv[4], &flags) != napi_ok || flags > 0x7fffffffu || napi_is_array(env, argv[5], &is) != napi_ok || !is)
+        return 0;
+    j->i0 = (int)nc; j->i1 = (int)flags;
+    for (uint32_t k = 0; k < 9; k++)
+        if (napi_get_element(env, argv[5], k, &el) != napi_ok || !get_bytes(env, el, &j->in[k], &j->nin[k])) return 0;
+    for (uint32_t m = 0; m < 3; m++) {
+        uint64_t nnz;
+        if (j->nin[3 * m] != 8 * ((size_t)nc + 1) || ((uintptr_t)j->in[3 * m] & 7) || ((uintptr_t)j->in[3 * m + 1] & 3)) return 0;
+        memcpy(&nnz, j->in[3 * m] + 8 * (size_t)nc, 8);
+        if (nnz > ((uint64_t)1 << 32) || j->nin[3 * m + 1] != 4 * nnz || j->nin[3 * m + 2] != 32 * nnz) return 0;
+    }
+    return 1;
+}
+#define ROWS_ARGS_TEXT "expected (nVars, nPublic, nConstraints, domain, flags, [rowPtr, col, coef] x 3: u64 x (nConstraints + 1), u32 and 32 bytes per entry)"
+/* circuitFromRows(...) -> Promise<ArrayBuffer>: u32 domain, u32 0, lens[3] (u64), the wsnark_rows_report_t, polsA | polsB | polsC */
+static napi_value js_circuit_from_rows(napi_env env, napi_callback_info info) {
+    size_t argc = 6; napi_value argv[6];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CIRCUIT_FROM_ROWS;
+    if (argc < 6 || !rows_args(env, j, argv)) FAIL(env, j, ROWS_ARGS_TEXT);
+    keep(env, j, argv[5]);      /* the array keeps its nine buffers alive */
+    return start_job(env, j, "wsnark_circuit_from_rows");
+}
+/* loadCircuitRows(...) -> Promise<handle>: loadCircuit's handle (wsnark_circuit_load_rows) */
+static napi_value js_circuit_load_rows(napi_env env, napi_callback_info info) {
+    size_t argc = 6; napi_value argv[6];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CIRCUIT_LOAD_ROWS;
+    if (argc < 6 || !rows_args(env, j, argv)) FAIL(env, j, ROWS_ARGS_TEXT);
+    keep(env, j, argv[5]);
+    return start_job(env, j, "wsnark_circuit_load_rows");
 }
 /* circuitInfo(handle) -> {nVars, nPublic, domain, nnz: [A, B, C], bytes} */
 static napi_value js_circuit_info(napi_env env, napi_callback_info info) {
@@ -1397,6 +1476,8 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"checkPowers", NULL, js_check_powers, NULL, NULL, NULL, napi_default, NULL},
         {"checkKeyCircuit", NULL, js_check_key_circuit, NULL, NULL, NULL, napi_default, NULL},
         {"loadCircuit", NULL, js_circuit_load, NULL, NULL, NULL, napi_default, NULL},
+        {"circuitFromRows", NULL, js_circuit_from_rows, NULL, NULL, NULL, napi_default, NULL},
+        {"loadCircuitRows", NULL, js_circuit_load_rows, NULL, NULL, NULL, napi_default, NULL},
         {"circuitInfo", NULL, js_circuit_info, NULL, NULL, NULL, napi_default, NULL},
         {"circuitFree", NULL, js_circuit_free, NULL, NULL, NULL, napi_default, NULL},
         {"circuitCheckWitness", NULL, js_circuit_check_witness, NULL, NULL, NULL, napi_default, NULL},

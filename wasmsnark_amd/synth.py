@@ -238,6 +238,20 @@ def circuit_blobs(circ):
             "polsA": _pol_blob(circ.A), "polsB": _pol_blob(circ.B), "polsC": _pol_blob(circ.C)}
 
 
+def circuit_rows(circ):
+    """The circuit ROW BY ROW (the `rows` of Bn128.circuit_from_rows / load_circuit(rows=...); wsnark_rows_t): its nConstraints = domain
+    - nPublic - 1 real constraints, a row's terms by ascending signal.  The input-binding rows are left out: public_rows=True appends them."""
+    from .formats import rows_from_constraints
+    n_cons = circ.domain - circ.n_public - 1
+    cons = [([], [], []) for _ in range(n_cons)]
+    for k, m in enumerate((circ.A, circ.B, circ.C)):
+        for s, col in enumerate(m):
+            for c, coef in col.items():
+                if c < n_cons:
+                    cons[c][k].append((s, coef))
+    return rows_from_constraints(cons, circ.n_vars, circ.n_public)
+
+
 def build_key(circ, S, mul_base):
     """Returns (proving_key.bin bytes, verification key dict in the reference's JSON shape)."""
     npub = circ.n_public
