@@ -354,7 +354,8 @@ int wsnark_g2_ntt(const void* points, uint64_t n, int inverse, void* out);
  *                             counts all its 2n entries) and for a beta2 that fails the audit's fixed-point tests.  The outputs are
  *                             then unspecified.
  * Not tested here: whether the powers ARE powers of one tau, and the G2 subgroup test of tau_g2 -- both are wsnark_powers_check's
- * (below): run it on a transcript before a key is built on it.  No .ptau / .r1cs readers, no file-to-file variant, one GPU.  Each call takes a lane of the context; nothing
+ * (below): run it on a transcript before a key is built on it.  No .ptau / .r1cs readers (a finished key's .zkey has one: wsnark_zkey_import),
+ * no file-to-file variant, one GPU.  Each call takes a lane of the context; nothing
  * else calls these functions and no other entry point changes. */
 typedef struct {                 /* what a phase-1 transcript holds for a domain of n = `domain` */
     uint32_t domain;             /* power of two */
@@ -583,8 +584,8 @@ int wsnark_circuit_witness_check_batch_dev(wsnark_circuit_res_t* h, const void* 
  *               that is no power of two, below the total rows or outside [2, 2^24], a matrix of 2^32 records or more, n_vars > 2^30, a
  *               capacity below lens[M] WSNARK_ERR_SIZE; before wsnark_init WSNARK_ERR_NOINIT.
  *   threads     each call takes one lane; scratch belongs to the call.
- *   Out of scope: readers of .r1cs / .wtns / snarkjs JSON files (a front end packs its constraints into wsnark_rows_t:
- *   wasmsnark_amd/formats.py rows_from_constraints); merging repeated signals of a row; group (multi-GPU) handles; no other entry
+ *   Out of scope: readers of .r1cs and snarkjs JSON files (a front end packs its constraints into wsnark_rows_t:
+ *   wasmsnark_amd/formats.py rows_from_constraints; a .zkey and a .wtns have their readers below); merging repeated signals of a row; group (multi-GPU) handles; no other entry
  *   point changes. */
 typedef struct {                      /* one matrix, CSR over the constraints as given */
     const uint64_t* row_ptr;          /* n_constraints + 1 entries, row_ptr[0] == 0, non-decreasing */
@@ -605,6 +606,85 @@ int wsnark_circuit_from_rows_size(const wsnark_rows_t* rows, uint32_t flags, uin
 int wsnark_circuit_from_rows(const wsnark_rows_t* rows, uint32_t flags, void* out_polsA, uint64_t capA, void* out_polsB, uint64_t capB,
                              void* out_polsC, uint64_t capC, uint32_t* domain, wsnark_rows_report_t* rep);
 int wsnark_circuit_load_rows(const wsnark_rows_t* rows, uint32_t flags, wsnark_circuit_res_t** out_handle);
+/* ---- snarkjs' .zkey in and out; the H basis change (csrc/zkey.hip) ----
+ * What circom / snarkjs / rapidsnark users hold is a .zkey and a .wtns, not proving_key.bin and witness.bin.  Two sections of a .zkey
+ * are in another FORM than the key's: the coefficients are one flat list of (matrix, constraint, signal, value) records in row order
+ * with A and B interleaved (the key wants one column stream per matrix), and H holds the odd Lagrange points of the doubled domain,
+ * N_i = (L^{2n}_{2i+1}(tau) / delta) G1, where CALC_H's sum wants hExps_k = (tau^k (tau^n - 1) / delta) G1.  With n = domainSize, w_n
+ * the root wsnark_fr_ntt uses, w_2n^2 = w_n:
+ *       hExps_k = (-2 w_2n^k) sum_i w_n^(ik) N_i              N_i = sum_k w_n^(-ik) (-(2n)^-1 w_2n^(-k)) hExps_k
+ * -- a group transform and one scalar per point, the latter BEHIND the stages on the way in and IN FRONT of them on the way out, where
+ * it carries the inverse's 1/n as well.  The layout of the container, the sections, the points (proving_key.bin's own: sections
+ * 5 - 8 and the fixed points are copied byte for byte) and the coefficient values (c R^2 mod r in a .zkey, c R mod r in a key) is
+ * README.md's "zkey" section.
+ *   wsnark_g1_h_basis          points / out: host, n points of 64 B as in wsnark_g1_ntt (out may be points); to_lagrange = 0: N -> hExps,
+ *                              1: hExps -> N.  n a power of two in [2, 2^24], else WSNARK_ERR_SIZE.  Every input gets the audit's two
+ *                              cheap tests; a bad point is WSNARK_ERR_FORMAT, wsnark_last_error names the first index, out untouched.
+ *                              Outputs are canonical affine, infinity as zero bytes.  The points stay on the device from upload to
+ *                              download: load, stages, twist are wsnark_g1_ntt's and wsnark_g1_mul_batch's kernels.
+ *   wsnark_zkey_info           host only, no wsnark_init: the header's numbers, records per matrix, contributions, the length of the
+ *                              proving_key.bin (may be 2^32 or more: then only the sections variant imports it) and of the vk.
+ *   wsnark_zkey_import         the key as proving_key.bin in out_pkey[0 .. *out_len) and the verification key in out_vk (the layout
+ *                              wsnark_groth16_verify reads, plain: alfa1 | beta2 | gamma2 | delta2 | IC[0 .. nPublic]).
+ *   wsnark_zkey_import_sections the same key as twelve separate buffers for keys past 4 GiB, in this order with their capacities:
+ *                              polsA, polsB, then wsnark_pkey_setup's pointsA, pointsB1, pointsB2, pointsC, pointsH, alfa1, beta1,
+ *                              delta1, beta2, delta2 (IC goes into out_vk).  pointsC may be NULL when nVars == nPublic + 1.
+ *     streams                  every signal's records have ascending constraint, equal constraints keep file order, a zero value
+ *                              stays as a record, a value >= r is reduced and counted.  The nPublic + 1 input-binding rows are
+ *                              already records of section 4: nothing is appended.  One kernel reads the 44-byte records, takes the
+ *                              value out of one Montgomery factor and partitions STABLY by matrix (a block scan of the matrix flag
+ *                              plus scanned per-tile bases; no order comes from an atomic); the stable radix sort and the emit are
+ *                              wsnark_circuit_from_rows'.  Where a matrix's records are not non-decreasing in constraint (snarkjs
+ *                              always writes them so), passes over the constraint bits run first: the result is that of the file
+ *                              stably sorted by constraint.  ROWS_TILE as above; no byte depends on it.
+ *     validation               before anything is written, WSNARK_ERR_FORMAT with a text that names it: bad magic, version or
+ *                              protocol (PLONK and FFLONK ids included), n8q or n8r != 32, q or r not BN128's, nPublic + 1 > nVars, a
+ *                              section size that does not match its counts, a truncated file, a required section (1 - 9) missing or
+ *                              any section present twice, matrix > 1, signal >= nVars, constraint >= domainSize (the last two
+ *                              found on the device by a min-reduction), a bad point of H (unreduced or off the curve, with its
+ *                              index).  Unknown section types are skipped; sections may come in any order.  WSNARK_ERR_SIZE: a
+ *                              domainSize that is no power of two in [2, 2^24], a capacity that is too small, a key past 4 GiB in the
+ *                              proving_key.bin variant.  On every error the outputs and the report are untouched.
+ *     NOT audited              sections 3 and 5 - 8 and the fixed points are copied, not tested: that is wsnark_pkey_check's job, to be
+ *                              run on the imported key before it is trusted.
+ *   wsnark_zkey_export*        sections 1 - 10 in numeric order.  Section 4 by ascending constraint; inside a constraint matrix 0's records
+ *                              by ascending signal (equal signals in stream order), then matrix 1's: one stable sort by constraint
+ *                              of the two streams' records, then an emit that multiplies by R and stores the 44-byte records
+ *                              with 32-bit stores in output order.  gamma2 and IC come from vk (the verifier's layout, n_inputs =
+ *                              nPublic, else WSNARK_ERR_ARG; vk == NULL is WSNARK_ERR_ARG).  Section 10 is 64 zero bytes and n = 0: the
+ *                              circuit hash is over data a key does not hold, so `snarkjs zkey verify` rejects the file while
+ *                              provers take it.  wsnark_zkey_export_size: the length, host only.
+ *   rep                        records / unreduced / zero per matrix; sorted: 1 iff every matrix's records were already in constraint
+ *                              order (always 1 on export); the H array's points / infinity / bad / first_bad / first_reason; ms:
+ *                              parse + upload, coefficients, H basis, download, whole call.
+ *   Each call takes one lane; before wsnark_init WSNARK_ERR_NOINIT (not wsnark_zkey_info and _export_size).  No other entry point
+ *   changes.  Out of scope: .r1cs and .ptau readers, a faithful section 10, other protocols, groups (multi-GPU). */
+typedef struct {
+    uint32_t n_vars, n_public, domain, n_coeffs;
+    uint64_t records[2];                 /* section 4's records of matrix 0 (A) and 1 (B) */
+    uint32_t n_contributions, reserved;
+    uint64_t pkey_len;                   /* the proving_key.bin this key makes */
+    uint64_t vk_len;                     /* 448 + 64 (nPublic + 1) */
+} wsnark_zkey_info_t;
+typedef struct {
+    uint64_t records[2], unreduced[2], zero[2];
+    uint32_t sorted, reserved;
+    uint64_t h_points, h_infinity, h_bad;
+    uint64_t h_first_bad;                /* UINT64_MAX if none */
+    uint32_t h_first_reason, reserved2;
+    double   ms[5];                      /* parse + upload, coefficients, H basis, download, whole call */
+} wsnark_zkey_report_t;
+int wsnark_g1_h_basis(const void* points, uint64_t n, int to_lagrange, void* out);
+int wsnark_zkey_info(const void* zkey, size_t len, wsnark_zkey_info_t* out);
+int wsnark_zkey_import(const void* zkey, size_t len, void* out_pkey, size_t cap, size_t* out_len,
+                       void* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep);
+int wsnark_zkey_import_sections(const void* zkey, size_t len, void* const out[12], const uint64_t caps[12],
+                                void* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep);
+int wsnark_zkey_export(const void* pkey, size_t len, const void* vk, size_t vk_len, uint64_t n_inputs,
+                       void* out_zkey, size_t cap, size_t* out_len, wsnark_zkey_report_t* rep);
+int wsnark_zkey_export_sections(const wsnark_key_sections_t* key, const void* vk, size_t vk_len, uint64_t n_inputs,
+                                void* out_zkey, size_t cap, size_t* out_len, wsnark_zkey_report_t* rep);
+int wsnark_zkey_export_size(uint32_t n_vars, uint32_t n_public, uint32_t domain, uint64_t nnzA, uint64_t nnzB, size_t* out_len);
 /* ---- powers of tau: contribute to a transcript, audit one (csrc/pwtau.hip; snarkjs: `powersoftau contribute` / `powersoftau verify`) ----
  * Phase 1 itself: the transcript wsnark_pkey_setup builds a key on.  A contribution by secrets t, a, b (non-zero mod r) turns the
  * transcript of (tau, alpha, beta) into the one of (t tau, a alpha, b beta):

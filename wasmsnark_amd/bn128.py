@@ -9,6 +9,7 @@ Python mirror exists so the parity tests read like the reference's own tests.
 """
 import ctypes as C
 import os
+import struct
 import weakref
 
 from . import _lib
@@ -85,6 +86,40 @@ def _report_dict(r):
     out["ok"] = bool(r.ok)
     out["ms"] = {"points": r.ms[0], "relation_sums": r.ms[1], "pairings": r.ms[2], "total": r.ms[3]}
     return out
+
+
+class _ZkeyInfo(C.Structure):      # wsnark_zkey_info_t
+    _fields_ = [("n_vars", C.c_uint32), ("n_public", C.c_uint32), ("domain", C.c_uint32), ("n_coeffs", C.c_uint32),
+                ("records", C.c_uint64 * 2), ("n_contributions", C.c_uint32), ("reserved", C.c_uint32),
+                ("pkey_len", C.c_uint64), ("vk_len", C.c_uint64)]
+
+
+class _ZkeyReport(C.Structure):    # wsnark_zkey_report_t
+    _fields_ = [("records", C.c_uint64 * 2), ("unreduced", C.c_uint64 * 2), ("zero", C.c_uint64 * 2),
+                ("sorted", C.c_uint32), ("reserved", C.c_uint32),
+                ("h_points", C.c_uint64), ("h_infinity", C.c_uint64), ("h_bad", C.c_uint64), ("h_first_bad", C.c_uint64),
+                ("h_first_reason", C.c_uint32), ("reserved2", C.c_uint32), ("ms", C.c_double * 5)]
+
+
+def _zkey_report_dict(r):
+    bad = int(r.h_bad)
+    return {"records": (int(r.records[0]), int(r.records[1])), "unreduced": (int(r.unreduced[0]), int(r.unreduced[1])),
+            "zero": (int(r.zero[0]), int(r.zero[1])), "sorted": bool(r.sorted),
+            "H": {"points": int(r.h_points), "infinity": int(r.h_infinity), "bad": bad,
+                  "first_bad": int(r.h_first_bad) if bad else None, "first_reason": KEY_REASONS[r.h_first_reason] if bad else None},
+            "ms": {"upload": r.ms[0], "coefficients": r.ms[1], "h_basis": r.ms[2], "download": r.ms[3], "total": r.ms[4]}}
+
+
+def vk_from_bytes(b, n_public):
+    """The inverse of vk_to_bytes: wsnark_groth16_verify's layout -> the reference's verification key object."""
+    d = lambda o: str(int.from_bytes(b[o:o + 32], "little"))
+    g1 = lambda o: [d(o), d(o + 32), "1"]
+    g2 = lambda o: [[d(o), d(o + 32)], [d(o + 64), d(o + 96)], ["1", "0"]]
+    return {"protocol": "groth", "nPublic": n_public, "vk_alfa_1": g1(0), "vk_beta_2": g2(64), "vk_gamma_2": g2(192),
+            "vk_delta_2": g2(320), "IC": [g1(448 + 64 * i) for i in range(n_public + 1)]}
+
+
+_ZKEY_OUTPUTS = ("polsA", "polsB", "pointsA", "pointsB1", "pointsB2", "pointsC", "pointsH", "alfa1", "beta1", "delta1", "beta2", "delta2")
 
 
 class _DeltaReport(C.Structure):   # wsnark_pkey_delta_report_t
@@ -647,6 +682,41 @@ class ResidentPoints:
             self.free()
         except Exception:
             pass
+
+
+def _out_bytes(n):
+    """(a new bytes object of n bytes for the library to FILL, its address).  PyBytes_FromStringAndSize(NULL, n) is the C API's own way
+    to make a bytes object whose contents the caller writes before anybody else sees it: a key of half a gigabyte then costs neither
+    the zero fill of a ctypes array nor the copy out of it.  The object must not be used before the call that fills it has returned."""
+    new = C.pythonapi.PyBytes_FromStringAndSize
+    new.restype, new.argtypes = C.py_object, [C.c_char_p, C.c_ssize_t]
+    b = new(None, max(int(n), 1))
+    return b, C.cast(C.c_char_p(b), C.c_void_p)
+
+
+class _zkey_source:
+    """(pointer, length) of a .zkey given as bytes or as a path: the file is mapped read-only for the duration of the block"""
+
+    def __init__(self, zkey, path):
+        if (zkey is None) == (path is None):
+            raise ValueError("exactly one of zkey, path")
+        self.zkey, self.path, self.map, self.file = zkey, path, None, None
+
+    def __enter__(self):
+        if self.path is None:
+            return _ro(self.zkey)
+        import mmap
+        self.file = open(self.path, "rb")
+        self.map = mmap.mmap(self.file.fileno(), 0, access=mmap.ACCESS_COPY)      # private and writable for ctypes; never written
+        self.view = (C.c_uint8 * len(self.map)).from_buffer(self.map)
+        return C.c_void_p(C.addressof(self.view)), len(self.map)
+
+    def __exit__(self, *exc):
+        if self.map is not None:
+            del self.view
+            self.map.close()
+            self.file.close()
+        return False
 
 
 def _key_sections(sections):
@@ -1309,6 +1379,104 @@ class Bn128:
         del ptr
         return {"n_vars": rows["n_vars"], "n_public": rows["n_public"], "domain": dom.value,
                 "polsA": bytes(out[0][:lens[0]]), "polsB": bytes(out[1][:lens[1]]), "polsC": bytes(out[2][:lens[2]])}
+
+    # --- snarkjs' .zkey / .wtns in and out (csrc/zkey.hip; no reference counterpart) ---
+    def h_basis(self, points, to_lagrange=False):
+        """A .zkey's H section (the odd Lagrange points of the doubled domain) to the key's hExps (monomial form), or with to_lagrange
+        the way back (wsnark_g1_h_basis).  points: n affine Montgomery G1 points of 64 bytes, n a power of two in [2, 2^24]."""
+        p, nb = _ro(points)
+        if nb % 64:
+            raise ValueError("points: not a whole number of 64-byte points")
+        out = (C.c_uint8 * max(nb, 1))()
+        self.lib.check(self.lib.c.wsnark_g1_h_basis(p, nb // 64, 1 if to_lagrange else 0, out))
+        return bytes(out)[:nb]
+
+    def zkey_info(self, zkey=None, path=None):
+        """A .zkey's numbers without any device work (wsnark_zkey_info): {n_vars, n_public, domain, n_coeffs, records: (A, B),
+        n_contributions, pkey_len, vk_len}."""
+        with _zkey_source(zkey, path) as (ptr, n):
+            info = _ZkeyInfo()
+            self.lib.check(self.lib.c.wsnark_zkey_info(ptr, n, C.byref(info)))
+        return {"n_vars": info.n_vars, "n_public": info.n_public, "domain": info.domain, "n_coeffs": info.n_coeffs,
+                "records": (int(info.records[0]), int(info.records[1])), "n_contributions": info.n_contributions,
+                "pkey_len": int(info.pkey_len), "vk_len": int(info.vk_len)}
+
+    def import_zkey(self, zkey=None, path=None, sections=False, wtns=None, report=None):
+        """A snarkjs .zkey (bytes, or path=: the file is mapped and the library reads the mapping) as a key of this library
+        (wsnark_zkey_import / _import_sections): returns (proving_key.bin bytes, or with sections=True the sections dict load_key takes
+        -- the form for keys past 4 GiB --, the verification key object).  The coefficient records become the two column streams, the H
+        section changes basis on the device; sections 3 and 5 - 8 are copied and NOT audited: that is check_key.  wtns: .wtns bytes of a
+        witness of the circuit -- a TRIAL PROOF: the witness is proved with the new key and the proof verified against the returned
+        verification key; ValueError if it does not verify (a file written under another convention than this reader's fails here,
+        not in production).  report: a dict that receives {records, unreduced, zero: (A, B), sorted, H: {...}, ms}."""
+        with _zkey_source(zkey, path) as (ptr, n):
+            info = _ZkeyInfo()
+            self.lib.check(self.lib.c.wsnark_zkey_info(ptr, n, C.byref(info)))
+            vk = (C.c_uint8 * int(info.vk_len))()
+            rep = _ZkeyReport()
+            nv, npub, dom = info.n_vars, info.n_public, info.domain
+            if sections:
+                sizes = (4 * nv + 36 * int(info.records[0]), 4 * nv + 36 * int(info.records[1]), 64 * nv, 64 * nv, 128 * nv,
+                         64 * (nv - npub - 1), 64 * dom, 64, 64, 64, 128, 128)
+                bufs = [(C.c_uint8 * max(sz, 1))() for sz in sizes]
+                ptrs = (C.c_void_p * 12)(*[C.cast(b, C.c_void_p) for b in bufs])
+                caps = (C.c_uint64 * 12)(*sizes)
+                self.lib.check(self.lib.c.wsnark_zkey_import_sections(ptr, n, ptrs, caps, vk, len(vk), C.byref(rep)))
+                key = {"n_vars": nv, "n_public": npub, "domain": dom}
+                for name, sz, b in zip(_ZKEY_OUTPUTS, sizes, bufs):
+                    key[name] = bytes(b)[:sz]
+            else:
+                key, out = _out_bytes(info.pkey_len)
+                ln = C.c_size_t()
+                self.lib.check(self.lib.c.wsnark_zkey_import(ptr, n, out, len(key), C.byref(ln), vk, len(vk), C.byref(rep)))
+                assert ln.value == len(key)
+        if report is not None:
+            report.update(_zkey_report_dict(rep))
+        vk_obj = vk_from_bytes(bytes(vk), npub)
+        if wtns is not None:
+            from .formats import wtns_to_witness_bin
+            wit = wtns_to_witness_bin(wtns)
+            handle = self.load_key(sections=key) if sections else self.load_key(key)
+            try:
+                proof = self.groth16GenProof(wit, handle)
+            finally:
+                handle.free()
+            pub = [int.from_bytes(wit[32 * i:32 * i + 32], "little") for i in range(1, npub + 1)]
+            if not self.groth16Verify(vk_obj, pub, proof):
+                raise ValueError("import_zkey: the trial proof of the given witness does not verify against the file's verification key -- "
+                                 "the file's coefficients or H section follow another convention than this reader's, or the witness is not "
+                                 "one of this circuit")
+        return key, vk_obj
+
+    def export_zkey(self, pkey=None, sections=None, vk=None, report=None):
+        """A key of this library (proving_key.bin bytes, or sections=) and its verification key object as a snarkjs .zkey
+        (wsnark_zkey_export / _export_sections): gamma2 and IC come from vk.  Section 10 holds no contributions and a zero circuit
+        hash: provers take the file, `snarkjs zkey verify` does not."""
+        if vk is None:
+            raise ValueError("export_zkey: vk is required (gamma2 and IC are not part of a proving key)")
+        if (pkey is None) == (sections is None):
+            raise ValueError("export_zkey: exactly one of pkey, sections")
+        if sections is not None:
+            ks, keep = _key_sections(sections)
+            nv, npub, dom = sections["n_vars"], sections["n_public"], sections["domain"]
+            la, lb = len(sections["polsA"]), len(sections["polsB"])
+        else:
+            p, n = _ro(pkey)
+            h = struct.unpack_from("<10I", bytes(pkey[:40]))
+            nv, npub, dom, la, lb = h[0], h[1], h[2], h[4] - h[3], h[5] - h[4]
+        vkb = vk_to_bytes(vk, npub)
+        ln = C.c_size_t()
+        self.lib.check(self.lib.c.wsnark_zkey_export_size(nv, npub, dom, max(la - 4 * nv, 0) // 36, max(lb - 4 * nv, 0) // 36, C.byref(ln)))
+        z, out = _out_bytes(ln.value)
+        rep = _ZkeyReport()
+        if sections is not None:
+            self.lib.check(self.lib.c.wsnark_zkey_export_sections(C.byref(ks), vkb, len(vkb), npub, out, len(z), C.byref(ln), C.byref(rep)))
+        else:
+            self.lib.check(self.lib.c.wsnark_zkey_export(p, n, vkb, len(vkb), npub, out, len(z), C.byref(ln), C.byref(rep)))
+        assert ln.value == len(z)
+        if report is not None:
+            report.update(_zkey_report_dict(rep))
+        return z
 
     def check_witness(self, circuit, witness, max_rows=16):
         """Load, check and free in one call (wsnark_witness_check): ResidentCircuit.check_witness's report and lists, with the

@@ -404,6 +404,43 @@ int wsnark_pkey_setup_pkey(const wsnark_powers_t* powers, const wsnark_circuit_t
     return pkey_setup_bytes(powers, circuit, (uint8_t*)out_pkey, out_cap, out_len, (uint8_t*)out_ic, rep);
 }
 int wsnark_pkey_setup_size(const wsnark_circuit_t* circuit, size_t* out_len) { return pkey_setup_size(circuit, out_len); }
+// ---- snarkjs' .zkey in and out, the H basis change (zkey.hip) ----
+static_assert(sizeof(wsnark_zkey_info_t) == 56 && sizeof(wsnark_zkey_report_t) == 136, "the bindings read these by offset");
+int wsnark_g1_h_basis(const void* points, uint64_t n, int to_lagrange, void* out) {
+    REQUIRE_CTX();
+    return g1_h_basis(points, n, to_lagrange, out);
+}
+int wsnark_zkey_info(const void* zkey, size_t len, wsnark_zkey_info_t* out) { return zkey_info((const uint8_t*)zkey, len, out); }
+int wsnark_zkey_import(const void* zkey, size_t len, void* out_pkey, size_t cap, size_t* out_len, void* out_vk, size_t vk_cap,
+                       wsnark_zkey_report_t* rep) {
+    REQUIRE_CTX();
+    if (!out_pkey) return WSNARK_ERR_ARG;
+    return zkey_import((const uint8_t*)zkey, len, nullptr, nullptr, (uint8_t*)out_pkey, cap, out_len, (uint8_t*)out_vk, vk_cap, rep);
+}
+int wsnark_zkey_import_sections(const void* zkey, size_t len, void* const out[12], const uint64_t caps[12], void* out_vk, size_t vk_cap,
+                                wsnark_zkey_report_t* rep) {
+    REQUIRE_CTX();
+    if (!out || !caps) return WSNARK_ERR_ARG;
+    return zkey_import((const uint8_t*)zkey, len, out, caps, nullptr, 0, nullptr, (uint8_t*)out_vk, vk_cap, rep);
+}
+int wsnark_zkey_export(const void* pkey, size_t len, const void* vk, size_t vk_len, uint64_t n_inputs, void* out_zkey, size_t cap,
+                       size_t* out_len, wsnark_zkey_report_t* rep) {
+    REQUIRE_CTX();
+    if (!pkey || !vk) return WSNARK_ERR_ARG;
+    KeyInput in;
+    int rc = in.open(pkey, len);
+    return rc ? rc : zkey_export(in.S, (const uint8_t*)vk, vk_len, n_inputs, (uint8_t*)out_zkey, cap, out_len, rep);
+}
+int wsnark_zkey_export_sections(const wsnark_key_sections_t* key, const void* vk, size_t vk_len, uint64_t n_inputs, void* out_zkey,
+                                size_t cap, size_t* out_len, wsnark_zkey_report_t* rep) {
+    REQUIRE_CTX();
+    KeyInput in;
+    if (!vk || in.open(key)) return WSNARK_ERR_ARG;
+    return zkey_export(in.S, (const uint8_t*)vk, vk_len, n_inputs, (uint8_t*)out_zkey, cap, out_len, rep);
+}
+int wsnark_zkey_export_size(uint32_t n_vars, uint32_t n_public, uint32_t domain, uint64_t nnzA, uint64_t nnzB, size_t* out_len) {
+    return zkey_export_size(n_vars, n_public, domain, nnzA, nnzB, out_len);
+}
 // ---- powers of tau: a scalar per point, the contribution, the audit (pwtau.hip) ----
 int wsnark_g1_mul_batch(const void* points, const void* scalars, uint64_t n, void* out_affine) {
     REQUIRE_CTX();

@@ -42,8 +42,7 @@ namespace wsnark {
 static constexpr uint32_t kBits = 6, kDigits = 1u << kBits;      // digits per radix pass
 static constexpr uint32_t kMaxPerLane = 16;                      // a tile is at most 4096 entries: its ranks fit 16 bits
 
-// one matrix's running result; first_bad holds ~index of the smallest bad entry (0 = none) so that atomicMax finds the minimum (PkAcc)
-struct RowsAcc { unsigned long long first_bad, unreduced, zero, empty, max_column; };
+// (RowsAcc, one matrix's running result, is keybytes.h's: zkey.hip enters the sort and the emit below with pairs of its own)
 
 // entry e of a matrix: its signal and its row.  e < nnz: the input's; e >= nnz: public row e - nnz, {signal e - nnz: 1}
 __device__ __forceinline__ uint32_t rows_signal(const uint32_t* __restrict__ col, uint32_t nnz, uint32_t e) { return e < nnz ? col[e] : e - nnz; }
@@ -272,28 +271,68 @@ struct TimerScope {
     TimerScope& operator=(const TimerScope&) = delete;
 };
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-// pieces of ONE device allocation (calch.hip on why: every hipMalloc / hipFree is a call into the driver)
-struct Slab {
-    DevBuf buf;
-    std::vector<std::pair<void**, size_t>> want;
-    void add(void** p, size_t bytes) { want.emplace_back(p, up256(bytes ? bytes : 1)); }
-    hipError_t alloc() {
-        size_t total = 0;
-        for (auto& w : want) total += w.second;
-        const hipError_t e = buf.alloc(total);
-        if (e != hipSuccess) return e;
-        size_t off = 0;
-        for (auto& w : want) { *w.first = (uint8_t*)buf.p + off; off += w.second; }
-        return hipSuccess;
-    }
-};
-
+// (Slab, the pieces of ONE device allocation, is keybytes.h's)
 int bad_entry_error(int m, unsigned long long first_bad) {
     set_last_error(std::string("circuit rows: a signal index >= nVars in ") + kMatrixName[m] + ", first at entry " + std::to_string(~first_bad));
     return WS_ERR_FORMAT;
 }
 }  // namespace
+
+int rows_tile(uint32_t* tile) {
+    const long tile_asked = tuning_get("ROWS_TILE", 2048);
+    if (tile_asked < 256 || tile_asked > 256 * (long)kMaxPerLane || tile_asked % 256) {
+        set_last_error("circuit rows: ROWS_TILE must be a multiple of 256 in [256, 4096]");
+        return WS_ERR_ARG;
+    }
+    *tile = (uint32_t)tile_asked;
+    return WS_OK;
+}
+
+// the stable sort of the n pairs (key, val) of B.key / B.val[*cur] by bits [first_bit, first_bit + bits) of the key: ceil(bits / 6)
+// passes, each one hist / scan / scatter into the other pair of arrays; *cur names the pair that holds the result
+int rows_sort_dev(Context* X, const RowsSort& B, uint32_t n, uint32_t first_bit, uint32_t bits, int* cur, hipStream_t s) {
+    KernelTimer& T = X->timer;
+    const uint32_t passes = (bits + kBits - 1) / kBits, per_lane = B.tile / 256, n_tiles = ceil_div_u64(n, B.tile);
+    int c = *cur, rc;
+    for (uint32_t pass = 0; pass < passes && n; pass++, c ^= 1) {
+        const uint32_t shift = first_bit + pass * kBits;
+        {
+            TimerScope t(T, "rows_hist", s);
+            hipLaunchKernelGGL(rows_hist_kernel, dim3(n_tiles), dim3(256), 0, s, B.key[c], n, B.tile, shift, B.hist, n_tiles);
+            WS_HIP_CHECK(hipGetLastError());
+        }
+        {
+            TimerScope t(T, "rows_scan", s);
+            if ((rc = scan_exclusive_dev(B.hist, kDigits * n_tiles, B.tiles, B.base, B.cursor, s))) return rc;
+        }
+        {
+            TimerScope t(T, "rows_scatter", s);
+            hipLaunchKernelGGL(rows_scatter_kernel, dim3(n_tiles), dim3(256), 0, s, B.key[c], B.val[c], n, per_lane, shift, B.base, n_tiles,
+                               B.key[c ^ 1], B.val[c ^ 1]);
+            WS_HIP_CHECK(hipGetLastError());
+        }
+    }
+    *cur = c;
+    return WS_OK;
+}
+
+// one record stream from the n pairs sorted by signal: the headers, then the records (entry e: row d_row[e], coefficient d_coef[e],
+// any 256-bit value; e >= nnz: a public row's 1); the counts into d_acc
+int rows_emit_dev(Context* X, const uint32_t* d_key, const uint32_t* d_val, uint32_t n, uint32_t nnz, uint32_t n_vars, const uint32_t* d_row,
+                  const Fe* d_coef, uint32_t* d_words, RowsAcc* d_acc, hipStream_t s) {
+    KernelTimer& T = X->timer;
+    {
+        TimerScope t(T, "rows_header", s);
+        hipLaunchKernelGGL(rows_header_kernel, dim3(ceil_div_u64(n_vars, 256)), dim3(256), 0, s, d_key, n, n_vars, d_words, d_acc);
+        WS_HIP_CHECK(hipGetLastError());
+    }
+    {
+        TimerScope t(T, "rows_emit", s);
+        if (n) hipLaunchKernelGGL(rows_emit_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_key, d_val, n, nnz, d_row, d_coef, d_words, d_acc);
+        WS_HIP_CHECK(hipGetLastError());
+    }
+    return WS_OK;
+}
 
 int circuit_from_rows_size(const wsnark_rows_t* R, uint32_t flags, uint32_t* domain, uint64_t lens[3]) {
     if (!domain || !lens) return WS_ERR_ARG;
@@ -315,18 +354,14 @@ int circuit_from_rows(const wsnark_rows_t* R, uint32_t flags, void* const out[3]
         if (cap[m] < P.lens[m]) { set_last_error(std::string("circuit rows: the capacity of pols") + kMatrixName[m] + " is below its length"); return WS_ERR_SIZE; }
 
     const uint32_t nv = P.n_vars;
-    const long tile_asked = tuning_get("ROWS_TILE", 2048);
-    if (tile_asked < 256 || tile_asked > 256 * (long)kMaxPerLane || tile_asked % 256) {
-        set_last_error("circuit rows: ROWS_TILE must be a multiple of 256 in [256, 4096]");
-        return WS_ERR_ARG;
-    }
-    const uint32_t per_lane = (uint32_t)tile_asked / 256, tile = 256 * per_lane;
+    uint32_t tile;
+    if (int rc = rows_tile(&tile)) return rc;
     uint32_t bits = 0;
     while (bits < 32 && ((uint64_t)1 << bits) < nv) bits++;      // bits of n_vars - 1
-    const uint32_t passes = (bits + kBits - 1) / kBits;
     const uint64_t most = std::max(P.entries[0], std::max(P.entries[1], P.entries[2]));
     const uint32_t most_tiles = ceil_div_u64(std::max<uint64_t>(most, 1), tile);
     const uint32_t n_hist = kDigits * most_tiles;
+    static_assert(kDigits == 64, "rows_sort_counters (keybytes.h) counts 64 digits per tile");
 
     LaneLock L = acquire_lane(X);
     hipStream_t s = L->stream;
@@ -350,6 +385,7 @@ int circuit_from_rows(const wsnark_rows_t* R, uint32_t flags, void* const out[3]
     slab.add((void**)&d_tiles, (size_t)ceil_div_u64(n_hist, 1024) * 4);
     slab.add((void**)&d_acc, 3 * sizeof(RowsAcc));
     WS_HIP_CHECK(slab.alloc());
+    const RowsSort B{{d_key[0], d_key[1]}, {d_val[0], d_val[1]}, d_hist, d_base, d_cursor, d_tiles, tile};
 
     // 1. up, through the staging ring
     int rc;
@@ -366,7 +402,7 @@ int circuit_from_rows(const wsnark_rows_t* R, uint32_t flags, void* const out[3]
     const auto t_kernels = Clock::now();
     RowsAcc acc[3];
     for (int m = 0; m < 3; m++) {
-        const uint32_t n = (uint32_t)P.entries[m], nnz = (uint32_t)P.nnz[m], n_tiles = ceil_div_u64(n, tile);
+        const uint32_t n = (uint32_t)P.entries[m], nnz = (uint32_t)P.nnz[m];
         {
             TimerScope t(T, "rows_prepare", s);
             if (n) hipLaunchKernelGGL(rows_prepare_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_rp[m], d_col[m], P.n_cons, nnz, n, nv,
@@ -377,35 +413,8 @@ int circuit_from_rows(const wsnark_rows_t* R, uint32_t flags, void* const out[3]
         WS_HIP_CHECK(hipStreamSynchronize(s));
         if (acc[m].first_bad) return bad_entry_error(m, acc[m].first_bad);
         int cur = 0;
-        for (uint32_t pass = 0; pass < passes && n; pass++, cur ^= 1) {
-            const uint32_t shift = pass * kBits;
-            {
-                TimerScope t(T, "rows_hist", s);
-                hipLaunchKernelGGL(rows_hist_kernel, dim3(n_tiles), dim3(256), 0, s, d_key[cur], n, tile, shift, d_hist, n_tiles);
-                WS_HIP_CHECK(hipGetLastError());
-            }
-            {
-                TimerScope t(T, "rows_scan", s);
-                if ((rc = scan_exclusive_dev(d_hist, kDigits * n_tiles, d_tiles, d_base, d_cursor, s))) return rc;
-            }
-            {
-                TimerScope t(T, "rows_scatter", s);
-                hipLaunchKernelGGL(rows_scatter_kernel, dim3(n_tiles), dim3(256), 0, s, d_key[cur], d_val[cur], n, per_lane, shift, d_base, n_tiles,
-                                   d_key[cur ^ 1], d_val[cur ^ 1]);
-                WS_HIP_CHECK(hipGetLastError());
-            }
-        }
-        {
-            TimerScope t(T, "rows_header", s);
-            hipLaunchKernelGGL(rows_header_kernel, dim3(ceil_div_u64(nv, 256)), dim3(256), 0, s, d_key[cur], n, nv, d_out[m], d_acc + m);
-            WS_HIP_CHECK(hipGetLastError());
-        }
-        {
-            TimerScope t(T, "rows_emit", s);
-            if (n) hipLaunchKernelGGL(rows_emit_kernel, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_key[cur], d_val[cur], n, nnz, d_row, d_coef[m],
-                                      d_out[m], d_acc + m);
-            WS_HIP_CHECK(hipGetLastError());
-        }
+        if ((rc = rows_sort_dev(X, B, n, 0, bits, &cur, s))) return rc;
+        if ((rc = rows_emit_dev(X, d_key[cur], d_val[cur], n, nnz, nv, d_row, d_coef[m], d_out[m], d_acc + m, s))) return rc;
     }
     WS_HIP_CHECK(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, s));
     WS_HIP_CHECK(hipStreamSynchronize(s));

@@ -184,6 +184,23 @@ inline int stage_chunk(void* d_dst, const uint8_t* src, size_t bytes, hipStream_
     return rc;
 }
 
+// pieces of ONE device allocation (calch.hip on why: every hipMalloc / hipFree is a call into the driver, and a free waits for the device)
+struct Slab {
+    DevBuf buf;
+    std::vector<std::pair<void**, size_t>> want;
+    static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+    template <class T> void add(T** p, size_t bytes) { want.emplace_back((void**)p, up256(bytes ? bytes : 1)); }
+    hipError_t alloc() {
+        size_t total = 0;
+        for (auto& w : want) total += w.second;
+        const hipError_t e = buf.alloc(total);
+        if (e != hipSuccess) return e;
+        size_t off = 0;
+        for (auto& w : want) { *w.first = (uint8_t*)buf.p + off; off += w.second; }
+        return hipSuccess;
+    }
+};
+
 // d_out[i] = rho_(base + i), i < n: 128 non-zero bits of the ChaCha20 block under key = seed32, counter = the global index
 int pkcheck_rho_dev(Fe* d_out, uint64_t n, uint64_t base, const uint8_t* seed32, hipStream_t s);
 
@@ -273,6 +290,17 @@ int circuit_witness_check_batch(CircuitRes* H, const void* witnesses, size_t wit
 int circuit_from_rows_size(const wsnark_rows_t* R, uint32_t flags, uint32_t* domain, uint64_t lens[3]);
 int circuit_from_rows(const wsnark_rows_t* R, uint32_t flags, void* const out[3], const uint64_t cap[3], uint32_t* domain, wsnark_rows_report_t* rep);
 int circuit_load_rows(const wsnark_rows_t* R, uint32_t flags, CircuitRes** out);
+// ... and its sort and its emit on device-resident (key, entry) pairs (zkey.hip: a .zkey's coefficient records in, a key's streams out
+// by constraint).  One matrix's running result; first_bad holds ~index of the smallest bad entry (0 = none) so that atomicMax finds the
+// minimum (PkAcc)
+struct RowsAcc { unsigned long long first_bad, unreduced, zero, empty, max_column; };
+// the sort's arrays, the caller's: two pairs of n words each, three arrays of rows_sort_counters words, ceil(that / 1024) words; tile = rows_tile's
+struct RowsSort { uint32_t* key[2]; uint32_t* val[2]; uint32_t *hist, *base, *cursor, *tiles; uint32_t tile; };
+inline uint32_t rows_sort_counters(uint64_t most, uint32_t tile) { return 64 * (uint32_t)((std::max<uint64_t>(most, 1) + tile - 1) / tile); }
+int rows_tile(uint32_t* tile);      // ROWS_TILE, a multiple of 256 in [256, 4096], else WS_ERR_ARG
+int rows_sort_dev(Context* X, const RowsSort& B, uint32_t n, uint32_t first_bit, uint32_t bits, int* cur, hipStream_t s);
+int rows_emit_dev(Context* X, const uint32_t* d_key, const uint32_t* d_val, uint32_t n, uint32_t nnz, uint32_t n_vars, const uint32_t* d_row,
+                  const Fe* d_coef, uint32_t* d_words, RowsAcc* d_acc, hipStream_t s);
 // the audit's per-point kernels on device-resident points in reference format (pkeycheck.hip): counts into d_acc with the global index
 // base + i; the G2 one with the order-r subgroup test (PKCHECK_SUBGROUP picks its form), d_K: the pairing constants on the device
 int pkcheck_g1_dev(Context* X, const void* d_pts, uint64_t n, uint64_t base, PkAcc* d_acc, hipStream_t s);
@@ -286,5 +314,23 @@ int g2_mul_batch(const void* points, const void* scalars, uint64_t n, void* out)
 int powers_contribute(const wsnark_powers_t* P, const uint8_t* tau32, const uint8_t* alpha32, const uint8_t* beta32, uint8_t* const out[5],
                       wsnark_powers_report_t* rep);
 int powers_check(const wsnark_powers_t* P, uint32_t flags, const uint8_t* seed32, wsnark_powers_report_t* rep);
+// the pieces of the two above on device-resident G1 points in reference format, on queue s (zkey.hip: the H basis change is the
+// group transform with a scalar per point in front of it or behind it).  group_root_of_unity: w_(2^bits), Montgomery;
+// g1_ntt_load_dev: the input tests (counts into d_acc), the internal form and the bit reversal, d_in -> d_work; g1_ntt_stages_dev: the
+// twiddle table into d_tw (n/2 entries) and the log2 n stages over d_work, reference format out, WITHOUT the inverse's 1/n;
+// fr_powers_dev: d_out[i] = c t^(first + i), plain; g1_mul_dev: d_out[i] = d_scalars[i] d_pts[i] (d_out != d_pts), synchronises s
+Fe group_root_of_unity(int bits);
+int g1_ntt_load_dev(Context* X, const void* d_in, void* d_work, uint64_t n, int bits, PkAcc* d_acc, hipStream_t s);
+int g1_ntt_stages_dev(Context* X, void* d_work, int bits, int inverse, ScaleDigits* d_tw, hipStream_t s);
+int fr_powers_dev(Context* X, const Fe& c_mont, const Fe& t_mont, uint64_t first, uint64_t count, Fe* d_out, hipStream_t s);
+int g1_mul_dev(Context* X, const void* d_pts, const Fe* d_scalars, uint64_t n, void* d_out, PkAcc* d_acc, hipStream_t s);
+// snarkjs' .zkey (zkey.hip); include/wsnark.h has the contracts
+int g1_h_basis(const void* points, uint64_t n, int to_lagrange, void* out);
+int zkey_info(const uint8_t* zkey, size_t len, wsnark_zkey_info_t* out);
+int zkey_import(const uint8_t* zkey, size_t len, void* const out[12], const uint64_t caps[12], uint8_t* out_pkey, size_t pkey_cap, size_t* out_len,
+                uint8_t* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep);
+int zkey_export(const KeySections& S, const uint8_t* vk, size_t vk_len, uint64_t n_inputs, uint8_t* out, size_t cap, size_t* out_len,
+                wsnark_zkey_report_t* rep);
+int zkey_export_size(uint32_t n_vars, uint32_t n_public, uint32_t domain, uint64_t nnzA, uint64_t nnzB, size_t* out_len);
 
 }  // namespace wsnark

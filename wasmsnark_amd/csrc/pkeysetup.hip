@@ -762,6 +762,16 @@ int pkey_setup_bytes(const wsnark_powers_t* P, const wsnark_circuit_t* K, uint8_
     return rc;
 }
 
+// ---- the transform's steps on device-resident G1 points (zkey.hip: the H basis change puts its twist before or behind the stages) ----
+Fe group_root_of_unity(int bits) { return root_of_unity(bits); }
+int g1_ntt_load_dev(Context* X, const void* d_in, void* d_work, uint64_t n, int bits, PkAcc* d_acc, hipStream_t s) {
+    return ntt_load<G1R29>(X, (const G1R29::AffP*)d_in, (G1R29::AffP*)d_work, n, bits, d_acc, s);
+}
+int g1_ntt_stages_dev(Context* X, void* d_work, int bits, int inverse, ScaleDigits* d_tw, hipStream_t s) {
+    if (int rc = build_twiddles(X, bits, inverse, d_tw, s)) return rc;
+    return run_stages<G1R29>(X, (G1R29::AffP*)d_work, bits, d_tw, s);
+}
+
 int g1_group_ntt(const void* points, uint64_t n, int inverse, void* out) { return group_ntt<G1R29>(points, n, inverse, out); }
 int g2_group_ntt(const void* points, uint64_t n, int inverse, void* out) { return group_ntt<G2R29>(points, n, inverse, out); }
 

@@ -314,6 +314,47 @@ int draw_secret(const uint8_t* caller32, const char* name, Fe* out) {
 }
 }  // namespace
 
+// ---- the same two kernels on device-resident arrays (zkey.hip: the twist of the H basis change) ----
+int fr_powers_dev(Context* X, const Fe& c_mont, const Fe& t_mont, uint64_t first, uint64_t count, Fe* d_out, hipStream_t s) {
+    if (!count) return WS_OK;
+    PowerBase W;
+    W.c = c_mont;
+    W.p[0] = t_mont;
+    for (int j = 1; j < 25; j++) W.p[j] = Fr::sqr(W.p[j - 1]);
+    X->timer.begin("fr_powers", s);
+    hipLaunchKernelGGL(fr_powers_kernel, dim3(ceil_div_u64(count, 256)), dim3(256), 0, s, W, first, count, d_out);
+    WS_HIP_CHECK(hipGetLastError());
+    X->timer.end(s);
+    return WS_OK;
+}
+int g1_mul_dev(Context* X, const void* d_pts, const Fe* d_scalars, uint64_t n, void* d_out, PkAcc* d_acc, hipStream_t s) {
+    typedef G1R29 C;
+    if (!n) return WS_OK;
+    C::El cb;
+    int rc = curve_b(&cb);
+    if (rc) return rc;
+    // PWTAU_CHUNK points per launch: the table of the windowed chain is sized by the chunk, not by the array
+    const uint64_t chunk = key_chunk("PWTAU_CHUNK"), cap = key_chunk_cap(chunk, n);
+    const int mode = mul_mode();
+    DevBuf d_tab;
+    if (mode == 1) WS_HIP_CHECK(d_tab.alloc((size_t)cap * PW_TAB * sizeof(C::PtP)));
+    const C::AffP* in = (const C::AffP*)d_pts;
+    C::AffP* out = (C::AffP*)d_out;
+    for (uint64_t lo = 0; lo < n; lo += chunk) {
+        const uint64_t m = std::min<uint64_t>(chunk, n - lo);
+        const dim3 grid(ceil_div_u64(m, 256)), block(256);
+        X->timer.begin(mode == 0 ? "mul_points_g1_naf" : "mul_points_g1_win", s);
+        if (mode == 0)
+            hipLaunchKernelGGL((mul_points_kernel<C, 0>), grid, block, 0, s, in + lo, d_scalars + lo, m, lo, cb, out + lo, (C::PtP*)nullptr, (uint64_t)0, d_acc);
+        else
+            hipLaunchKernelGGL((mul_points_kernel<C, 1>), grid, block, 0, s, in + lo, d_scalars + lo, m, lo, cb, out + lo, d_tab.as<C::PtP>(), cap, d_acc);
+        WS_HIP_CHECK(hipGetLastError());
+        X->timer.end(s);
+    }
+    WS_HIP_CHECK(hipStreamSynchronize(s));      // (the table goes with this call)
+    return WS_OK;
+}
+
 int g1_mul_batch(const void* points, const void* scalars, uint64_t n, void* out) { return mul_batch<G1R29>(points, scalars, n, out); }
 int g2_mul_batch(const void* points, const void* scalars, uint64_t n, void* out) { return mul_batch<G2R29>(points, scalars, n, out); }
 

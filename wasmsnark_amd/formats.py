@@ -24,6 +24,10 @@ Command line (the reference's two tools under their own names):
     python -m wasmsnark_amd.formats buildwitness -i witness.json     -o witness.bin
     python -m wasmsnark_amd.formats dumppkey     -i proving_key.bin  -o proving_key.json
     python -m wasmsnark_amd.formats pkey64       -i proving_key.bin  -o proving_key.wsnark64     (the u64-offset container, below)
+    python -m wasmsnark_amd.formats wtns2bin     -i witness.wtns     -o witness.bin
+    python -m wasmsnark_amd.formats zkey2pkey    -i circuit.zkey     -o proving_key.bin  [--vk verification_key.json] [--wtns witness.wtns]
+    python -m wasmsnark_amd.formats pkey2zkey    -i proving_key.bin  -o circuit.zkey      --vk verification_key.json
+(the last two run on the GPU: Bn128.import_zkey / export_zkey; --wtns makes the import prove and verify that witness once)
 """
 from __future__ import annotations
 
@@ -61,7 +65,8 @@ def rows_from_constraints(constraints, n_vars, n_public):
     """Constraints as a front end holds them -- a list of (A, B, C), each a dict {signal: coefficient} or a list of (signal,
     coefficient) pairs -- packed into the `rows` dict of Bn128.circuit_from_rows / load_circuit(rows=...) (wsnark_rows_t): per matrix
     row_ptr (u64), col (u32) and coef (32 bytes plain little-endian) as bytes.  Format-agnostic on purpose: there is no reader of
-    .r1cs, .wtns or snarkjs' JSON export here; whatever parses those hands its constraints to this.  Terms keep their order;
+    .r1cs or snarkjs' JSON export here; whatever parses those hands its constraints to this.  (A finished key's .zkey and a .wtns
+    have readers: Bn128.import_zkey, wtns_to_witness_bin.)  Terms keep their order;
     coefficients are taken mod 2^256 when non-negative (the device reduces them mod r) and mod r when negative."""
     out = {"n_vars": int(n_vars), "n_public": int(n_public), "n_constraints": len(constraints)}
     for k, name in enumerate("ABC"):
@@ -328,17 +333,83 @@ def proof_from_bytes(p: bytes) -> dict:
     return {"pi_a": v[0:3], "pi_b": [v[3:5], v[5:7], v[7:9]], "pi_c": v[9:12]}
 
 
+def wtns_to_witness_bin(b) -> bytes:
+    """snarkjs' .wtns -> witness.bin: "wtns", u32 version 2, u32 nSections; section 1 = u32 n8 (32), the prime r, u32 nWitness;
+    section 2 = nWitness x 32 bytes plain little-endian -- which is witness.bin as it is.  Sections are found by type."""
+    b = bytes(b)
+    if len(b) < 12 or b[:4] != b"wtns":
+        raise FormatError("not a .wtns file (bad magic)")
+    version, n_sec = struct.unpack_from("<II", b, 4)
+    if version != 2:
+        raise FormatError(".wtns version %d is not 2" % version)
+    at, sec = 12, {}
+    for _ in range(n_sec):
+        if len(b) - at < 12:
+            raise FormatError(".wtns: truncated section header")
+        typ, size = struct.unpack_from("<IQ", b, at)
+        at += 12
+        if size > len(b) - at:
+            raise FormatError(".wtns: truncated section %d" % typ)
+        if typ in sec:
+            raise FormatError(".wtns: section %d is present twice" % typ)
+        sec[typ] = b[at:at + size]
+        at += size
+    if 1 not in sec or 2 not in sec:
+        raise FormatError(".wtns: section 1 or 2 is missing")
+    if len(sec[1]) != 40 or struct.unpack_from("<I", sec[1])[0] != 32:
+        raise FormatError(".wtns: n8 is not 32")
+    if int.from_bytes(sec[1][4:36], "little") != R:
+        raise FormatError(".wtns: the prime is not BN128's group order")
+    n = struct.unpack_from("<I", sec[1], 36)[0]
+    if len(sec[2]) != 32 * n:
+        raise FormatError(".wtns: section 2 does not hold nWitness values")
+    return sec[2]
+
+
+def witness_bin_to_wtns(w) -> bytes:
+    """witness.bin -> snarkjs' .wtns (version 2, sections 1 and 2)"""
+    w = bytes(w)
+    if len(w) % 32:
+        raise FormatError("witness.bin: not a whole number of 32-byte values")
+    head = struct.pack("<I", 32) + R.to_bytes(32, "little") + struct.pack("<I", len(w) // 32)
+    return b"wtns" + struct.pack("<II", 2, 2) + struct.pack("<IQ", 1, len(head)) + head + struct.pack("<IQ", 2, len(w)) + w
+
+
 def _main(argv) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m wasmsnark_amd.formats")
-    ap.add_argument("tool", choices=["buildpkey", "buildwitness", "dumppkey", "dumpwitness", "pkey64"])
+    ap.add_argument("tool", choices=["buildpkey", "buildwitness", "dumppkey", "dumpwitness", "pkey64", "wtns2bin", "zkey2pkey", "pkey2zkey"])
     ap.add_argument("-i", "--input")
     ap.add_argument("-o", "--output")
+    ap.add_argument("--vk", help="verification_key.json: written by zkey2pkey, read by pkey2zkey")
+    ap.add_argument("--wtns", help="zkey2pkey: a .wtns of the circuit for one trial proof")
     a = ap.parse_args(argv)
     defaults = {"buildpkey": ("proving_key.json", "proving_key.bin"), "buildwitness": ("witness.json", "witness.bin"),
                 "dumppkey": ("proving_key.bin", "proving_key.json"), "dumpwitness": ("witness.bin", "witness.json"),
-                "pkey64": ("proving_key.bin", "proving_key.wsnark64")}
+                "pkey64": ("proving_key.bin", "proving_key.wsnark64"), "wtns2bin": ("witness.wtns", "witness.bin"),
+                "zkey2pkey": ("circuit.zkey", "proving_key.bin"), "pkey2zkey": ("proving_key.bin", "circuit.zkey")}
     src, dst = a.input or defaults[a.tool][0], a.output or defaults[a.tool][1]
+    if a.tool == "wtns2bin":
+        with open(src, "rb") as f, open(dst, "wb") as g:
+            g.write(wtns_to_witness_bin(f.read()))
+        return 0
+    if a.tool in ("zkey2pkey", "pkey2zkey"):
+        import wasmsnark_amd
+        bn = wasmsnark_amd.build()
+        if a.tool == "zkey2pkey":
+            wtns = open(a.wtns, "rb").read() if a.wtns else None
+            pkey, vk = bn.import_zkey(path=src, wtns=wtns)
+            if a.vk:
+                with open(a.vk, "w") as f:
+                    json.dump(vk, f)
+        else:
+            if not a.vk:
+                ap.error("pkey2zkey needs --vk (gamma2 and IC are not part of a proving key)")
+            with open(src, "rb") as f, open(a.vk) as g:
+                pkey = bn.export_zkey(pkey=f.read(), vk=json.load(g))
+        with open(dst, "wb") as f:
+            f.write(pkey)
+        return 0
     if a.tool == "pkey64":
         with open(src, "rb") as f:
             pkey_bin_to_container(f.read(), dst)

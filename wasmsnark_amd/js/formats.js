@@ -143,4 +143,49 @@ function writeKeyContainer(path, sec) {
 }
 function pkeyBinToContainer(key, path) { return writeKeyContainer(path, pkeyBinSections(key)); }
 
-module.exports = { pkeyJsonToBin, witnessJsonToBin, pkeyBinSections, writeKeyContainer, pkeyBinToContainer };
+/* snarkjs' .wtns: "wtns", u32 version 2, u32 nSections; section 1 = u32 n8 (32), the prime r, u32 nWitness; section 2 = nWitness x 32
+ * bytes plain little-endian, which is witness.bin as it is.  Sections are found by type. */
+const WTNS_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
+function isWtns(v) {
+    const b = bytesOf(v);
+    return b.length >= 12 && b.toString("latin1", 0, 4) === "wtns";
+}
+function wtnsToWitness(v) {
+    const b = bytesOf(v);
+    if (!isWtns(b)) throw new Error("not a .wtns file (bad magic)");
+    if (b.readUInt32LE(4) !== 2) throw new Error(".wtns version " + b.readUInt32LE(4) + " is not 2");
+    const sec = new Map();
+    let at = 12;
+    for (let k = 0; k < b.readUInt32LE(8); k++) {
+        if (b.length - at < 12) throw new Error(".wtns: truncated section header");
+        const type = b.readUInt32LE(at), size = Number(b.readBigUInt64LE(at + 4));
+        at += 12;
+        if (size > b.length - at) throw new Error(".wtns: truncated section " + type);
+        if (sec.has(type)) throw new Error(".wtns: section " + type + " is present twice");
+        sec.set(type, b.subarray(at, at + size));
+        at += size;
+    }
+    const h = sec.get(1), w = sec.get(2);
+    if (!h || !w) throw new Error(".wtns: section 1 or 2 is missing");
+    if (h.length !== 40 || h.readUInt32LE(0) !== 32) throw new Error(".wtns: n8 is not 32");
+    let r = 0n;
+    for (let i = 31; i >= 0; i--) r = (r << 8n) | BigInt(h[4 + i]);
+    if (r !== WTNS_R) throw new Error(".wtns: the prime is not BN128's group order");
+    if (w.length !== 32 * h.readUInt32LE(36)) throw new Error(".wtns: section 2 does not hold nWitness values");
+    return w;
+}
+function witnessToWtns(v) {
+    const w = bytesOf(v);
+    if (w.length % 32) throw new Error("witness.bin: not a whole number of 32-byte values");
+    const head = Buffer.alloc(12 + 12 + 40 + 12);
+    head.write("wtns", 0, "latin1"); head.writeUInt32LE(2, 4); head.writeUInt32LE(2, 8);
+    head.writeUInt32LE(1, 12); head.writeBigUInt64LE(40n, 16);
+    head.writeUInt32LE(32, 24);
+    let r = WTNS_R;
+    for (let i = 0; i < 32; i++) { head[28 + i] = Number(r & 255n); r >>= 8n; }
+    head.writeUInt32LE(w.length / 32, 60);
+    head.writeUInt32LE(2, 64); head.writeBigUInt64LE(BigInt(w.length), 68);
+    return Buffer.concat([head, w]);
+}
+
+module.exports = { pkeyJsonToBin, witnessJsonToBin, pkeyBinSections, writeKeyContainer, pkeyBinToContainer, isWtns, wtnsToWitness, witnessToWtns };

@@ -537,6 +537,57 @@ class Bn128 {
         const pols = lens.map((n) => { const b = Buffer.from(ab, off, n); off += n; return b; });
         return { nVars: rows.nVars, nPublic: rows.nPublic, domain: v.getUint32(0, true), polsA: pols[0], polsB: pols[1], polsC: pols[2], report };
     }
+    /* No counterpart in the reference: snarkjs' .zkey in and out (include/wsnark.h: wsnark_zkey_*; a key of one GPU's 4 GiB at most).
+     * zkeyInfo(zkey) -> {nVars, nPublic, domain, nCoeffs, records: [A, B], nContributions, pkeyLen, vkLen}, host work only.
+     * importZkey(zkey bytes | path, {wtns}) -> {pkey: Buffer (proving_key.bin), vk: the verification key object, report}.  The
+     * coefficient records become the key's column streams and the H section changes basis on the device; the other point sections
+     * are copied and NOT audited (checkKey does that).  opts.wtns: .wtns (or witness.bin) bytes of a witness of the circuit -- a TRIAL
+     * PROOF: it is proved with the new key and verified against the returned vk, and the call rejects if that fails, so that a file
+     * written under another convention than this reader's fails here and not in production.
+     * exportZkey(pkey bytes, vk) -> Buffer (.zkey): gamma2 and IC come from vk; section 10 holds no contributions and a zero circuit
+     * hash, so provers take the file and `snarkjs zkey verify` does not. */
+    zkeyInfo(zkey) {
+        const v = new DataView(addon.zkeyInfo(typeof zkey === "string" ? require("fs").readFileSync(zkey) : zkey));
+        return { nVars: v.getUint32(0, true), nPublic: v.getUint32(4, true), domain: v.getUint32(8, true), nCoeffs: v.getUint32(12, true),
+                 records: [Number(v.getBigUint64(16, true)), Number(v.getBigUint64(24, true))], nContributions: v.getUint32(32, true),
+                 pkeyLen: Number(v.getBigUint64(40, true)), vkLen: Number(v.getBigUint64(48, true)) };
+    }
+    async importZkey(zkey, opts) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: importZkey runs on a single GPU (build a Bn128 without {devices})");
+        if (typeof zkey === "string") zkey = require("fs").readFileSync(zkey);
+        const ab = await addon.importZkey(zkey);
+        const v = new DataView(ab);
+        const keyLen = Number(v.getBigUint64(0, true)), vkLen = Number(v.getBigUint64(8, true));
+        const report = zkeyReport(v, 16);
+        const vkb = Buffer.from(ab, 152, vkLen), pkey = Buffer.from(ab, 152 + vkLen, keyLen);
+        const nPublic = (vkLen - 448) / 64 - 1;
+        const dec = (o) => { let x = 0n; for (let i = 31; i >= 0; i--) x = (x << 8n) | BigInt(vkb[o + i]); return x.toString(); };
+        const g1 = (o) => [dec(o), dec(o + 32), "1"], g2 = (o) => [[dec(o), dec(o + 32)], [dec(o + 64), dec(o + 96)], ["1", "0"]];
+        const vk = { protocol: "groth", nPublic, vk_alfa_1: g1(0), vk_beta_2: g2(64), vk_gamma_2: g2(192), vk_delta_2: g2(320), IC: [] };
+        for (let i = 0; i <= nPublic; i++) vk.IC.push(g1(448 + 64 * i));
+        if (opts && opts.wtns) {
+            const wit = formats.isWtns(opts.wtns) ? formats.wtnsToWitness(opts.wtns) : Buffer.from(asBytes(opts.wtns));
+            const proof = await this.groth16GenProof(wit, pkey, { trustCache: false });
+            const pub = [];
+            for (let i = 1; i <= nPublic; i++) { let x = 0n; for (let k = 31; k >= 0; k--) x = (x << 8n) | BigInt(wit[32 * i + k]); pub.push(x.toString()); }
+            if (!(await this.groth16Verify(vk, pub, proof)))
+                throw new Error("wsnark: importZkey: the trial proof of the given witness does not verify against the file's verification key -- " +
+                                "the file's coefficients or H section follow another convention than this reader's, or the witness is not one of this circuit");
+        }
+        return { pkey, vk, report };
+    }
+    async exportZkey(pkey, vk) {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: exportZkey runs on a single GPU (build a Bn128 without {devices})");
+        if (!vk || !vk.IC) throw new Error("wsnark: exportZkey needs the verification key (gamma2 and IC are not part of a proving key)");
+        const g1 = (p) => [p[0], p[1]], g2 = (p) => [p[0][0], p[0][1], p[1][0], p[1][1]];
+        const vkb = le32cat([].concat(g1(vk.vk_alfa_1), g2(vk.vk_beta_2), g2(vk.vk_gamma_2), g2(vk.vk_delta_2), ...vk.IC.map(g1)).map((x) => BigInt(x)));
+        const ab = await addon.exportZkey(pkey, vkb, vk.IC.length - 1);
+        const out = Buffer.from(ab, 152, Number(new DataView(ab).getBigUint64(0, true)));
+        out.report = zkeyReport(new DataView(ab), 16);
+        return out;
+    }
     /* A key FILE -- the reference's proving_key.bin or the WSNARK64 container for keys beyond its 4 GiB (js/formats.js:
      * writeKeyContainer; 2^24 constraints = 7.8 GB, more than one Buffer holds).  The library maps the file and reads only what it makes
      * resident; with a group every device reads its own shard.  Handles are cached per path while the file's size and mtime stand. */
@@ -570,6 +621,8 @@ class Bn128 {
      * bad constraint and its a, b, c (.report holds the whole report); no proof is computed.  Without it nothing changes. */
     async groth16GenProof(signals, pkey, opts) {
         if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        // a snarkjs .wtns is taken for its section 2, which is witness.bin (found by its magic: a witness.bin starts with the signal 1)
+        if ((signals instanceof ArrayBuffer || ArrayBuffer.isView(signals)) && formats.isWtns(signals)) signals = formats.wtnsToWitness(signals);
         const t0 = process.hrtime.bigint();
         if (opts && opts.circuit) {
             const ci = opts.circuit.info(), ki = await this.keyInfo(pkey);
@@ -774,6 +827,16 @@ async function buildBn128(device, opts) {
 function terminate() {
     if (singleton) { singleton.terminate(); singleton = null; }
 }
+function zkeyReport(v, o) {      // wsnark_zkey_report_t
+    const pair = (at) => [Number(v.getBigUint64(o + at, true)), Number(v.getBigUint64(o + at + 8, true))];
+    const bad = Number(v.getBigUint64(o + 72, true));
+    return { records: pair(0), unreduced: pair(16), zero: pair(32), sorted: v.getUint32(o + 48, true) !== 0,
+             H: { points: Number(v.getBigUint64(o + 56, true)), infinity: Number(v.getBigUint64(o + 64, true)), bad,
+                  firstBad: bad ? Number(v.getBigUint64(o + 80, true)) : null },
+             ms: { upload: v.getFloat64(o + 96, true), coefficients: v.getFloat64(o + 104, true), hBasis: v.getFloat64(o + 112, true),
+                   download: v.getFloat64(o + 120, true), total: v.getFloat64(o + 128, true) } };
+}
+
 function groth16GenProof(witness, provingKey, cb) {   // main_bn128.js:26-39
     const p = (async () => {
         if (!singleton) singleton = await buildBn128();
@@ -814,4 +877,5 @@ function groth16VerifyBatch(verificationKey, inputs, proofs, cb) {
 const formats = require("./formats.js");     // snarkjs JSON -> proving_key.bin / witness.bin (reference tools/build*.js)
 module.exports = { buildBn128, groth16GenProof, groth16GenProofBatch, genZKSnarkProof: groth16GenProof, groth16Verify, groth16VerifyBatch, terminate, Bn128, proofFromBytes,
     pkeyJsonToBin: formats.pkeyJsonToBin, witnessJsonToBin: formats.witnessJsonToBin,
-    pkeyBinSections: formats.pkeyBinSections, writeKeyContainer: formats.writeKeyContainer, pkeyBinToContainer: formats.pkeyBinToContainer };
+    pkeyBinSections: formats.pkeyBinSections, writeKeyContainer: formats.writeKeyContainer, pkeyBinToContainer: formats.pkeyBinToContainer,
+    wtnsToWitness: formats.wtnsToWitness, witnessToWtns: formats.witnessToWtns };

@@ -78,6 +78,11 @@ static struct {
     int (*g2_ntt)(const void*, uint64_t, int, void*);
     int (*pkey_setup_pkey)(const void*, const void*, void*, size_t, size_t*, void*, void*);
     int (*pkey_setup_size)(const void*, size_t*);
+    /* snarkjs' .zkey in and out (include/wsnark.h: wsnark_zkey_*) */
+    int (*zkey_info)(const void*, size_t, void*);
+    int (*zkey_import)(const void*, size_t, void*, size_t, size_t*, void*, size_t, void*);
+    int (*zkey_export)(const void*, size_t, const void*, size_t, uint64_t, void*, size_t, size_t*, void*);
+    int (*zkey_export_size)(uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, size_t*);
     /* powers of tau (include/wsnark.h: wsnark_g{1,2}_mul_batch, wsnark_powers_contribute, wsnark_powers_check) */
     int (*g1_mul)(const void*, const void*, uint64_t, void*);
     int (*g2_mul)(const void*, const void*, uint64_t, void*);
@@ -148,6 +153,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(circuit_witness_check_batch, "wsnark_circuit_witness_check_batch")
     SYM(circuit_from_rows_size, "wsnark_circuit_from_rows_size") SYM(circuit_from_rows, "wsnark_circuit_from_rows")
     SYM(circuit_load_rows, "wsnark_circuit_load_rows")
+    SYM(zkey_info, "wsnark_zkey_info") SYM(zkey_import, "wsnark_zkey_import") SYM(zkey_export, "wsnark_zkey_export") SYM(zkey_export_size, "wsnark_zkey_export_size")
 #undef SYM
     return 0;
 }
@@ -177,7 +183,7 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
        OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
        OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
-       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH, OP_CIRCUIT_FROM_ROWS, OP_CIRCUIT_LOAD_ROWS };
+       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH, OP_CIRCUIT_FROM_ROWS, OP_CIRCUIT_LOAD_ROWS, OP_ZKEY_IMPORT, OP_ZKEY_EXPORT };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -311,6 +317,9 @@ static int hash_bytes(const uint8_t* p, size_t n, uint8_t out[16]) {
 #define WITNESS_VERDICT_BYTES 48         /* sizeof(wsnark_witness_verdict_t) */
 #define WITNESS_BATCH_REPORT_BYTES 64    /* sizeof(wsnark_witness_batch_report_t) */
 #define ROWS_REPORT_BYTES 152            /* sizeof(wsnark_rows_report_t) */
+#define ZKEY_INFO_BYTES 56              /* sizeof(wsnark_zkey_info_t) */
+#define ZKEY_REPORT_BYTES 136           /* sizeof(wsnark_zkey_report_t) */
+#define ZKEY_HEAD_BYTES (16 + ZKEY_REPORT_BYTES)      /* importZkey / exportZkey: u64 length of the key or file, u64 length of the vk, the report */
 #define ROWS_HEAD_BYTES (8 + 24 + ROWS_REPORT_BYTES)      /* circuitFromRows: u32 domain, u32 0, lens[3], the report; then the three streams */
 /* wsnark_powers_t and wsnark_circuit_t (include/wsnark.h) */
 typedef struct {
@@ -374,6 +383,36 @@ static void job_execute(napi_env env, void* data) {
     case OP_DELTA_VERIFY:
         j->rc = j->path ? L.pkey_delta_verify_file(j->path, j->path2, j->r32, j->out) : L.pkey_delta_verify(j->a, j->na, j->b, j->nb, j->r32, j->out);
         break;
+    case OP_ZKEY_IMPORT: {   /* out (sized here, from the file's own header): the head, the vk, proving_key.bin */
+        uint8_t info[ZKEY_INFO_BYTES];
+        uint64_t pkey_len, vk_len;
+        if ((j->rc = L.zkey_info(j->a, j->na, info))) break;
+        memcpy(&pkey_len, info + 40, 8); memcpy(&vk_len, info + 48, 8);
+        j->nout = ZKEY_HEAD_BYTES + (size_t)vk_len + (size_t)pkey_len;
+        j->out = (uint8_t*)calloc(j->nout, 1);
+        if (!j->out) { j->rc = -1; snprintf(j->err, sizeof j->err, "wsnark: out of memory for the imported key"); return; }
+        size_t len = 0;
+        j->rc = L.zkey_import(j->a, j->na, j->out + ZKEY_HEAD_BYTES + vk_len, (size_t)pkey_len, &len, j->out + ZKEY_HEAD_BYTES, (size_t)vk_len, j->out + 16);
+        pkey_len = len;
+        memcpy(j->out, &pkey_len, 8); memcpy(j->out + 8, &vk_len, 8);
+        break;
+    }
+    case OP_ZKEY_EXPORT: {   /* a = proving_key.bin, b = the vk in the verifier's layout, u0 = nPublic; out: the head, the file */
+        uint32_t h[10];
+        size_t len = 0;
+        if (j->na < 40) { j->rc = -1; snprintf(j->err, sizeof j->err, "wsnark: the key is shorter than its header"); return; }
+        memcpy(h, j->a, 40);
+        const uint64_t la = (uint64_t)h[4] - h[3], lb = (uint64_t)h[5] - h[4], heads = 4 * (uint64_t)h[0];
+        if ((j->rc = L.zkey_export_size(h[0], h[1], h[2], la > heads ? (la - heads) / 36 : 0, lb > heads ? (lb - heads) / 36 : 0, &len))) break;
+        j->nout = ZKEY_HEAD_BYTES + len;
+        j->out = (uint8_t*)calloc(j->nout, 1);
+        if (!j->out) { j->rc = -1; snprintf(j->err, sizeof j->err, "wsnark: out of memory for the file"); return; }
+        size_t cap = len;
+        j->rc = L.zkey_export(j->a, j->na, j->b, j->nb, j->u0, j->out + ZKEY_HEAD_BYTES, cap, &len, j->out + 16);
+        uint64_t l64 = len;
+        memcpy(j->out, &l64, 8);
+        break;
+    }
     case OP_GROUP_NTT: j->rc = (j->i0 == 2 ? L.g2_ntt : L.g1_ntt)(j->a, j->na / (j->i0 == 2 ? 128 : 64), j->i1, j->out); break;
     case OP_NEW_KEY: {       /* out = the report (192 B), IC ((nPublic + 1) x 64 B), the key */
         powers_t P;
@@ -870,6 +909,48 @@ static napi_value js_group_ntt(napi_env env, napi_callback_info info) {
     if (!j->out) FAIL(env, j, "out of memory");
     keep(env, j, argv[1]);
     return start_job(env, j, "wsnark_group_ntt");
+}
+/* zkeyInfo(zkey) -> ArrayBuffer 56: the wsnark_zkey_info_t of a .zkey (host work only, synchronous) */
+static napi_value js_zkey_info(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1], res;
+    uint8_t* p; size_t n;
+    void* dst;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (!L.h) { napi_throw_error(env, NULL, "wsnark_napi: init() has not been called (use buildBn128())"); return NULL; }
+    if (argc < 1 || !get_bytes(env, argv[0], &p, &n)) { napi_throw_type_error(env, NULL, "expected (zkey bytes)"); return NULL; }
+    uint8_t out[ZKEY_INFO_BYTES];
+    const int rc = L.zkey_info(p, n, out);
+    if (rc) {
+        char msg[600];
+        snprintf(msg, sizeof msg, "wsnark error %d: %s", rc, L.last_error());
+        napi_throw_error(env, NULL, msg);
+        return NULL;
+    }
+    CHECK(env, napi_create_arraybuffer(env, sizeof out, &dst, &res));
+    memcpy(dst, out, sizeof out);
+    return res;
+}
+/* importZkey(zkey) -> Promise<ArrayBuffer>: u64 key length, u64 vk length, the wsnark_zkey_report_t, the vk (the verifier's plain
+ * layout), proving_key.bin (wsnark_zkey_import) */
+static napi_value js_import_zkey(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_ZKEY_IMPORT;
+    if (argc < 1 || !get_bytes(env, argv[0], &j->a, &j->na)) FAIL(env, j, "expected (zkey bytes)");
+    keep(env, j, argv[0]);
+    return start_job(env, j, "wsnark_zkey_import");
+}
+/* exportZkey(pkey, vk bytes, nPublic) -> Promise<ArrayBuffer>: u64 file length, u64 0, the wsnark_zkey_report_t, the .zkey (wsnark_zkey_export) */
+static napi_value js_export_zkey(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_ZKEY_EXPORT;
+    if (argc < 3 || !get_bytes(env, argv[0], &j->a, &j->na) || !get_bytes(env, argv[1], &j->b, &j->nb) || napi_get_value_uint32(env, argv[2], &j->u0) != napi_ok)
+        FAIL(env, j, "expected (proving_key.bin bytes, verification key bytes, nPublic)");
+    keep(env, j, argv[0]); keep(env, j, argv[1]);
+    return start_job(env, j, "wsnark_zkey_export");
 }
 /* newKey(nVars, nPublic, domain, [tauG1, tauG2, alphaTauG1, betaTauG1, betaG2, polsA, polsB, polsC]) -> Promise<ArrayBuffer>: the
  * wsnark_pkey_setup_report_t (192 bytes), the nPublic + 1 IC points, then proving_key.bin (wsnark_pkey_setup_pkey) */
@@ -1470,6 +1551,9 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"contributeKey", NULL, js_contribute_key, NULL, NULL, NULL, napi_default, NULL},
         {"deltaVerify", NULL, js_delta_verify, NULL, NULL, NULL, napi_default, NULL},
         {"groupNtt", NULL, js_group_ntt, NULL, NULL, NULL, napi_default, NULL},
+        {"zkeyInfo", NULL, js_zkey_info, NULL, NULL, NULL, napi_default, NULL},
+        {"importZkey", NULL, js_import_zkey, NULL, NULL, NULL, napi_default, NULL},
+        {"exportZkey", NULL, js_export_zkey, NULL, NULL, NULL, napi_default, NULL},
         {"newKey", NULL, js_new_key, NULL, NULL, NULL, napi_default, NULL},
         {"mulPoints", NULL, js_mul_points, NULL, NULL, NULL, napi_default, NULL},
         {"contributePowers", NULL, js_contribute_powers, NULL, NULL, NULL, napi_default, NULL},
