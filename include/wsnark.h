@@ -821,6 +821,60 @@ int wsnark_groth16_verify_batch(const void* vk, size_t vk_len, const void* input
 int wsnark_groth16_verify_batch_dev(const void* vk, size_t vk_len, const void* d_inputs, uint64_t n_inputs, const void* d_proofs384,
                                     uint64_t count, uint8_t* status_host, void* stream);
 
+/* ---- compressed points and 128-byte proofs (csrc/pointcodec.hip): NO reference counterpart ----
+ * The reference speaks proofs only as 384-byte records; every other Groth16 stack on this curve hands points around compressed: x and
+ * one bit that names the root y of y^2 = x^3 + b (b = 3 on G1, 3 / (9 + u) on the twist).  32 bytes per G1 point, 64 per G2 point,
+ * 128 per proof.  q < 2^254, so the top two bits of x are free for flags.  "Larger" root: the one whose PLAIN value is > (q - 1) / 2; on
+ * G2 decided on y.c1 if that is not zero, else on y.c0 (the same as y > -y with c1 compared before c0).
+ *   WSNARK_ENC_LE  x little-endian; G2 is x.c0 | x.c1; flags in the top two bits of the LAST byte: 0x80 = y is the larger root,
+ *                  0x40 = infinity (every other bit zero); both set is malformed.           (ark-serialize's compressed mode, BN254)
+ *   WSNARK_ENC_BE  x big-endian; G2 is x.c1 | x.c0; flags in the top two bits of the FIRST byte: 0b10 = smaller root, 0b11 = larger
+ *                  root, 0b01 = infinity (every other bit zero); 0b00 ("uncompressed") is malformed here.  (gnark-crypto's bn254 marshal)
+ *   G1 = (1, 2):  01 00 .. 00 (LE),  80 00 .. 00 01 (BE);   -G1:  01 00 .. 00 80 (LE),  C0 00 .. 00 01 (BE);   infinity:  00 .. 00 40 (LE),
+ *   40 00 .. 00 (BE).
+ * NOT VERIFIED against either library: both layouts were written from knowledge of them; no file written by arkworks or gnark was
+ * available.  The statement above is the contract, and the tests pin it.
+ *
+ * Points (host memory both ways; streamed through the staging ring in chunks, so device memory does not grow with n):
+ *   compress    points: n affine points in key format (Montgomery words, 64 / 128 bytes, every word of x zero = infinity, the loaders'
+ *               rule) -> out: n x 32 / 64 bytes; status[i]: 0 = ok, 1 = a coordinate >= q, and that record is all zero.  The curve
+ *               equation is NOT tested (that is wsnark_pkey_check's job): any reduced (x, y) is compressed.
+ *   decompress  in: n x 32 / 64 bytes -> out_points: n affine points in key format (infinity: all zero); status[i] one of WSNARK_DEC_*;
+ *               the smallest number wins when several reasons apply; a point whose status is not 0 is written as all zero bytes.
+ *               flags: 0, or WSNARK_DEC_SUBGROUP (G2 only: the audit's [r] Q == O chain; ignored on G1, whose curve has prime order).
+ *   *n_bad: how many statuses are not 0, counted on the device.
+ * Proofs: a compressed proof is A | B | C at 32 + 64 + 32 bytes, the order in which both libraries write one; the 384-byte record is
+ * wsnark_groth16_prove's (plain little-endian integers).  status[i] has wsnark_groth16_verify_batch's meaning:
+ *   proof_compress     1 = written; 2 = one of the twelve words (z included) is not a reduced field element: a zero record.  The z
+ *                      words are otherwise ignored, as the verifiers ignore them; a component with x = 0 is written as infinity.
+ *   proof_decompress   1 = written, with z = 1 (z.c0 = 1, z.c1 = 0 for B); 2 = a malformed point; 0 = a point without a y, or one
+ *                      encoded as infinity (no verifier accepts a proof with a component at infinity).  0 and 2: a zero record.
+ *                      B's subgroup membership is not tested here: the verifiers test it.
+ *   verify_batch_compressed[_dev]   status[i] is exactly what wsnark_groth16_verify_batch says about the decompressed proof i: a proof
+ *                      with a malformed point is 2, one with a point without a y or at infinity is 0.  The proofs are decompressed on
+ *                      the device into the records the batch verifier's first kernel reads; nothing returns to the host in between.
+ *                      vk, inputs, count == 0, count > 2^24, the key-level outcomes, lanes and threads: as wsnark_groth16_verify_batch.
+ *                      _dev: d_inputs and d_proofs128 (16-byte aligned) in device memory, read on `stream` (NULL: the lane's queue).
+ * Every call here needs wsnark_init (WSNARK_ERR_NOINIT), returns WSNARK_ERR_ARG for an encoding that is not WSNARK_ENC_*, for an
+ * undefined flag and for a NULL pointer, WSNARK_OK without touching anything for n == 0 / count == 0, and leaves its outputs untouched
+ * on any error.
+ * Out of scope: readers of arkworks or gnark KEY files; a compressed key container; square roots in Fr; a host-only path without
+ * wsnark_init; group (multi-GPU) handles; provers that emit compressed proofs directly (wsnark_proof_compress on their output is the
+ * path). */
+enum { WSNARK_ENC_LE = 1, WSNARK_ENC_BE = 2 };
+enum { WSNARK_DEC_OK = 0, WSNARK_DEC_MALFORMED = 1, WSNARK_DEC_NO_POINT = 2, WSNARK_DEC_OUTSIDE_SUBGROUP = 3 };
+enum { WSNARK_DEC_SUBGROUP = 1 };      /* flags of the decompress calls */
+int wsnark_g1_compress(const void* points, uint64_t n, int encoding, void* out, uint8_t* status, uint64_t* n_bad);
+int wsnark_g2_compress(const void* points, uint64_t n, int encoding, void* out, uint8_t* status, uint64_t* n_bad);
+int wsnark_g1_decompress(const void* in, uint64_t n, int encoding, uint32_t flags, void* out_points, uint8_t* status, uint64_t* n_bad);
+int wsnark_g2_decompress(const void* in, uint64_t n, int encoding, uint32_t flags, void* out_points, uint8_t* status, uint64_t* n_bad);
+int wsnark_proof_compress(const void* proofs384, uint64_t count, int encoding, void* out128, uint8_t* status);
+int wsnark_proof_decompress(const void* proofs128, uint64_t count, int encoding, void* out384, uint8_t* status);
+int wsnark_groth16_verify_batch_compressed(const void* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proofs128,
+                                           uint64_t count, int encoding, uint8_t* status);
+int wsnark_groth16_verify_batch_compressed_dev(const void* vk, size_t vk_len, const void* d_inputs, uint64_t n_inputs, const void* d_proofs128,
+                                               uint64_t count, int encoding, uint8_t* status_host, void* stream);
+
 /* ---- many witnesses of ONE key in one call (csrc/provebatch.hip): NO reference counterpart ----
  * The reference's groth16GenProof takes one witness (src/bn128.js:580-720); a proving service holds one small circuit (2^10 .. 2^16
  * constraints) and many witnesses, and a single proof of that size leaves most of the device idle.
@@ -1027,7 +1081,13 @@ enum {
                                     inversion a^(p-2) on that field -- what the table build's normalisation runs (msm_table_norm_kernel) */
     WSNARK_ST_SQR_WEAK = 15,     /* (a - b)^2 with the uncorrected difference as the operand of the squaring        */
     WSNARK_ST_MUL_WEAK_A = 16,   /* (a - b) * b with the uncorrected difference as the FIRST operand of the product */
-    WSNARK_ST_MULSUB2_WEAK_B = 17 /* a*(a - b) - b*a: fused, second operand an uncorrected difference              */
+    WSNARK_ST_MULSUB2_WEAK_B = 17, /* a*(a - b) - b*a: fused, second operand an uncorrected difference              */
+    /* square roots (the reference's f1m_sqrt / f1m_isSquare, src/build_f1m.js:809-897): `which` 0 (Fq: a^((q+1)/4), q = 3 mod 4) and
+       2 (Fq2: the complex method, two exponentiations and no inversion); b is ignored.  `which` 1 (Fr) is WSNARK_ERR_ARG: Tonelli-Shanks
+       over a field of 2-adicity 28 has no user here.  impl 0 = the device's radix-2^29 field, 2 = the host's. */
+    WSNARK_ST_SQRT = 18,         /* Fq: the root whose PLAIN value is even, as the reference picks it (build_f1m.js:871-875); Fq2: the
+                                    not-larger root (WSNARK_ENC_* below: "larger").  A non-square: every output byte 0xFF.  sqrt(0) = 0 */
+    WSNARK_ST_IS_SQUARE = 19     /* out = 1 if a is a square (0 is one), else 0                                          */
 };
 int wsnark_selftest_field(int which, int impl, int op, const void* a, const void* b, void* out, uint64_t n);
 /*   g: 1 or 2; impl: 0 = radix-2^29 curve of the accumulation kernels, 1 = saturated-field curve on the device,

@@ -1582,6 +1582,41 @@ class Bn128:
         (1 valid, 0 invalid, 2 malformed)."""
         return groth16_verify_batch(self.lib, verificationKey, inputs, proofs, return_status)
 
+    # --- compressed points and 128-byte proofs (csrc/pointcodec.hip; include/wsnark.h has both encodings byte by byte) ---
+    def compress_points(self, g, points, encoding):
+        """points: affine Montgomery points (64 bytes each for g = 1, 128 for g = 2; x == 0 is infinity) -> (32 / 64 bytes per point,
+        status list: 0 ok, 1 a coordinate >= q -- that record is zero).  encoding: "le" (ark-serialize's compressed mode) or "be"
+        (gnark-crypto's marshal).  The curve equation is not tested: check_key does that.  wsnark_g{1,2}_compress."""
+        return _points_codec(self.lib, g, True, points, encoding, False)
+
+    def decompress_points(self, g, data, encoding, subgroup=False):
+        """data: 32 / 64 bytes per point -> (affine Montgomery points, infinity and every bad point as zero bytes; status list: 0 ok,
+        1 malformed, 2 no point with that x, 3 outside the order-r subgroup -- g = 2 with subgroup=True only).
+        wsnark_g{1,2}_decompress."""
+        return _points_codec(self.lib, g, False, data, encoding, subgroup)
+
+    def compress_proofs(self, proofs, encoding):
+        """proofs: a list of {pi_a, pi_b, pi_c} as the provers return them -> (128 bytes per proof: A | B | C, status list: 1 written,
+        2 a number of that proof is not a reduced field element -- a zero record).  wsnark_proof_compress."""
+        proofs = list(proofs)
+        for pr in proofs:
+            if any(not 0 <= int(v) < 1 << 256 for v in list(pr["pi_a"]) + [x for pair in pr["pi_b"] for x in pair] + list(pr["pi_c"])):
+                raise ValueError("a proof's numbers must lie in [0, 2^256)")
+        out, st = _proofs_codec(self.lib, True, b"".join(proof_to_bytes(pr) for pr in proofs), encoding)
+        return out, st
+
+    def decompress_proofs(self, data, encoding):
+        """data: 128 bytes per proof -> (a list of {pi_a, pi_b, pi_c} with z = 1, None where the status is not 1; status list: 1 written,
+        2 a malformed point, 0 a point without a y or encoded as infinity).  wsnark_proof_decompress."""
+        out, st = _proofs_codec(self.lib, False, data, encoding)
+        return [proof_from_bytes(out[384 * i:384 * i + 384]) if v == 1 else None for i, v in enumerate(st)], st
+
+    def groth16VerifyBatchCompressed(self, verificationKey, inputs, proof_bytes, encoding, return_status=False):
+        """groth16VerifyBatch on 128-byte proofs (wsnark_groth16_verify_batch_compressed): they are decompressed on the GPU and verified
+        there.  proof_bytes: 128 bytes per proof, or a list of 128-byte strings.  Proof by proof what groth16VerifyBatch says about the
+        decompressed proof; a malformed point is status 2, a point without a y or at infinity status 0."""
+        return groth16_verify_batch_compressed(self.lib, verificationKey, inputs, proof_bytes, encoding, return_status)
+
     def terminate(self):  # src/bn128.js:562-566
         self.lib.shutdown()
 
@@ -1646,6 +1681,80 @@ def groth16_verify_batch(lib, verificationKey, inputs, proofs, return_status=Fal
         prf = b"".join(proof_to_bytes(proofs[i]) for i in keep)
         st = (C.c_uint8 * len(keep))()
         lib.check(lib.c.wsnark_groth16_verify_batch(vkb, len(vkb), inp if n_in else None, n_in, prf, len(keep), st))
+        for i, v in zip(keep, st):
+            status[i] = int(v)
+    return status if return_status else [v == 1 for v in status]
+
+
+ENCODINGS = {"le": 1, "be": 2}      # WSNARK_ENC_LE, WSNARK_ENC_BE
+
+
+def _encoding(name):
+    if name not in ENCODINGS:
+        raise ValueError("encoding must be one of %s" % ", ".join(repr(k) for k in ENCODINGS))
+    return ENCODINGS[name]
+
+
+def _points_codec(lib, g, compress, data, encoding, subgroup):
+    if g not in (1, 2):
+        raise ValueError("g must be 1 or 2")
+    enc = _encoding(encoding)
+    b, nb = _ro(data)
+    in_sz, out_sz = (64 * g, 32 * g) if compress else (32 * g, 64 * g)
+    if nb % in_sz:
+        raise ValueError("expected a whole number of %d-byte records" % in_sz)
+    n = nb // in_sz
+    out, st, bad = (C.c_uint8 * max(n * out_sz, 1))(), (C.c_uint8 * max(n, 1))(), C.c_uint64(0)
+    if compress:
+        fn = lib.c.wsnark_g1_compress if g == 1 else lib.c.wsnark_g2_compress
+        lib.check(fn(b, n, enc, out, st, C.byref(bad)))
+    else:
+        fn = lib.c.wsnark_g1_decompress if g == 1 else lib.c.wsnark_g2_decompress
+        lib.check(fn(b, n, enc, 1 if subgroup else 0, out, st, C.byref(bad)))
+    return bytes(out)[:n * out_sz], list(st)[:n]
+
+
+def _proofs_codec(lib, compress, data, encoding):
+    enc = _encoding(encoding)
+    if isinstance(data, (list, tuple)):
+        data = b"".join(data)
+    b, nb = _ro(data)
+    in_sz, out_sz = (384, 128) if compress else (128, 384)
+    if nb % in_sz:
+        raise ValueError("expected a whole number of %d-byte proofs" % in_sz)
+    n = nb // in_sz
+    out, st = (C.c_uint8 * max(n * out_sz, 1))(), (C.c_uint8 * max(n, 1))()
+    lib.check((lib.c.wsnark_proof_compress if compress else lib.c.wsnark_proof_decompress)(b, n, enc, out, st))
+    return bytes(out)[:n * out_sz], list(st)[:n]
+
+
+def groth16_verify_batch_compressed(lib, verificationKey, inputs, proof_bytes, encoding, return_status=False):
+    """Bn128.groth16VerifyBatchCompressed over wsnark_groth16_verify_batch_compressed: needs an initialised library (a GPU)."""
+    enc = _encoding(encoding)
+    if isinstance(proof_bytes, (list, tuple)):
+        proof_bytes = b"".join(proof_bytes)
+    proof_bytes = bytes(proof_bytes)
+    if len(proof_bytes) % 128:
+        raise ValueError("expected a whole number of 128-byte proofs")
+    n = len(proof_bytes) // 128
+    inputs = [list(x) if isinstance(x, (list, tuple)) else ([] if x is None else [x]) for x in inputs]
+    if len(inputs) != n:
+        raise ValueError("%d input vectors for %d proofs" % (len(inputs), n))
+    if not n:
+        return []
+    n_in = len(inputs[0])
+    if any(len(x) != n_in for x in inputs):
+        raise ValueError("all proofs of a batch share the key, so every input vector must have %d entries" % n_in)
+    vkb = vk_to_bytes(verificationKey, n_in)
+    vals = [[int(v) for v in x] for x in inputs]
+    # an input outside [0, 2^256) makes that proof invalid without reaching the library, as in groth16_verify_batch
+    keep = [i for i, x in enumerate(vals) if all(0 <= v < 1 << 256 for v in x)]
+    status = [0] * n
+    if keep:
+        inp = b"".join(v.to_bytes(32, "little") for i in keep for v in vals[i])
+        prf = b"".join(proof_bytes[128 * i:128 * i + 128] for i in keep)
+        st = (C.c_uint8 * len(keep))()
+        lib.check(lib.c.wsnark_groth16_verify_batch_compressed(vkb, len(vkb), inp if n_in else None, n_in, prf, len(keep), enc, st))
         for i, v in zip(keep, st):
             status[i] = int(v)
     return status if return_status else [v == 1 for v in status]

@@ -667,6 +667,42 @@ int wsnark_groth16_verify_batch_dev(const void* vk, size_t vk_len, const void* d
     REQUIRE_CTX();
     return groth16_verify_batch((const uint8_t*)vk, vk_len, d_inputs, n_inputs, d_proofs384, count, status_host, true, (hipStream_t)stream);
 }
+// compressed points and proofs (pointcodec.hip)
+int wsnark_g1_compress(const void* points, uint64_t n, int encoding, void* out, uint8_t* status, uint64_t* n_bad) {
+    REQUIRE_CTX();
+    return points_codec(1, true, points, n, encoding, 0, out, status, n_bad);
+}
+int wsnark_g2_compress(const void* points, uint64_t n, int encoding, void* out, uint8_t* status, uint64_t* n_bad) {
+    REQUIRE_CTX();
+    return points_codec(2, true, points, n, encoding, 0, out, status, n_bad);
+}
+int wsnark_g1_decompress(const void* in, uint64_t n, int encoding, uint32_t flags, void* out_points, uint8_t* status, uint64_t* n_bad) {
+    REQUIRE_CTX();
+    return points_codec(1, false, in, n, encoding, flags, out_points, status, n_bad);
+}
+int wsnark_g2_decompress(const void* in, uint64_t n, int encoding, uint32_t flags, void* out_points, uint8_t* status, uint64_t* n_bad) {
+    REQUIRE_CTX();
+    return points_codec(2, false, in, n, encoding, flags, out_points, status, n_bad);
+}
+int wsnark_proof_compress(const void* proofs384, uint64_t count, int encoding, void* out128, uint8_t* status) {
+    REQUIRE_CTX();
+    return proofs_codec(true, proofs384, count, encoding, out128, status);
+}
+int wsnark_proof_decompress(const void* proofs128, uint64_t count, int encoding, void* out384, uint8_t* status) {
+    REQUIRE_CTX();
+    return proofs_codec(false, proofs128, count, encoding, out384, status);
+}
+int wsnark_groth16_verify_batch_compressed(const void* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proofs128,
+                                           uint64_t count, int encoding, uint8_t* status) {
+    REQUIRE_CTX();
+    return groth16_verify_batch_compressed((const uint8_t*)vk, vk_len, inputs, n_inputs, proofs128, count, encoding, status, false, nullptr);
+}
+int wsnark_groth16_verify_batch_compressed_dev(const void* vk, size_t vk_len, const void* d_inputs, uint64_t n_inputs, const void* d_proofs128,
+                                               uint64_t count, int encoding, uint8_t* status_host, void* stream) {
+    REQUIRE_CTX();
+    return groth16_verify_batch_compressed((const uint8_t*)vk, vk_len, d_inputs, n_inputs, d_proofs128, count, encoding, status_host, true,
+                                           (hipStream_t)stream);
+}
 int wsnark_last_blinding(void* r32, void* s32) {
     return last_blinding((uint8_t*)r32, (uint8_t*)s32) ? WSNARK_OK : WSNARK_ERR_ARG;
 }

@@ -129,11 +129,70 @@ Fe mont_mul32(Fe a, Fe b) {
 }
 #endif
 
+// ---- square roots for a modulus p = 3 (mod 4): Fq (p mod 8 = 7).  Not Fr: p = 1 (mod 4) there, and Tonelli-Shanks over a field of
+// 2-adicity 28 has no user.  Replaces the reference's f1m_sqrt / f1m_isSquare (src/build_f1m.js:809-897) for Fq. ----
+#ifndef WS_SQRT_WINDOW
+#define WS_SQRT_WINDOW 4      // bits per window of the chain below
+#endif
+// a^((p-3)/4) by fixed windows over a per-lane table of the powers a^1 .. a^(2^W - 1): the exponent (p >> 2, 252 bits) is a
+// compile-time constant with the same bits on every lane, so the loop over its windows never diverges, and every table index is a
+// constant (the table stays in registers).  W = 4: 14 products for the table, then 248 squarings and one product per non-zero window
+// below the top one (56 of 62) -- 318 products, against about 380 for the bit-by-bit ladder of inv().
+// With w = a^((p-3)/4):  a w is the candidate root a^((p+1)/4);  a w^2 = a^((p-1)/2) = +-1 is the quadratic character, so for a != 0
+// the inverse of the candidate is +-w and no root ever needs an inversion of its own (fp2.h: sqrt).
+template <class F, class P>
+WS_HD typename F::El ws_pow_pm3_4(const typename F::El& a) {
+    static_assert((P::P0 & 3) == 3, "the chain's exponent is (p - 3) / 4: p = 3 (mod 4) only");
+    typedef typename F::El El;
+    constexpr int W = WS_SQRT_WINDOW, N = 1 << W;
+    static_assert(W >= 2 && W <= 4, "window of 2, 3 or 4 bits");
+    constexpr int kBits = 252, kWindows = (kBits + W - 1) / W;
+    const uint64_t e[4] = {(P::P0 >> 2) | (P::P1 << 62), (P::P1 >> 2) | (P::P2 << 62), (P::P2 >> 2) | (P::P3 << 62), P::P3 >> 2};
+    El t[N];
+    t[1] = a;
+#pragma unroll
+    for (int k = 2; k < N; k++) t[k] = (k & 1) ? F::mul(t[k - 1], a) : F::sqr(t[k / 2]);
+    El acc = F::one();
+#pragma unroll 1
+    for (int j = kWindows - 1; j >= 0; j--) {
+        const int o = j * W;
+        uint32_t d = (uint32_t)(e[o >> 6] >> (o & 63));
+        if ((o & 63) + W > 64 && (o >> 6) < 3) d |= (uint32_t)(e[(o >> 6) + 1] << (64 - (o & 63)));
+        d &= (uint32_t)(N - 1);
+        if (j != kWindows - 1) {
+#pragma unroll
+            for (int k = 0; k < W; k++) acc = F::sqr(acc);
+        }
+        if (d == 0) continue;
+        El m = t[1];
+        switch (d) {      // (a branch on a value every lane shares: the index of each table read is a constant)
+#define WS_SQRT_CASE(k) case k: m = t[(k) < N ? (k) : 1]; break;
+            WS_SQRT_CASE(2) WS_SQRT_CASE(3) WS_SQRT_CASE(4) WS_SQRT_CASE(5) WS_SQRT_CASE(6) WS_SQRT_CASE(7) WS_SQRT_CASE(8)
+            WS_SQRT_CASE(9) WS_SQRT_CASE(10) WS_SQRT_CASE(11) WS_SQRT_CASE(12) WS_SQRT_CASE(13) WS_SQRT_CASE(14) WS_SQRT_CASE(15)
+#undef WS_SQRT_CASE
+            default: break;
+        }
+        acc = (j == kWindows - 1) ? m : F::mul(acc, m);
+    }
+    return acc;
+}
+// plain value v (canonical, NOT Montgomery) > (p - 1) / 2: the "larger" of the two roots v, p - v
+template <class P>
+WS_HD bool ws_gt_half(const Fe& v) {
+    const uint64_t h[4] = {(P::P0 >> 1) | (P::P1 << 63), (P::P1 >> 1) | (P::P2 << 63), (P::P2 >> 1) | (P::P3 << 63), P::P3 >> 1};   // (p - 1) / 2
+    for (int i = 3; i >= 0; i--) {
+        if (v.l[i] > h[i]) return true;
+        if (v.l[i] < h[i]) return false;
+    }
+    return false;
+}
+
 template <class P>
 struct Field {
     typedef Fe El;
     typedef Fe Packed;                             // global-memory form == register form here
     static constexpr bool kInternalDomain = false;
+    static constexpr bool kHasSqrt = (P::P0 & 3) == 3;      // sqrt / is_square below: p = 3 (mod 4), Fq
     WS_HD static Fe unpack(const Fe& x) { return x; }
     WS_HD static Fe pack(const Fe& x) { return x; }
     WS_HD static Fe to_internal(const Fe& x) { return x; }
@@ -283,6 +342,30 @@ struct Field {
         }
         return acc;
     }
+    // ---- square roots (p = 3 mod 4 only: Fq; ws_pow_pm3_4 above has the chain) ----
+    WS_HD static Fe pow_pm3_4(const Fe& a) { return ws_pow_pm3_4<Field<P>, P>(a); }
+    // *root = a^((p+1)/4); true iff a is a square (0 included: sqrt(0) = 0), and then *root squared is a.  Which of the two roots
+    // comes out is the chain's business: callers pick by parity (the reference, build_f1m.js:871-875) or by is_larger
+    WS_HD static bool sqrt(const Fe& a, Fe* root) {
+        *root = mul(pow_pm3_4(a), a);
+        return eq(sqr(*root), a);
+    }
+    WS_HD static bool is_square(const Fe& a) { Fe r; return sqrt(a, &r); }
+    // the plain (non-Montgomery) canonical value, and whether it is > (p - 1) / 2
+    WS_HD static Fe plain(const Fe& a) { return from_mont(a); }
+    WS_HD static bool is_larger(const Fe& a) { return ws_gt_half<P>(plain(a)); }
+    // a / 2: (a + p) / 2 for an odd representative
+    WS_HD static Fe halve(const Fe& a) {
+        const uint64_t m = (uint64_t)0 - (a.l[0] & 1);
+        uint64_t c = 0;
+        Fe t;
+        t.l[0] = ws_addc(a.l[0], P::P0 & m, c, &c);
+        t.l[1] = ws_addc(a.l[1], P::P1 & m, c, &c);
+        t.l[2] = ws_addc(a.l[2], P::P2 & m, c, &c);
+        t.l[3] = ws_addc(a.l[3], P::P3 & m, c, &c);      // (p < 2^254: no carry out)
+        return Fe{{(t.l[0] >> 1) | (t.l[1] << 63), (t.l[1] >> 1) | (t.l[2] << 63), (t.l[2] >> 1) | (t.l[3] << 63), t.l[3] >> 1}};
+    }
+
     // reduce an arbitrary 256-bit integer mod p (plain domain): 2^256 / p < 6
     WS_HD static Fe reduce_full(const Fe& a) {
         Fe t = a;

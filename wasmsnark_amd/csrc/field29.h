@@ -83,6 +83,7 @@ struct Field29 {
     typedef Fe Packed;
     static constexpr bool kInternalDomain = true;
     static constexpr bool kHasMul2Add = true;
+    static constexpr bool kHasSqrt = (P::P0 & 3) == 3;      // sqrt / is_square below: p = 3 (mod 4), Fq
 
     // ---- constants as compile-time limbs ----
     WS_HD static constexpr uint32_t p_limb(int i) { return ws_limb29(P::P0, P::P1, P::P2, P::P3, i); }
@@ -520,6 +521,35 @@ struct Field29 {
             base = sqr(base);
         }
         return acc;
+    }
+    // ---- square roots (p = 3 mod 4 only: Fq; field.h: ws_pow_pm3_4 has the chain and what its value gives) ----
+    WS_HD static F29 pow_pm3_4(const F29& a) { return ws_pow_pm3_4<Field29<P>, P>(a); }
+    // *root = a^((p+1)/4), strict; true iff a is a square (0 included), and then *root squared is a
+    WS_HD static bool sqrt(const F29& a, F29* root) {
+        *root = mul(pow_pm3_4(a), a);
+        return eq(sqr(*root), a);
+    }
+    WS_HD static bool is_square(const F29& a) { F29 r; return sqrt(a, &r); }
+    // the plain canonical value of an internal-domain element (a * 1 * 2^-261), packed; whether it is > (p - 1) / 2
+    WS_HD static Fe plain(const F29& a) { return pack(canonical(mul(a, from_words(1, 0, 0, 0)))); }
+    WS_HD static bool is_larger(const F29& a) { return ws_gt_half<P>(plain(a)); }
+    // a / 2 for a in [0, 2p): (a + p) / 2 for an odd representative; tight limbs, result < 1.5p
+    WS_HD static F29 halve(const F29& a) {
+        const uint32_t m = 0u - (a.v[0] & 1);
+        F29 s;
+        uint32_t c = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const uint32_t t = a.v[i] + (p_limb(i) & m) + c;
+            s.v[i] = t & WS_M29;
+            c = t >> 29;
+        }
+        s.v[8] = a.v[8] + (p_limb(8) & m) + c;
+        F29 r;
+#pragma unroll
+        for (int i = 0; i < 8; i++) r.v[i] = (s.v[i] >> 1) | ((s.v[i + 1] & 1) << 28);
+        r.v[8] = s.v[8] >> 1;
+        return r;
     }
     // canonical representative in [0, p) of a value in [0, 2p)
     WS_HD static F29 canonical(const F29& a) {

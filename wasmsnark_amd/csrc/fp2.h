@@ -122,6 +122,36 @@ struct Fp2T {
         return El{B::mul(a.c0, t), B::neg(B::mul(a.c1, t))};
     }
     WS_HD static El from_mont(const El& a) { return El{B::from_mont(a.c0), B::from_mont(a.c1)}; }
+    // Square root by the complex method (q = 3 mod 4), at most TWO exponentiations on any lane and no inversion.  With
+    // pw(x) = x^((q-3)/4) (field.h: ws_pow_pm3_4): x pw(x) is the candidate root of x and, for x != 0, 1 / (x pw(x)) = +-pw(x).
+    //   c1 == 0:  r = c0 pw(c0); the root is (r, 0) if r^2 = c0, else r^2 = -c0 and the root is (0, r).  Always a square.
+    //   else      s = sqrt(c0^2 + c1^2) (not a square: a is none);  t = (c0 + s) / 2 (never 0: that needs c1 = 0);  w = pw(t),
+    //             x0 = t w,  h = c1 w / 2.  x0^2 = t:  1 / x0 = w and the root is (x0, h).  Otherwise x0^2 = -t, 1 / x0 = -w, and because
+    //             ((c0 + s) / 2)((c0 - s) / 2) = -c1^2 / 4 the root of (c0 - s) / 2 is c1 / (2 x0) = -h: the root is (-h, x0).
+    // The first exponentiation is shared by both cases (its operand is c0 or the norm), so lanes that differ still run one chain each.
+    // true iff a is a square; *root is then one of the two roots (callers pick by is_larger).
+    WS_HD static bool sqrt(const El& a, El* root) {
+        const bool real = B::is_zero(a.c1);
+        const BE n = real ? a.c0 : B::add(B::sqr(a.c0), B::sqr(a.c1));
+        const BE s = B::mul(B::pow_pm3_4(n), n);
+        const bool sq = B::eq(B::sqr(s), n);
+        if (real) {
+            *root = sq ? El{s, B::zero()} : El{B::zero(), s};
+            return true;
+        }
+        if (!sq) { *root = zero(); return false; }
+        const BE t = B::halve(B::add(a.c0, s));
+        const BE w = B::pow_pm3_4(t);
+        const BE x0 = B::mul(w, t), h = B::halve(B::mul(w, a.c1));
+        *root = B::eq(B::sqr(x0), t) ? El{x0, h} : El{B::neg(h), x0};
+        return true;
+    }
+    WS_HD static bool is_square(const El& a) {      // the norm decides (c1 == 0: always)
+        if (B::is_zero(a.c1)) return true;
+        return B::is_square(B::add(B::sqr(a.c0), B::sqr(a.c1)));
+    }
+    // the "larger" of the two roots y, -y: decided on c1 if c1 != 0, else on c0 (y > -y with c1 compared before c0)
+    WS_HD static bool is_larger(const El& a) { return B::is_zero(a.c1) ? B::is_larger(a.c0) : B::is_larger(a.c1); }
 };
 
 typedef Fp2T<Fq> Fq2;

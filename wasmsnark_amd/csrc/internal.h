@@ -306,6 +306,12 @@ int pairing_consts(const PairConsts** out);
 // host (staged through the ring) or on the device
 int groth16_verify_batch(const uint8_t* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proofs384, uint64_t count,
                          uint8_t* status_host, bool on_device, hipStream_t s);
+// compressed points and proofs (pointcodec.hip; include/wsnark.h has the encodings and every status): arrays of points either way
+// through the staging ring (g = 1 / 2), proofs 384 <-> 128 bytes, and the batch verifier on proofs it decompresses on the device
+int points_codec(int g, bool compress, const void* in, uint64_t n, int enc, uint32_t flags, void* out, uint8_t* status, uint64_t* n_bad);
+int proofs_codec(bool compress, const void* in, uint64_t count, int enc, void* out, uint8_t* status);
+int groth16_verify_batch_compressed(const uint8_t* vk, size_t vk_len, const void* inputs, uint64_t n_inputs, const void* proofs128, uint64_t count,
+                                    int enc, uint8_t* status_host, bool on_device, hipStream_t stream);
 
 // ---- CALC_H pieces (calch.hip) ----
 struct CsrMatrix {            // row-major transpose of the reference's column-major pols blob

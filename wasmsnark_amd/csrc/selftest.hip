@@ -62,6 +62,17 @@ __host__ __device__ inline Fe st_base_op(int op, const Fe& ap, const Fe& bp, con
         if (op == WSNARK_ST_NEG_WEAK_MUL) return F::from_internal(F::mul(F::neg(a), b));
         if (op == WSNARK_ST_MUL2ADD) return F::from_internal(F::add(F::mul(a, a), F::mul(b, b)));
     }
+    // square roots, Fq only (Fr: not defined).  The root handed out is the reference's: the one whose PLAIN value is even
+    // (src/build_f1m.js:871-875); every byte 0xFF for a non-square
+    if constexpr (F::kHasSqrt) {
+        if (op == WSNARK_ST_SQRT) {
+            El r;
+            if (!F::sqrt(a, &r)) return Fe{{~0ull, ~0ull, ~0ull, ~0ull}};
+            if (F::plain(r).l[0] & 1) r = F::neg(r);
+            return F::from_internal(r);
+        }
+        if (op == WSNARK_ST_IS_SQUARE) return st_flag<Fe>(F::is_square(a));
+    }
     *ok = false;
     return ap;
 }
@@ -86,6 +97,16 @@ __host__ __device__ inline typename F2::Packed st_ext_op(int op, const typename 
         case WSNARK_ST_MULSUB2_WEAK_B: return F2::from_internal(F2::mulsub2(a, F2::sub_weak(a, b), b, a));
         case WSNARK_ST_EQ: return st_flag<Pk>(F2::is_zero(F2::sub(a, b)));
         case WSNARK_ST_EQ_WEAK: return st_flag<Pk>(F2::is_zero_weak(F2::sub_weak(a, b)));
+        case WSNARK_ST_SQRT: {      // the not-larger root; every byte 0xFF for a non-square
+            El r;
+            Pk none;
+            uint64_t* w = reinterpret_cast<uint64_t*>(&none);
+            for (size_t i = 0; i < sizeof(Pk) / 8; i++) w[i] = ~0ull;
+            if (!F2::sqrt(a, &r)) return none;
+            if (F2::is_larger(r)) r = F2::neg(r);
+            return F2::from_internal(r);
+        }
+        case WSNARK_ST_IS_SQUARE: return st_flag<Pk>(F2::is_square(a));
         default: break;
     }
     *ok = false;

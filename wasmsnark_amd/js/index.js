@@ -786,6 +786,56 @@ class Bn128 {
         keep.forEach((i, k) => { out[i] = st[k] === 1; });
         return out;
     }
+    /* Compressed points and 128-byte proofs (csrc/pointcodec.hip; include/wsnark.h has both encodings byte by byte).  encoding: "le"
+     * (ark-serialize's compressed mode) or "be" (gnark-crypto's marshal).  Each resolves to {data: ArrayBuffer, status: number[]}:
+     * compressPoints(g, points)        affine Montgomery points (64 g bytes) -> 32 g bytes each; status 0 ok, 1 a coordinate >= q
+     * decompressPoints(g, data)        -> points; status 0 ok, 1 malformed, 2 no point, 3 outside the subgroup (g = 2 with subgroup)
+     * compressProofs(proofs)           [{pi_a, pi_b, pi_c}] -> 128 bytes each (A | B | C); status 1 written, 2 malformed
+     * decompressProofs(data)           -> {proofs: [{pi_a, pi_b, pi_c} | null], status}: 1 written, 2 malformed, 0 no point / infinity */
+    async compressPoints(g, points, encoding) { return codecSplit(await addon.codecPoints(g, true, points, encodingId(encoding), 0), 32 * g); }
+    async decompressPoints(g, data, encoding, subgroup) {
+        return codecSplit(await addon.codecPoints(g, false, data, encodingId(encoding), subgroup ? 1 : 0), 64 * g);
+    }
+    async compressProofs(proofs, encoding) {
+        if (!Array.isArray(proofs)) throw new TypeError("expected an array of proofs");
+        if (proofs.length === 0) return { data: new ArrayBuffer(0), status: [] };
+        const pf = le32cat([].concat(...proofs.map((p) => [].concat(p.pi_a, p.pi_b[0], p.pi_b[1], p.pi_b[2], p.pi_c))));
+        return codecSplit(await addon.codecProofs(true, pf, encodingId(encoding)), 128);
+    }
+    async decompressProofs(data, encoding) {
+        if (data.byteLength === 0) return { proofs: [], status: [] };
+        const r = codecSplit(await addon.codecProofs(false, data, encodingId(encoding)), 384);
+        const w = new Uint8Array(r.data);
+        const num = (i, k) => { let v = 0n; for (let b = 31; b >= 0; b--) v = (v << 8n) | BigInt(w[384 * i + 32 * k + b]); return v.toString(); };
+        const proofs = r.status.map((st, i) => st !== 1 ? null : {
+            pi_a: [num(i, 0), num(i, 1), num(i, 2)], pi_b: [[num(i, 3), num(i, 4)], [num(i, 5), num(i, 6)], [num(i, 7), num(i, 8)]],
+            pi_c: [num(i, 9), num(i, 10), num(i, 11)] });
+        return { proofs, status: r.status };
+    }
+    /* groth16VerifyBatch on 128-byte proofs (one buffer of count x 128 bytes): decompressed on the GPU and verified there.  Resolves to
+     * boolean[], or with returnStatus to the raw statuses (1 valid, 0 invalid, 2 malformed). */
+    async groth16VerifyBatchCompressed(verificationKey, inputs, proofBytes, encoding, returnStatus) {
+        const enc = encodingId(encoding), count = proofBytes.byteLength / 128;
+        if (!Array.isArray(inputs) || !Number.isInteger(count) || inputs.length !== count) throw new TypeError("expected one input array per 128-byte proof");
+        if (count === 0) return [];
+        const rows = inputs.map((x) => (x === undefined || x === null ? [] : Array.isArray(x) ? x : [x]).map((v) => BigInt(v)));
+        const nIn = rows[0].length;
+        if (rows.some((r) => r.length !== nIn)) throw new TypeError("all proofs of a batch share the key: every input array must have " + nIn + " entries");
+        const IC = verificationKey.IC;
+        if (!IC || IC.length < nIn + 1) throw new Error("verification key has fewer IC points than inputs + 1");
+        const g1 = (p) => [p[0], p[1]], g2 = (p) => [p[0][0], p[0][1], p[1][0], p[1][1]];
+        const vk = le32cat([].concat(g1(verificationKey.vk_alfa_1), g2(verificationKey.vk_beta_2), g2(verificationKey.vk_gamma_2),
+            g2(verificationKey.vk_delta_2), ...IC.slice(0, nIn + 1).map(g1)));
+        const keep = rows.map((r, i) => i).filter((i) => !rows[i].some((v) => v < 0n || v >= (1n << 256n)));
+        const status = new Array(count).fill(0);
+        if (keep.length) {
+            const all = new Uint8Array(proofBytes.buffer || proofBytes, proofBytes.byteOffset || 0, proofBytes.byteLength), pf = new Uint8Array(128 * keep.length);
+            keep.forEach((i, k) => pf.set(all.subarray(128 * i, 128 * i + 128), 128 * k));
+            const st = new Uint8Array(await addon.verifyBatchCompressed(vk, le32cat([].concat(...keep.map((i) => rows[i]))), pf, nIn, enc));
+            keep.forEach((i, k) => { status[i] = st[k]; });
+        }
+        return returnStatus ? status : status.map((v) => v === 1);
+    }
     /* src/bn128.js:562-566.  The GPU context is process-wide (one per addon): it is shut down when the LAST live Bn128
      * object terminates, so one object's terminate() does not pull the device out from under another's proofs. */
     terminate() {
@@ -797,6 +847,15 @@ class Bn128 {
     }
 }
 let liveInstances = 0;
+function encodingId(name) {         // WSNARK_ENC_LE, WSNARK_ENC_BE
+    if (name === "le") return 1;
+    if (name === "be") return 2;
+    throw new TypeError('encoding must be "le" or "be"');
+}
+function codecSplit(buf, recordBytes) {      // the addon's `records | one status byte each`
+    const n = buf.byteLength / (recordBytes + 1);
+    return { data: buf.slice(0, n * recordBytes), status: Array.from(new Uint8Array(buf, n * recordBytes, n)) };
+}
 function le32cat(list) {            // decimal strings / BigInts -> concatenated 32-byte little-endian integers
     const out = new Uint8Array(32 * list.length);
     list.forEach((x, k) => { let v = BigInt(x); for (let i = 0; i < 32; i++) { out[32 * k + i] = Number(v & 0xffn); v >>= 8n; } });

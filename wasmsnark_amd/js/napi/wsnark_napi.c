@@ -102,6 +102,14 @@ static struct {
     int (*circuit_from_rows_size)(const void*, uint32_t, uint32_t*, uint64_t*);
     int (*circuit_from_rows)(const void*, uint32_t, void*, uint64_t, void*, uint64_t, void*, uint64_t, uint32_t*, void*);
     int (*circuit_load_rows)(const void*, uint32_t, wsnark_circuit_res_t**);
+    /* compressed points and 128-byte proofs (include/wsnark.h: wsnark_g{1,2}_compress / _decompress, wsnark_proof_*, ..._batch_compressed) */
+    int (*g1_compress)(const void*, uint64_t, int, void*, uint8_t*, uint64_t*);
+    int (*g2_compress)(const void*, uint64_t, int, void*, uint8_t*, uint64_t*);
+    int (*g1_decompress)(const void*, uint64_t, int, uint32_t, void*, uint8_t*, uint64_t*);
+    int (*g2_decompress)(const void*, uint64_t, int, uint32_t, void*, uint8_t*, uint64_t*);
+    int (*proof_compress)(const void*, uint64_t, int, void*, uint8_t*);
+    int (*proof_decompress)(const void*, uint64_t, int, void*, uint8_t*);
+    int (*verify_batch_compressed)(const void*, size_t, const void*, uint64_t, const void*, uint64_t, int, uint8_t*);
     char dir[4096];
 } L;
 
@@ -153,6 +161,9 @@ static int load_lib(char* err, size_t errlen) {
     SYM(circuit_witness_check_batch, "wsnark_circuit_witness_check_batch")
     SYM(circuit_from_rows_size, "wsnark_circuit_from_rows_size") SYM(circuit_from_rows, "wsnark_circuit_from_rows")
     SYM(circuit_load_rows, "wsnark_circuit_load_rows")
+    SYM(g1_compress, "wsnark_g1_compress") SYM(g2_compress, "wsnark_g2_compress") SYM(g1_decompress, "wsnark_g1_decompress")
+    SYM(g2_decompress, "wsnark_g2_decompress") SYM(proof_compress, "wsnark_proof_compress") SYM(proof_decompress, "wsnark_proof_decompress")
+    SYM(verify_batch_compressed, "wsnark_groth16_verify_batch_compressed")
     SYM(zkey_info, "wsnark_zkey_info") SYM(zkey_import, "wsnark_zkey_import") SYM(zkey_export, "wsnark_zkey_export") SYM(zkey_export_size, "wsnark_zkey_export_size")
 #undef SYM
     return 0;
@@ -183,7 +194,8 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
        OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
        OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
-       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH, OP_CIRCUIT_FROM_ROWS, OP_CIRCUIT_LOAD_ROWS, OP_ZKEY_IMPORT, OP_ZKEY_EXPORT };
+       OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH, OP_CIRCUIT_FROM_ROWS, OP_CIRCUIT_LOAD_ROWS, OP_ZKEY_IMPORT, OP_ZKEY_EXPORT,
+       OP_CODEC_POINTS, OP_CODEC_PROOFS, OP_VERIFY_BATCH_COMPRESSED };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -373,6 +385,21 @@ static void job_execute(napi_env env, void* data) {
     case OP_GROUP_LOADKEY_FILE: j->rc = L.group_pkey_load_file(j->gr->g, j->path, &j->gk->k); break;
     case OP_VERIFY: j->rc = L.verify(j->a, j->na, j->b, j->nb / 32, j->c, &j->i0); break;
     case OP_VERIFY_BATCH: j->rc = L.verify_batch(j->a, j->na, j->nb ? j->b : NULL, j->u0, j->c, j->nc / 384, j->out); break;
+    case OP_VERIFY_BATCH_COMPRESSED:
+        j->rc = L.verify_batch_compressed(j->a, j->na, j->nb ? j->b : NULL, j->u0, j->c, j->nc / 128, (int)j->u1, j->out);
+        break;
+    case OP_CODEC_POINTS: {   /* i0 = g, i1 = 1 compress / 0 decompress, u0 = encoding, u1 = flags; out = the records | a status byte each */
+        const size_t in_sz = (j->i1 ? 64 : 32) * (size_t)j->i0, out_sz = (j->i1 ? 32 : 64) * (size_t)j->i0, n = j->na / in_sz;
+        uint64_t bad = 0;
+        if (j->i1) j->rc = (j->i0 == 1 ? L.g1_compress : L.g2_compress)(j->a, n, (int)j->u0, j->out, j->out + n * out_sz, &bad);
+        else j->rc = (j->i0 == 1 ? L.g1_decompress : L.g2_decompress)(j->a, n, (int)j->u0, j->u1, j->out, j->out + n * out_sz, &bad);
+        break;
+    }
+    case OP_CODEC_PROOFS: {   /* i1 = 1 compress / 0 decompress, u0 = encoding; out = the records | a status byte each */
+        const size_t in_sz = j->i1 ? 384 : 128, out_sz = j->i1 ? 128 : 384, n = j->na / in_sz;
+        j->rc = (j->i1 ? L.proof_compress : L.proof_decompress)(j->a, n, (int)j->u0, j->out, j->out + n * out_sz);
+        break;
+    }
     case OP_CHECK_KEY:
         j->rc = j->path ? L.pkey_check_file(j->path, j->u0, j->r32, j->out) : L.pkey_check(j->a, j->na, j->u0, j->r32, j->out);
         break;
@@ -802,6 +829,62 @@ static napi_value js_prove_batch(napi_env env, napi_callback_info info) {
     j->out = (uint8_t*)calloc(j->nout, 1);
     if (!j->out) FAIL(env, j, "out of memory");
     return start_job(env, j, "wsnark_groth16_prove_batch");
+}
+
+/* codecPoints(g, compress, bytes, encoding, flags) -> Promise<ArrayBuffer>: the n records (compress: 32 g bytes each, else points of
+ * 64 g bytes), then n status bytes (include/wsnark.h: wsnark_g{1,2}_compress / _decompress; on the GPU, needs init()) */
+static napi_value js_codec_points(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5];
+    bool comp = false;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CODEC_POINTS;
+    if (argc < 5 || napi_get_value_int32(env, argv[0], &j->i0) != napi_ok || (j->i0 != 1 && j->i0 != 2) ||
+        napi_get_value_bool(env, argv[1], &comp) != napi_ok || !get_bytes(env, argv[2], &j->a, &j->na) ||
+        napi_get_value_uint32(env, argv[3], &j->u0) != napi_ok || napi_get_value_uint32(env, argv[4], &j->u1) != napi_ok ||
+        j->na == 0 || j->na % ((comp ? 64 : 32) * (size_t)j->i0))
+        FAIL(env, j, "expected (g = 1 | 2, compress, bytes (a whole number of records), encoding, flags)");
+    j->i1 = comp ? 1 : 0;
+    const size_t n = j->na / ((comp ? 64 : 32) * (size_t)j->i0);
+    j->nout = n * (comp ? 32 : 64) * (size_t)j->i0 + n;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_points_codec");
+}
+/* codecProofs(compress, bytes, encoding) -> Promise<ArrayBuffer>: the n records (128 or 384 bytes each), then n status bytes */
+static napi_value js_codec_proofs(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    bool comp = false;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_CODEC_PROOFS;
+    if (argc < 3 || napi_get_value_bool(env, argv[0], &comp) != napi_ok || !get_bytes(env, argv[1], &j->a, &j->na) ||
+        napi_get_value_uint32(env, argv[2], &j->u0) != napi_ok || j->na == 0 || j->na % (comp ? 384 : 128))
+        FAIL(env, j, "expected (compress, bytes (a whole number of proofs), encoding)");
+    j->i1 = comp ? 1 : 0;
+    const size_t n = j->na / (comp ? 384 : 128);
+    j->nout = n * (comp ? 128 : 384) + n;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[1]);
+    return start_job(env, j, "wsnark_proofs_codec");
+}
+/* verifyBatchCompressed(vkBytes, inputBytes (count x nInputs x 32), proofs (count x 128), nInputs, encoding) -> Promise<ArrayBuffer count> */
+static napi_value js_verify_batch_compressed(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_VERIFY_BATCH_COMPRESSED;
+    if (argc < 5 || !get_bytes(env, argv[0], &j->a, &j->na) || !get_bytes(env, argv[1], &j->b, &j->nb) ||
+        !get_bytes(env, argv[2], &j->c, &j->nc) || napi_get_value_uint32(env, argv[3], &j->u0) != napi_ok ||
+        napi_get_value_uint32(env, argv[4], &j->u1) != napi_ok || j->nc == 0 || j->nc % 128 || j->nb != (j->nc / 128) * (size_t)j->u0 * 32)
+        FAIL(env, j, "expected (vkBytes, inputBytes (count x nInputs x 32), proofs (count x 128), nInputs, encoding)");
+    j->nout = j->nc / 128;
+    j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[0]); keep(env, j, argv[1]); keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_groth16_verify_batch_compressed");
 }
 
 /* verify(vkBytes, inputBytes, proof384) -> Promise<boolean>   (layouts: include/wsnark.h, wsnark_groth16_verify) */
@@ -1546,6 +1629,9 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"waitTables", NULL, js_wait_tables, NULL, NULL, NULL, napi_default, NULL},
         {"verify", NULL, js_verify, NULL, NULL, NULL, napi_default, NULL},
         {"verifyBatch", NULL, js_verify_batch, NULL, NULL, NULL, napi_default, NULL},
+        {"codecPoints", NULL, js_codec_points, NULL, NULL, NULL, napi_default, NULL},
+        {"codecProofs", NULL, js_codec_proofs, NULL, NULL, NULL, napi_default, NULL},
+        {"verifyBatchCompressed", NULL, js_verify_batch_compressed, NULL, NULL, NULL, napi_default, NULL},
         {"proveBatch", NULL, js_prove_batch, NULL, NULL, NULL, napi_default, NULL},
         {"checkKey", NULL, js_check_key, NULL, NULL, NULL, napi_default, NULL},
         {"contributeKey", NULL, js_contribute_key, NULL, NULL, NULL, napi_default, NULL},
