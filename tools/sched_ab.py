@@ -2,7 +2,8 @@
 """Round 5: wavefront priorities x queue orders on whole 2^20 proofs, A/B in ONE process (wsnark_tuning_set).
    python tools/sched_ab.py [rounds] ["NAME=v,NAME2=v;NAME=v;..."]   (a combo list; default: the priority / order matrix)
 Each combo: 3 warm-up + 20 timed proofs, resident witness, proofs checked against the closed form; the list is run `rounds`
-times in alternation so that box drift shows."""
+times in alternation so that box drift shows.  LOGD=22 in the environment: another size.
+   python tools/sched_ab.py 6 "PROVE_TAIL_SIDE=0;PROVE_TAIL_SIDE=1"   -> profiles/tail_beside_acc_ab.txt"""
 import json, os, sys, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch, wasmsnark_amd

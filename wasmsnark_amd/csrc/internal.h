@@ -86,7 +86,7 @@ struct Lane {
     DevBuf batch_ws;                            // batch proving (provebatch.hip): index lists, partial sums, window sums of a chunk (grow-only)
     DevBuf verify_ws;                           // batch verification (pairing.hip): key tables, per-proof points, Miller values (grow-only)
     hipEvent_t ev_start = nullptr, ev_tail = nullptr, ev_h = nullptr;   // cross-queue ordering of one proof
-    hipEvent_t ev_plan = nullptr, ev_g2 = nullptr;                      // ... witness plan ready / G2 sum enqueued (third queue)
+    hipEvent_t ev_plan = nullptr, ev_g2 = nullptr;                      // ... witness plan ready / G2 sum enqueued (third queue); ev_tail: the tail levels given to the third queue
 };
 static const int kMaxLanes = 4;
 
@@ -266,10 +266,15 @@ int msm_points_mask(const Affine<Fq>* d_g1, const Affine<Fq2>* d_g2, uint64_t n,
 // asynchronous form: launch enqueues the kernels and the copy of the window sums, finish waits
 // for that copy and runs the serial host tail.  `prepared` = the point array was converted in place by
 // msm_prepare_points (resident keys).
-int msm_g1_launch(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot, hipStream_t s);
-int msm_g2_launch(Lane& L, const Affine<Fq2>* d_points, bool prepared, int* slot, hipStream_t s);
+// s_levels: the queue of the reduction tail's latency levels (msm_chunks2, msm_tree, msm_rows, the copy of the rows, the completion
+// event).  `s` itself: everything on one queue; another queue: it is ordered behind msm_chunks and `s` goes on without the levels;
+// null: WSNARK_PROVE_TAIL_SIDE decides (1: the lane's third queue, else `s`).
+int msm_g1_launch(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot, hipStream_t s, hipStream_t s_levels = nullptr);
+int msm_g2_launch(Lane& L, const Affine<Fq2>* d_points, bool prepared, int* slot, hipStream_t s, hipStream_t s_levels = nullptr);
 // plan_ids (optional): the plan each set is accumulated against (variants of one plan: same geometry)
-int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, bool prepared, int* slots, hipStream_t s, const int* plan_ids = nullptr);
+int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, bool prepared, int* slots, hipStream_t s, const int* plan_ids = nullptr,
+                        hipStream_t s_levels = nullptr);
+long msm_tail_side_switch();      // WSNARK_PROVE_TAIL_SIDE (0 off, 1 wherever a third queue exists, default 2: the prover's full-size arrangement)
 // Two sums of which only the TOTAL is wanted (the prover's C and H) under one reduction tail: each is accumulated into its buckets
 // by msm_g1_launch_acc_only (no tail), then msm_g1_launch_tail_merged reduces the bucket-wise sum of the two on `s`, which the caller
 // has ordered behind both accumulations.  The total is collected from slot_a; slot_b is released with it and never finished.  Plans

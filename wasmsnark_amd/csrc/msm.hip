@@ -1156,12 +1156,14 @@ struct MsmPending {
     void* h_sums = nullptr;
     size_t h_bytes = 0;
     hipEvent_t ev = nullptr;
-    const void* d_points_used = nullptr;            // the (converted) point array the accumulation reads
+    hipEvent_t ev_chunks = nullptr;               // msm_chunks has ended on the sum's queue: what a side queue with the tail's levels waits for
+    const void* d_points_used = nullptr;           // the (converted) point array the accumulation reads
     int partner = -1;             // a launch whose buckets went through THIS launch's tail (msm_g1_launch_tail_merged): busy until this one is finished
     void release() {
         if (h_sums) (void)hipHostFree(h_sums);
         if (ev) (void)hipEventDestroy(ev);
-        h_sums = nullptr; ev = nullptr; h_bytes = 0; active = false;
+        if (ev_chunks) (void)hipEventDestroy(ev_chunks);
+        h_sums = nullptr; ev = ev_chunks = nullptr; h_bytes = 0; active = false;
         d_sums.release(); d_rows.release();
         S.buckets.release(); S.partials.release(); S.chunkS.release(); S.chunkA.release(); S.points_conv.release(); S.hot_sums.release();
         S.hot_done.release(); S.tree_half.release(); S.tree_done.release();
@@ -1200,6 +1202,7 @@ void msm_select_plan(Lane& L, int id) { ws(L).cur = (id >= 0 && id < kPlans) ? i
 void msm_abort_slots(Lane& L, const int* slots, int nslots, hipStream_t a, hipStream_t b) {
     if (a) (void)hipStreamSynchronize(a);
     if (b && b != a) (void)hipStreamSynchronize(b);
+    if (L.stream3 && L.stream3 != a && L.stream3 != b) (void)hipStreamSynchronize(L.stream3);      // (the side queue may hold the slots' tail levels)
     if (!L.msm) return;
     for (int k = 0; k < nslots; k++)
         if (slots[k] >= 0 && slots[k] < kPendingSlots) L.msm->slot[slots[k]].active = false;
@@ -1733,7 +1736,8 @@ static int msm_launch_acc(Lane& L, int which, const typename H::Aff* d_points_re
 
     MsmScratch& S = P.S;                        // this launch's accumulation buffers (the plan's own are read by the kernels)
     // Everything runs in order on the caller's stream.  Tried and measured slower on MI355X (rounds 1, 3, 5): accumulations on
-    // concurrent streams (cache thrash), and the reduction tail on another (or a high-priority) stream: docs/HISTORY.md, DESIGN.md section 5.
+    // concurrent streams (cache thrash), and the WHOLE reduction tail on another (or a high-priority) stream: docs/HISTORY.md, DESIGN.md
+    // section 5.  (Its latency levels alone on another stream do pay: msm_launch_tail.)
     WS_HIP_CHECK(S.buckets.reserve((size_t)nbuckets * sizeof(Pt)));
     WS_HIP_CHECK(S.partials.reserve((size_t)I.hot_cap * sizeof(Pt)));
     // (level-1 chunk pairs first; with a second chunk level its W * J pairs follow them in the same buffers)
@@ -1799,17 +1803,11 @@ template <class C> static bool tail_split() { return sizeof(typename C::AffP) > 
 // one there), C: the curve of msm_tree / msm_rows (latency-bound LDS reductions: the lane-paired forms halve every step).  Same buffers.
 // second_slot >= 0 (one launch only): that launch's buckets are added to the first one's bucket by bucket in msm_chunks, and the rows
 // that reach the host -- in the first launch's slot -- are those of the sum of the two (same geometry: the caller has checked)
-template <class C, class CC = C>
-static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t s, int second_slot = -1) {
-    typedef PointIO<C> IO;
-    typedef typename IO::Stored St;
-    static_assert(sizeof(typename PointIO<CC>::Stored) == sizeof(St), "the chunk and tree kernels share their buffers");
-    Context* X = ctx();
-    if (!s) s = L.stream;
+template <class C>
+static void tail_sets(Lane& L, const int* slot_ids, int nslots, int second_slot, TailSets<C>& ts) {
+    typedef typename PointIO<C>::Stored St;
     MsmPending* slots = ws(L).slot;
     const MsmPlanInfo& I = slots[slot_ids[0]].info;
-    if (I.n == 0) return WS_OK;
-    TailSets<C> ts;
     for (int k = 0; k < 4; k++) {
         MsmPending& P = slots[slot_ids[k < nslots ? k : 0]];
         ts.buckets[k] = P.S.buckets.template as<St>();
@@ -1832,7 +1830,20 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
             ts.bend2[k] = ws(L).plan[P2.plan_id].S.bend.template as<uint32_t>();
         }
     }
-    const uint32_t J = I.J, logJ = I.logJ, nsum = I.nsum, LPP = IO::LPP, W = I.tW;
+}
+// The tail in two halves, so that a caller may give them different queues (prove.hip: the side queue).  msm_launch_tail_chunks:
+// msm_chunks alone -- throughput-bound, 2 additions per bucket on every lane of the chip; it stays on the queue of the sum's accumulation.
+template <class C, class CC = C>
+static int msm_launch_tail_chunks(Lane& L, const int* slot_ids, int nslots, hipStream_t s, int second_slot = -1) {
+    typedef typename PointIO<C>::Stored St;
+    static_assert(sizeof(typename PointIO<CC>::Stored) == sizeof(St), "the chunk and tree kernels share their buffers");
+    Context* X = ctx();
+    if (!s) s = L.stream;
+    const MsmPlanInfo& I = ws(L).slot[slot_ids[0]].info;
+    if (I.n == 0) return WS_OK;
+    TailSets<C> ts;
+    tail_sets<C>(L, slot_ids, nslots, second_slot, ts);
+    const uint32_t W = I.tW;
     KernelTimer& T = X->timer;
     T.begin("msm_chunks", s);
     {
@@ -1846,6 +1857,24 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
     }
     T.end(s);
     WS_HIP_CHECK(hipGetLastError());
+    return WS_OK;
+}
+// msm_launch_tail_levels: the latency levels behind msm_chunks -- msm_chunks2, msm_tree, msm_rows (chains of dependent additions on a
+// few hundred workgroups) --, the copy of the rows to the host and the completion event(s), all on `s`, which the caller has ordered
+// behind the chunk sums.
+template <class C>
+static int msm_launch_tail_levels(Lane& L, const int* slot_ids, int nslots, hipStream_t s, int second_slot = -1) {
+    typedef PointIO<C> IO;
+    typedef typename IO::Stored St;
+    Context* X = ctx();
+    if (!s) s = L.stream;
+    MsmPending* slots = ws(L).slot;
+    const MsmPlanInfo& I = slots[slot_ids[0]].info;
+    if (I.n == 0) return WS_OK;
+    TailSets<C> ts;
+    tail_sets<C>(L, slot_ids, nslots, second_slot, ts);
+    const uint32_t J = I.J, logJ = I.logJ, nsum = I.nsum, LPP = IO::LPP, W = I.tW;
+    KernelTimer& T = X->timer;
     if (I.m2 > 1) {
         T.begin("msm_chunks2", s);
         hipLaunchKernelGGL(msm_chunks2<C>, dim3(ceil_div_u64((uint64_t)2 * W * J * LPP, 256), nslots), dim3(256), 0, s, ts, W * J, I.m2);
@@ -1886,24 +1915,52 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
     if (second_slot >= 0) WS_HIP_CHECK(hipEventRecord(slots[second_slot].ev, s));
     return WS_OK;
 }
+// WSNARK_PROVE_TAIL_SIDE: 0 = no side queue anywhere, 1 = wherever the lane has a third queue (stand-alone sums too), default (2):
+// the prover's full-size arrangement only (prove.hip)
+long msm_tail_side_switch() { return tuning_get("PROVE_TAIL_SIDE", 2); }
+// the queue a sum on `s` sends its latency levels to when its caller names none: the lane's third queue under switch 1, else `s` itself
+static hipStream_t tail_levels_queue(Lane& L, hipStream_t s, hipStream_t s_levels) {
+    if (s_levels) return s_levels;
+    return (msm_tail_side_switch() == 1 && L.stream3 && s != L.stream3) ? L.stream3 : s;
+}
+// both halves.  s_levels == s (or null): one queue, the launch sequence of the undivided tail.  Another queue: it waits for the
+// chunk sums (the first slot's ev_chunks) and takes the levels, the copy and the completion events; `s` goes on without them.  Whoever
+// reuses a slot's buffers waits for its completion event as before (msm_finish_t, wait_plan_users), wherever that was recorded.
+template <class C, class CC = C>
+static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t s, int second_slot = -1, hipStream_t s_levels = nullptr) {
+    if (!s) s = L.stream;
+    int rc = msm_launch_tail_chunks<C, CC>(L, slot_ids, nslots, s, second_slot);
+    if (rc) return rc;
+    MsmPending& P0 = ws(L).slot[slot_ids[0]];
+    if (s_levels && s_levels != s && P0.info.n) {
+        if (!P0.ev_chunks) WS_HIP_CHECK(hipEventCreateWithFlags(&P0.ev_chunks, hipEventDisableTiming));
+        WS_HIP_CHECK(hipEventRecord(P0.ev_chunks, s));
+        WS_HIP_CHECK(hipStreamWaitEvent(s_levels, P0.ev_chunks, 0));
+    } else {
+        s_levels = s;
+    }
+    return msm_launch_tail_levels<C>(L, slot_ids, nslots, s_levels, second_slot);
+}
 
 template <class C, class H>
-static int msm_launch(Lane& L, int which, const typename H::Aff* d_points_ref, bool prepared, int* slot_out, hipStream_t s) {
+static int msm_launch(Lane& L, int which, const typename H::Aff* d_points_ref, bool prepared, int* slot_out, hipStream_t s, hipStream_t s_levels) {
     if (!s) s = L.stream;
+    s_levels = tail_levels_queue(L, s, s_levels);
     int rc = msm_launch_acc<C, H>(L, which, d_points_ref, prepared, slot_out, s);
     if (rc) return rc;
-    rc = tail_split<C>() ? msm_launch_tail<typename TailCurve<C>::paired, typename TailCurve<C>::type>(L, slot_out, 1, s)
-                         : msm_launch_tail<typename TailCurve<C>::type>(L, slot_out, 1, s);
+    rc = tail_split<C>() ? msm_launch_tail<typename TailCurve<C>::paired, typename TailCurve<C>::type>(L, slot_out, 1, s, -1, s_levels)
+                         : msm_launch_tail<typename TailCurve<C>::type>(L, slot_out, 1, s, -1, s_levels);
     if (rc) msm_abort_slots(L, slot_out, 1, s, nullptr);
     return rc;
 }
 
 // several G1 point sets against the current plan (or, with plan_ids, against variants of one plan: same geometry): accumulations
 // back to back -- small sums: in ONE launch --, then ONE batched tail
-int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, bool prepared, int* slots, hipStream_t s, const int* plan_ids) {
+int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, bool prepared, int* slots, hipStream_t s, const int* plan_ids, hipStream_t s_levels) {
     if (!ctx()) return WS_ERR_NOINIT;
     if (nsets < 1 || nsets > 4) return WS_ERR_ARG;
     if (!s) s = L.stream;
+    s_levels = tail_levels_queue(L, s, s_levels);
     MsmWorkspace& M = ws(L);
     const int keep = M.cur;
     for (int k = 0; k < nsets; k++) slots[k] = -1;
@@ -1925,15 +1982,15 @@ int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, b
         for (int k = 0; k < nsets; k++) Ps[k] = &M.slot[slots[k]];
         rc = msm_acc_sets<G1R29>(L, Ps, nsets, 0, s);
     }
-    if (!rc) rc = tail_pair_g1() ? msm_launch_tail<TailCurve<G1R29>::paired, TailCurve<G1R29>::type>(L, slots, nsets, s)
-                                 : msm_launch_tail<TailCurve<G1R29>::type>(L, slots, nsets, s);
+    if (!rc) rc = tail_pair_g1() ? msm_launch_tail<TailCurve<G1R29>::paired, TailCurve<G1R29>::type>(L, slots, nsets, s, -1, s_levels)
+                                 : msm_launch_tail<TailCurve<G1R29>::type>(L, slots, nsets, s, -1, s_levels);
     if (rc) msm_abort_slots(L, slots, nsets, s, nullptr);
     return rc;
 }
 
-int msm_g1_launch(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot, hipStream_t s) {
+int msm_g1_launch(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot, hipStream_t s, hipStream_t s_levels) {
     if (!ctx()) return WS_ERR_NOINIT;
-    return msm_launch<G1R29, G1>(L, 0, d_points, prepared, slot, s);
+    return msm_launch<G1R29, G1>(L, 0, d_points, prepared, slot, s, s_levels);
 }
 // accumulation and combine only: the buckets wait for a tail (msm_g1_launch_tail_merged)
 int msm_g1_launch_acc_only(Lane& L, const Affine<Fq>* d_points, bool prepared, int* slot, hipStream_t s) {
@@ -1972,9 +2029,9 @@ int msm_g1_launch_tail_merged(Lane& L, int slot_a, int slot_b, hipStream_t s, bo
     }
     return rc;
 }
-int msm_g2_launch(Lane& L, const Affine<Fq2>* d_points, bool prepared, int* slot, hipStream_t s) {
+int msm_g2_launch(Lane& L, const Affine<Fq2>* d_points, bool prepared, int* slot, hipStream_t s, hipStream_t s_levels) {
     if (!ctx()) return WS_ERR_NOINIT;
-    return msm_launch<G2R29, G2>(L, 1, d_points, prepared, slot, s);
+    return msm_launch<G2R29, G2>(L, 1, d_points, prepared, slot, s, s_levels);
 }
 static MsmPending* live_slot(Lane& L, int slot, int which) {
     if (!L.msm || slot < 0 || slot >= kPendingSlots) return nullptr;

@@ -421,7 +421,8 @@ struct MsmSums {
 // this rank's partial sums.
 //
 // Two in-order queues.  Stream s: the witness plan (+ its variants), A, B1, C (one batched tail), B2.  The lane's
-// second queue: CALC_H, the H plan and the H sum.  The reduction tails are chains of ~30 dependent
+// second queue: CALC_H, the H plan and the H sum.  (Full size: the latency levels of B2's tail and of the batched tail of A and B1 on
+// the lane's third queue, see `side` below.)  The reduction tails are chains of ~30 dependent
 // point additions on a few hundred wavefronts; the other queue's full-width kernels take the SIMDs they leave idle.
 // Measured on MI355X, prove 2^20: round 1 one queue (WSNARK_PROVE_OVERLAP=0) 14.5 ms -> two queues 13.2 ms; round 2 (dense
 // key) one queue 12.8 ms -> two queues 11.2 ms, see the sweep notes at `overlap` below.  A tail that shares its SIMDs
@@ -525,14 +526,34 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
     // of A and B1 under ONE batched tail, C last; CALC_H and the H sum on the second queue.  The G2 tail is the slowest chain of the
     // proof (a G2 addition on a lone wavefront: ~23 us, G1: ~7 us); early in the queue it runs beside CALC_H's kernels instead of
     // at the end of the proof, where nothing is left to fill the SIMDs.  A and B1 reach the host before C's accumulation ends, so
-    // the host's share of pi_c (after_ab1) overlaps GPU work.  Every other arrangement tried -- tails on a third queue, all
+    // the host's share of pi_c (after_ab1) overlaps GPU work.  Every other arrangement tried -- whole tails on a third queue, all
     // accumulations back to back, the G2 sum in the middle or last, gates between the queues, stream and wavefront priorities --
     // measured the same or worse (rounds 1-3 and profiles/r05_schedule_experiments.txt).
     // SMALL (round 3; a rank's share of a points-sharded key, circuits up to 2^19): every sum of such a proof is a latency chain --
     // grouping, a sub-millisecond accumulation on a fraction of the SIMDs, a reduction tail of ~33 dependent additions -- so the
     // chains run BESIDE each other: B2 with its tail on a third queue, A, B1 and C under ONE batched tail on the first, CALC_H and
     // H on the second (profiles/r03_s12_prove_order3.txt: 2^16 proofs -31 %, 2^18 -35 %, 2^19 -8 %, 2^20 +3 %).
-    const bool small = overlap && (uint64_t)nv * msm_table_rows(table_cw ? table_cw : 16) < ((uint64_t)1 << 23) && L.stream3 && s != L.stream3;
+    // (WSNARK_PROVE_FULL_SIZE=1: the full-size arrangement whatever the size -- tests reach it at 2^12)
+    const bool small = overlap && (uint64_t)nv * msm_table_rows(table_cw ? table_cw : 16) < ((uint64_t)1 << 23) && L.stream3 && s != L.stream3 &&
+                       tuning_get("PROVE_FULL_SIZE", 0) != 1;
+    // THE SIDE QUEUE (WSNARK_PROVE_TAIL_SIDE; msm.hip: msm_launch_tail_chunks / _levels).  The latency levels of a reduction tail --
+    // msm_chunks2, msm_tree, msm_rows: chains of dependent additions on a few hundred workgroups -- leave this queue: behind B2's
+    // msm_chunks they go to the lane's third queue and this queue goes straight on to the accumulations of A and B1; the same for
+    // the batched tail of A and B1 beside C's accumulation.  The merged tail of C and H is the last work of the proof and stays here.
+    // 0: off; 1: wherever the third queue exists (the small arrangement too: the batched G1 tail's levels behind B2 on its queue);
+    // default: the full-size arrangement only.  Measured (profiles/tail_beside_acc_ab.txt): the levels start at once beside the running
+    // accumulation and last several times their time alone; proofs 8.44 -> 8.29 ms at 2^20, 32.27 -> 31.37 ms at 2^22.
+    const long side_sw = msm_tail_side_switch();
+    const bool side = overlap && L.stream3 && s != L.stream3 && s2 != L.stream3 && (side_sw == 1 || (side_sw != 0 && !small));
+    hipStream_t s_side = side ? L.stream3 : s;
+    if (side && !L.ev_tail) WS_HIP_CHECK(hipEventCreateWithFlags(&L.ev_tail, hipEventDisableTiming));
+    // `s` stays the caller's ordering point: it waits for everything the side queue was given
+    auto join_side = [&]() -> int {
+        if (!side) return WS_OK;
+        WS_HIP_CHECK(hipEventRecord(L.ev_tail, L.stream3));
+        WS_HIP_CHECK(hipStreamWaitEvent(s, L.ev_tail, 0));
+        return WS_OK;
+    };
     // ONE reduction tail for C and H (round 7): pi_c only uses their sum, so the H buckets are added to C's bucket by bucket and the
     // chunk sums, trees, rows, copy and host chain run once (msm.hip: msm_chunks<DUAL>; 3 additions per bucket pair instead of 4).  The
     // merged tail goes to the first queue behind C's accumulation and waits there for H's.  Only for the one-call prover on a whole
@@ -552,11 +573,11 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
         WS_HIP_CHECK(hipEventRecord(L.ev_plan, s));                  // the plan (and its variants) are complete on s
         WS_HIP_CHECK(hipStreamWaitEvent(s3, L.ev_plan, 0));
         msm_select_plan(L, planB);
-        rc = msm_g2_launch(L, K->pointsB2.as<Affine<Fq2>>(), true, &hB2, s3);                              // :619, on its own queue
+        rc = msm_g2_launch(L, K->pointsB2.as<Affine<Fq2>>(), true, &hB2, s3, s3);                          // :619, on its own queue
         msm_select_plan(L, 0);
         if (rc) return rc;
         WS_HIP_CHECK(hipEventRecord(L.ev_g2, s3));
-        rc = msm_g1_launch_batch(L, g1sets, ch_merge ? 2 : 3, true, g1slots, s, plans);                    // :617, :618, :620: one tail
+        rc = msm_g1_launch_batch(L, g1sets, ch_merge ? 2 : 3, true, g1slots, s, plans, s_side);            // :617, :618, :620: one tail
         hA = g1slots[0]; hB1 = g1slots[1]; hC = g1slots[2];
         if (rc) return rc;
         if (ch_merge && (rc = msm_g1_launch_acc_only(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s))) return rc;   // (its tail: with H's, below)
@@ -564,21 +585,22 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
         tr.mark("plan(w) + B2 on queue 3 + A, B1, C batched");
     } else {
         msm_select_plan(L, planB);
-        rc = msm_g2_launch(L, K->pointsB2.as<Affine<Fq2>>(), true, &hB2, s);                               // :619
+        rc = msm_g2_launch(L, K->pointsB2.as<Affine<Fq2>>(), true, &hB2, s, s_side);                       // :619
         msm_select_plan(L, 0);
         if (rc) return rc;
         tr.mark("plan(w) [+ variants] + launch B2");
-        rc = msm_g1_launch_batch(L, g1sets, 2, true, g1slots, s, plans);                                   // :617, :618
+        rc = msm_g1_launch_batch(L, g1sets, 2, true, g1slots, s, plans, s_side);                           // :617, :618
         hA = g1slots[0]; hB1 = g1slots[1];
         if (rc) return rc;
         msm_select_plan(L, 0);
         rc = ch_merge ? msm_g1_launch_acc_only(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s)               // (its tail: with H's, below)
-                      : msm_g1_launch(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s);                       // :620 (padded)
+                      : msm_g1_launch(L, K->pointsC.as<Affine<Fq>>(), true, &hC, s, s);                    // :620 (padded)
         if (rc) return rc;
         tr.mark("launch A, B1, C");
     }
     if (skip_h) {
         // distributed proving with the four-step CALC_H (wasmsnark_amd/dist.py): h and the H sum are the caller's
+        if ((rc = join_side())) return rc;
         if ((rc = msm_g1_finish(L, hA, &out->A))) return rc;
         if ((rc = msm_g1_finish(L, hB1, &out->B1))) return rc;
         if (after_ab1) after_ab1(*out);
@@ -598,12 +620,13 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
     msm_select_plan(L, (s2 != s || ch_merge) ? 1 : 0);
     rc = msm_plan_dev(L, d_h + K->hlo, K->h_local, sh, s2, table_ch);
     if (!rc) rc = ch_merge ? msm_g1_launch_acc_only(L, K->pointsH.as<Affine<Fq>>(), true, &hH, s2)
-                           : msm_g1_launch(L, K->pointsH.as<Affine<Fq>>(), true, &hH, s2);                 // :614
+                           : msm_g1_launch(L, K->pointsH.as<Affine<Fq>>(), true, &hH, s2, s2);             // :614
     msm_select_plan(L, 0);
     if (rc) return rc;
     if (s2 != s) { WS_HIP_CHECK(hipEventRecord(L.ev_h, s2)); WS_HIP_CHECK(hipStreamWaitEvent(s, L.ev_h, 0)); }   // s stays the caller's ordering point
     bool ch_merged = false;                          // hC carries C + H, hH is released with it
     if (ch_merge && (rc = msm_g1_launch_tail_merged(L, hC, hH, s, &ch_merged))) return rc;      // (behind the wait: H's buckets are complete)
+    if ((rc = join_side())) return rc;               // (behind the merged tail: nothing on this queue waits for the side queue's levels)
     tr.mark(ch_merged ? "plan(h) + accumulate H + one tail for C + H" : "plan(h) + launch H");
     const bool g2_fin = !small;                      // (small proofs: B2 ends on its own queue, A / B1 / C come first)
     if (g2_fin && (rc = msm_g2_finish(L, hB2, &out->B2))) return rc;
