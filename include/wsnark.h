@@ -328,8 +328,7 @@ int wsnark_pkey_delta_verify_file(const char* old_path, const char* new_path, co
  *                             input gets the audit's two cheap tests as in wsnark_g{1,2}_scale_batch (NOT the G2 subgroup test): a
  *                             bad point is WSNARK_ERR_FORMAT (wsnark_last_error names the first index), out is then untouched.
  *                             n/2 log2 n scalar multiplications, one butterfly per lane; needs wsnark_init (WSNARK_ERR_NOINIT) and
- *                             takes a lane of the context.  WSNARK_PKSETUP_NTT_UNIFORM=0 reads every stage's twiddle digits per lane
- *                             (a measurement switch: the bytes do not depend on it). */
+ *                             takes a lane of the context. */
 int wsnark_g1_ntt(const void* points, uint64_t n, int inverse, void* out);
 int wsnark_g2_ntt(const void* points, uint64_t n, int inverse, void* out);
 /* wsnark_pkey_setup*: the key of a circuit under delta = 1 and gamma = 1 -- the key wsnark_pkey_contribute is then applied to.
@@ -702,9 +701,8 @@ int wsnark_zkey_export_size(uint32_t n_vars, uint32_t n_public, uint32_t domain,
  *                             n > 2^24: WSNARK_ERR_SIZE; a NULL pointer: WSNARK_ERR_ARG; before wsnark_init WSNARK_ERR_NOINIT.
  *                             Points, scalars and results stream through the staging ring in chunks of WSNARK_PWTAU_CHUNK points
  *                             (default 2^18, clamped to [64, 2^22]): device memory does not grow with n.  Each call takes a lane.
- *                             WSNARK_PWTAU_MUL picks the kernel's chain (same bytes): 1 = shipped: fixed signed 4-bit windows over a
- *                             per-lane table of the point's multiples 1 .. 8, every lane adding at the same steps; 0 = a per-lane
- *                             non-adjacent form, the chain of wsnark_g{1,2}_scale_batch with the digit branch divergent.
+ *                             The kernel's chain: fixed signed 4-bit windows over a per-lane table of the point's multiples
+ *                             1 .. 8, every lane adding at the same steps.
  *   tau32, alpha32, beta32    32 bytes plain little-endian each, reduced mod r; a secret that is 0 mod r is WSNARK_ERR_ARG.  NULL
  *                             draws the 32 bytes from the OS (getrandom): the production case.  The library never returns a secret
  *                             and wipes t, a, b and the table of t^(2^j) (volatile stores) before it returns; the device buffer

@@ -194,18 +194,6 @@ def check_ntt_round_trip(bn, g, bits):
         assert bn.group_ntt(g, bn.group_ntt(g, data, first), not first) == data
 
 
-def check_ntt_uniform_switch(bn, g, bits, tune):
-    """PKSETUP_NTT_UNIFORM = 0, 2, 3 (per-lane digits in offset order, in block order; the late stages in offset order) give the bytes
-    of the shipped variant"""
-    logs = logs_for(bits, seed=10)
-    data = points_of_logs(bn, g, logs)
-    want = points_of_logs(bn, g, ntt_logs(logs, True))
-    assert bn.group_ntt(g, data, True) == want
-    for mode in (0, 2, 3):
-        tune(bn.lib, "PKSETUP_NTT_UNIFORM", mode)
-        assert bn.group_ntt(g, data, True) == want, mode
-
-
 def check_ntt_errors(bn, so_path):
     from wasmsnark_amd._lib import WsnarkError
     c = bn.lib.c

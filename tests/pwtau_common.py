@@ -147,8 +147,8 @@ def check_mul_outside_subgroup(bn):
     assert got == want, ps.differing(2, got, want)
 
 
-def check_mul_modes(bn, g, tune, n=130):
-    """PWTAU_MUL = 0 (per-lane NAF) and 1 (fixed signed windows) give the same bytes, and those of the yardstick"""
+def check_mul_modes(bn, g, n=130):
+    """The planted scalars, then random 256-bit ones, on random points with one infinity among them: the bytes of the yardstick"""
     sz = size_of(g)
     ks = planted_scalars()[:n]
     rnd = random.Random(80 + g)
@@ -157,12 +157,8 @@ def check_mul_modes(bn, g, tune, n=130):
     pts = bytearray(ps.points_of_logs(bn, g, logs))
     want = bytearray(want_products(bn, g, logs, ks))
     pts[sz * 11:sz * 12] = want[sz * 11:sz * 12] = inf9(g)
-    out = {}
-    for mode in (0, 1):
-        tune(bn.lib, "PWTAU_MUL", mode)
-        out[mode] = bn.mul_points(g, pts, scalars_bytes(ks))
-        assert out[mode] == bytes(want), (g, mode, ps.differing(g, out[mode], bytes(want)))
-    assert out[0] == out[1]
+    got = bn.mul_points(g, pts, scalars_bytes(ks))
+    assert got == bytes(want), (g, ps.differing(g, got, bytes(want)))
 
 
 def check_mul_chunks(bn, tune, n=150):

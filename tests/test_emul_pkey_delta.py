@@ -18,8 +18,13 @@ def bn():
 
 
 @pytest.fixture(scope="module")
-def key7(bn):
-    return pk.synth_sections(bn, 7, seed=1)[2]
+def key7_parts(bn):
+    return pk.synth_sections(bn, 7, seed=1)      # the circuit, its toxic waste, the key's sections
+
+
+@pytest.fixture(scope="module")
+def key7(key7_parts):
+    return key7_parts[2]
 
 
 @pytest.fixture(scope="module")
@@ -37,13 +42,14 @@ def test_rekeyed_key_equals_the_closed_form(bn, tmp_path, tune, log_domain):
     pd.check_closed_form(bn, tmp_path, tune, log_domain)
 
 
-def test_both_normalisations_give_the_same_bytes(bn, key7, tune):
-    outs = []
-    for norm in (0, 1):
-        tune(bn.lib, "PKDELTA_NORM", norm)
-        outs.append(bn.contribute_key(sections=key7, d=pd.D_FIXED)[0])
-        outs.append(bn.scale_points(2, key7["pointsB2"][:128 * 70], pk.R - 2))
-    assert outs[0] == outs[2] and outs[1] == outs[3]
+def test_shared_normalisation_gives_the_yardsticks_bytes(bn, key7_parts):
+    """The one normalisation, an inversion per workgroup, against Python integers.  The contribution to key7 is the closed form: the
+    same key built under delta * d.  70 points of B2 times r - 2 are g2_mul's: a partly filled workgroup passes 1 into the shared
+    inversion, and the chain passes through -P."""
+    circ, S, key7 = key7_parts
+    pd.assert_same_key(bn.contribute_key(sections=key7, d=pd.D_FIXED)[0], pd.closed_form(bn, circ, S, pd.D_FIXED)[0])
+    pts = bytes(key7["pointsB2"][:128 * 70])
+    assert bn.scale_points(2, pts, pk.R - 2) == pd.expected_scale(2, pts, pk.R - 2)
 
 
 def test_scale_batch_rejects_bad_points(bn):

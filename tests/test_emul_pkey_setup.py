@@ -41,10 +41,6 @@ def test_group_ntt_round_trip(bn):
     ps.check_ntt_round_trip(bn, 2, 4)
 
 
-def test_group_ntt_per_lane_digits_give_the_same_bytes(bn, tune):
-    ps.check_ntt_uniform_switch(bn, 1, 7, tune)
-
-
 def test_group_ntt_errors(bn):
     ps.check_ntt_errors(bn, SO_PATH)
 

@@ -46,11 +46,6 @@ def test_group_ntt_round_trip(bn, g):
     ps.check_ntt_round_trip(bn, g, 11)
 
 
-@pytest.mark.parametrize("g", [1, 2])
-def test_group_ntt_per_lane_digits_give_the_same_bytes(bn, g, tune):
-    ps.check_ntt_uniform_switch(bn, g, 10, tune)
-
-
 def test_group_ntt_errors(bn):
     ps.check_ntt_errors(bn, bn.lib.path)
 

@@ -46,8 +46,8 @@ def test_mul_points_g2_point_outside_the_subgroup(bn):
 
 
 @pytest.mark.parametrize("g", [1, 2])
-def test_mul_points_both_chains_give_the_same_bytes(bn, g, tune):
-    pw.check_mul_modes(bn, g, tune, n=300)
+def test_mul_points_both_chains_give_the_same_bytes(bn, g):
+    pw.check_mul_modes(bn, g, n=300)
 
 
 def test_mul_points_chunks(bn, tune):

@@ -115,7 +115,6 @@ def check_basis_uniform_switch(bn, bits, tune):
     logs = ps.logs_for(bits, seed=32)
     data = ps.points_of_logs(bn, 1, logs)
     want = [ps.points_of_logs(bn, 1, to_monomial(logs)), ps.points_of_logs(bn, 1, to_lagrange(logs))]
-    tune(bn.lib, "PKSETUP_NTT_UNIFORM", 0)
     for lag in (False, True):
         assert bn.h_basis(data, to_lagrange=lag) == want[lag], lag
 

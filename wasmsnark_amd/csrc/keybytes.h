@@ -78,8 +78,14 @@ __device__ inline void pk_reduce(int st, uint64_t index, PkAcc* __restrict__ acc
     if (st >= 1 && st <= 3) atomicMax(&acc->first, ~(((unsigned long long)index << 3) | (unsigned long long)st));
 }
 
-// ---- one scalar for many points (pkeydelta.hip: scale_points_kernel; pkeysetup.hip: the twiddles of the group transform; pwtau.hip:
-// a scalar per point) ----
+// ---- one scalar for many points (pkeydelta.hip: scale_points_kernel; pkeysetup.hip: the twiddles of the group transform and the
+// coefficients of the column sums) ----
+// a wipe the compiler cannot drop: the stores are volatile
+inline void wipe(void* p, size_t n) {
+    volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
+    for (size_t i = 0; i < n; i++) v[i] = 0;
+}
+
 // the scalar in non-adjacent form: digit i is non-zero iff bit i of nz, negative iff bit i of neg; top = index of the leading digit
 // (always +1), -1 for k = 0.  k < r < 2^254, so the form has at most 255 digits.
 struct ScaleDigits { uint64_t nz[4], neg[4]; int32_t top; };
@@ -92,7 +98,8 @@ __device__ __forceinline__ uint64_t word4(uint64_t a0, uint64_t a1, uint64_t a2,
     r = w == 3 ? a3 : r;
     return r;
 }
-// k (plain, < 2^255) -> non-adjacent form: while k: odd -> digit 2 - (k mod 4) in {1, -1}, k -= digit; k >>= 1
+// k (plain, < 2^255) -> non-adjacent form: while k: odd -> digit 2 - (k mod 4) in {1, -1}, k -= digit; k >>= 1.  On the host k may be
+// a contribution's secret (pkeydelta.hip: d^-1, the scalar of scale_batch): the working words are wiped before the function returns.
 WS_HD void naf_digits(const Fe& k, ScaleDigits* D) {
     for (int i = 0; i < 4; i++) D->nz[i] = D->neg[i] = 0;
     D->top = -1;
@@ -101,7 +108,7 @@ WS_HD void naf_digits(const Fe& k, ScaleDigits* D) {
         if (w[0] & 1) {
             D->nz[i >> 6] |= (uint64_t)1 << (i & 63);
             D->top = i;
-            if ((w[0] & 3) == 3) {                      // digit -1: k += 1
+            if ((w[0] & 3) == 3) {                      // digit -1: k += 1 (the carry chain of a run of ones)
                 D->neg[i >> 6] |= (uint64_t)1 << (i & 63);
                 for (int j = 0; j < 5 && ++w[j] == 0; j++) {}
             } else {
@@ -111,11 +118,52 @@ WS_HD void naf_digits(const Fe& k, ScaleDigits* D) {
         for (int j = 0; j < 4; j++) w[j] = (w[j] >> 1) | (w[j + 1] << 63);
         w[4] >>= 1;
     }
+#ifndef __HIP_DEVICE_COMPILE__
+    wipe(w, sizeof w);
+#endif
 }
 
-// 1 / z for every lane of a 256-lane workgroup behind ONE inversion, scale_points_kernel's tree: heap-ordered products in LDS, node
-// j = node 2j x node 2j+1, leaves 256 + lane; wavefront 0 inverts the root; down again node j holds the INVERSE of its product.
-// Every lane of the workgroup arrives (a lane with nothing to invert passes 1); once per kernel.
+// The double-and-add chain over the digits z (non-zero) and g (negative), most significant first: a enters as P itself in XYZZ -- the
+// leading digit `top` is +1 -- and leaves as k P.  The masks are eight values, not two arrays: they stay in registers (word4), and
+// where the caller's digits are the wavefront's (the argument block of scale_points_kernel, readfirstlane in the group transform)
+// the digit test is a scalar branch.
+// Every addition is C::madd, the mixed addition WITH all four corner cases, and it has to be: a = m P with m the value of the digits
+// read so far, doubled; a == +/-P happens iff 2m = +/-1 mod ord(P), which a scalar near the group order reaches in its last steps
+// (k = r - 2 passes through -P and adds -P: a doubling), and which a G2 point outside the order-r subgroup -- legal input here, the
+// subgroup test is the audit's -- can reach anywhere; a == infinity follows one step later.  The unguarded madd_fast would need a
+// proof that the input has order r and that no digit prefix is +/-1/2 mod r: not available.  The doubling handles infinity and
+// y == 0 by itself (curve.h).
+template <class C>
+__device__ __forceinline__ void naf_chain(typename C::Pt& a, const typename C::Aff& P, uint64_t z0, uint64_t z1, uint64_t z2, uint64_t z3,
+                                          uint64_t g0, uint64_t g1, uint64_t g2, uint64_t g3, int top) {
+#pragma unroll 1
+    for (int d = top - 1; d >= 0; d--) {
+        a = C::dbl(a);
+        if ((word4(z0, z1, z2, z3, d >> 6) >> (d & 63)) & 1) C::madd(a, P, ((word4(g0, g1, g2, g3, d >> 6) >> (d & 63)) & 1) != 0);
+    }
+}
+
+// One result R (XYZZ) behind its inverse inv = 1 / (ZZ ZZZ): affine, in reference format (last: canonical words, what leaves the
+// device) or in the field's packed internal form (between the stages of the group transform).  Not finite -- R = O, which x == 0
+// encodes, or a lane whose input was bad (unspecified) -- is zero bytes.
+template <class C>
+__device__ inline typename C::AffP affine_result(const typename C::Pt& R, bool fin, const typename C::El& inv, int last) {
+    typedef typename C::Field F;
+    typename C::AffP r;
+    if (!fin) {
+        memset(&r, 0, sizeof r);
+    } else {
+        const typename C::El x = F::mul(R.x, F::mul(inv, R.zzz)), y = F::mul(R.y, F::mul(inv, R.zz));
+        r = last ? typename C::AffP{F::from_internal(x), F::from_internal(y)} : typename C::AffP{F::pack(x), F::pack(y)};
+    }
+    return r;
+}
+
+// 1 / z for every lane of a 256-lane workgroup behind ONE inversion: heap-ordered products in LDS, node j = node 2j x node 2j+1,
+// leaves 256 + lane; wavefront 0 inverts the root while the other three wait; down again node j holds the INVERSE of its product: the
+// children of j are inv(j) x the sibling's product, both written by the one lane that read both (24 products and a quarter of an
+// inversion per lane instead of a Fermat inversion's 363).  Every lane of the workgroup arrives (a lane with nothing to invert passes
+// 1); once per kernel.
 template <class F>
 __device__ inline typename F::El block_inverse(const typename F::El& z) {
     typedef typename F::El El;
@@ -154,6 +202,16 @@ inline void pk_decode(const PkAcc& a, uint64_t* inf, uint64_t* bad, uint64_t* fi
 }
 // pk_classify's curve_b for the two device curves (either may be nullptr); the twist's comes from pairing_consts
 int pk_curve_b(G1R29::El* b1, G2R29::El* b2);
+inline int curve_b(G1R29::El* out) { return pk_curve_b(out, nullptr); }
+inline int curve_b(G2R29::El* out) { return pk_curve_b(nullptr, out); }
+// k32 (plain LE, any 256-bit value, possibly a secret: the copy is wiped) reduced mod r
+inline Fe load_scalar(const uint8_t* k32) {
+    Fe k;
+    memcpy(&k, k32, 32);
+    const Fe r = Fr::reduce_full(k);
+    wipe(&k, sizeof k);
+    return r;
+}
 
 // reference-format bytes -> the host pairing's point; the reason it is bad (0 = good).  check = false: only the infinity rule
 uint32_t fixed_g1(const uint8_t* p, bool check, hostpair::G1A* out);

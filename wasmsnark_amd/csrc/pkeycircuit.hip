@@ -97,12 +97,6 @@ int circuit_to_csr(const wsnark_circuit_t* K, CsrMatrix M[3], hipStream_t s) {
 }
 
 namespace {
-// a wipe the compiler cannot drop: the stores are volatile
-void wipe(void* p, size_t n) {
-    volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
-    for (size_t i = 0; i < n; i++) v[i] = 0;
-}
-
 // what setup_prepare (pkeysetup.hip) rejects of a transcript, with its codes
 int powers_shape_check(const wsnark_powers_t* P, uint64_t n) {
     if (!P || !P->tau_g1 || !P->tau_g2 || !P->alpha_tau_g1 || !P->beta_tau_g1 || !P->beta_g2) return WS_ERR_ARG;

@@ -10,16 +10,14 @@
 //   scale_points_kernel<C>: one lane per point (reference format in and out).  The scalar never comes from memory: the host recodes
 //     it once into non-adjacent form (digits -1, 0, 1; on average 1/3 of them non-zero: ~85 additions behind the 253 doublings
 //     instead of ~127) and passes the two digit masks in the argument block, so the loop's branches are scalar branches and no
-//     wavefront diverges on them.  A negative digit is madd's negate flag.
+//     wavefront diverges on them.  A negative digit is madd's negate flag.  The chain itself is keybytes.h's naf_chain.
 //     Before the chain each lane classifies its point with the audit's own code (keybytes.h: pk_classify -- infinity by the loaders'
 //     rule, every coordinate < q, the curve equation); counts and the first bad index are reduced by the audit's pk_reduce and read
 //     by its pk_decode.  An infinity point is copied through.
 //     Products per finite point on G1 (counted from curve.h's formulas, squarings as products, the fused Y3 as two): input tests
-//     2 + 3, chain 253 x 9 (dbl) + ~85 x 11 (madd), normalisation 363 (Fermat) + 5, output 2: ~3600, the inversion ~10 % of it.
-//   normalisation (PKDELTA_NORM): 0 = one Fermat inversion per lane; 1 = ONE inversion per workgroup: a product tree over the
-//     256 lanes' ZZ ZZZ in LDS (8 levels up), wavefront 0 inverts the root while the other three wait, 8 levels down give every
-//     lane its own inverse (24 products and a quarter of an inversion per lane instead of 363).  Measured at 2^20 points: 24.7 ms
-//     per lane, 23.7 ms shared: the shared inversion is the default.
+//     2 + 3, chain 253 x 9 (dbl) + ~85 x 11 (madd), normalisation 24 + 363 / 4 + 5, output 2: ~3350.
+//   normalisation: ONE inversion per workgroup (keybytes.h: block_inverse): a product tree over the 256 lanes' ZZ ZZZ in LDS (8
+//     levels up), wavefront 0 inverts the root while the other three wait, 8 levels down give every lane its own inverse.
 //
 //   streaming: a section goes through the staging ring in chunks of PKDELTA_CHUNK points (default 2^18); chunk k + 1 is staged on
 //     the lane's copy queue while chunk k's kernel runs on its first queue, and chunk k's result comes down into one of two pinned
@@ -43,13 +41,11 @@ namespace wsnark {
 using namespace hostpair;
 
 // ---- device ----
-// (the scalar in non-adjacent form: keybytes.h, ScaleDigits)
+// (the scalar in non-adjacent form, the chain over its digits, the shared inversion and the affine result: keybytes.h)
 template <class C>
 __global__ __launch_bounds__(256) void scale_points_kernel(const typename C::AffP* __restrict__ pts, uint64_t n, uint64_t base, ScaleDigits D,
-                                                             typename C::El curve_b, int norm, typename C::AffP* __restrict__ out,
-                                                             PkAcc* __restrict__ acc) {
+                                                             typename C::El curve_b, typename C::AffP* __restrict__ out, PkAcc* __restrict__ acc) {
     typedef typename C::Field F;
-    typedef typename C::El El;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int st = 0;               // pk_reduce's states: 0 good, 1 unreduced, 2 off the curve, 4 infinity
     bool live = false;        // a good finite point and a non-zero scalar: this lane runs the chain
@@ -60,111 +56,24 @@ __global__ __launch_bounds__(256) void scale_points_kernel(const typename C::Aff
     }
     pk_reduce(st, base + i, acc);
 
-    // The chain, most significant digit first.  The leading digit is +1: acc starts as P itself (finite: x != 0 was decided above).
-    // Every later addition is C::madd, the mixed addition WITH all four corner cases, and it has to be: acc = m P with m the value
-    // of the digits read so far, doubled; acc == +/-P happens iff 2m = +/-1 mod ord(P), which a scalar near the group order reaches
-    // in its last steps (k = r - 2 passes through -P and adds -P: a doubling), and which a G2 point outside the order-r subgroup
-    // -- legal input here, the subgroup test is the audit's -- can reach anywhere; acc == infinity follows one step later.  The
-    // unguarded madd_fast would need a proof that the input has order r and that no digit prefix is +/-1/2 mod r: not available.
-    // The doubling handles infinity and y == 0 by itself (curve.h).
+    // the chain starts as P itself (finite: x != 0 was decided above)
     typename C::Pt a = C::infinity();
     if (live) {
         a = typename C::Pt{P.x, P.y, F::one(), F::one()};
-#pragma unroll 1
-        for (int d = D.top - 1; d >= 0; d--) {
-            a = C::dbl(a);
-            if ((D.nz[d >> 6] >> (d & 63)) & 1) C::madd(a, P, ((D.neg[d >> 6] >> (d & 63)) & 1) != 0);
-        }
+        naf_chain<C>(a, P, D.nz[0], D.nz[1], D.nz[2], D.nz[3], D.neg[0], D.neg[1], D.neg[2], D.neg[3], D.top);
     }
     const bool fin = live && !C::is_inf(a);
 
-    El izz = F::one(), izzz = F::one();
-    if (norm == 0) {
-        // one Fermat inversion per lane, as mul_base_kernel / to_affine_jac
-        if (fin) {
-            const El inv = F::inv(F::mul(a.zz, a.zzz));
-            izz = F::mul(inv, a.zzz);
-            izzz = F::mul(inv, a.zz);
-        }
-    } else {
-        // one inversion per workgroup (blockDim.x == 256): heap-ordered product tree in LDS, node j = node 2j x node 2j+1, leaves
-        // 256 + lane (1 for a lane with nothing to normalise).  Down again node j holds the INVERSE of its product: the children of
-        // j are inv(j) x the sibling's product, both written by the one lane that read both.
-        __shared__ El tree[512];
-        const unsigned t = threadIdx.x;
-        tree[256 + t] = fin ? F::mul(a.zz, a.zzz) : F::one();
-        __syncthreads();
-        for (unsigned w = 128; w >= 1; w >>= 1) {
-            if (t < w) tree[w + t] = F::mul(tree[2 * (w + t)], tree[2 * (w + t) + 1]);
-            __syncthreads();
-        }
-        if (t < 64) {                         // wavefront 0, every lane the same value: a uniform chain, one store
-            const El r = F::inv(tree[1]);
-            if (t == 0) tree[1] = r;
-        }
-        __syncthreads();
-        for (unsigned w = 1; w <= 128; w <<= 1) {
-            if (t < w) {
-                const El up = tree[w + t], l = tree[2 * (w + t)], r = tree[2 * (w + t) + 1];
-                tree[2 * (w + t)] = F::mul(up, r);
-                tree[2 * (w + t) + 1] = F::mul(up, l);
-            }
-            __syncthreads();
-        }
-        if (fin) {
-            const El inv = tree[256 + t];
-            izz = F::mul(inv, a.zzz);
-            izzz = F::mul(inv, a.zz);
-        }
-    }
-    if (i < n) {
-        typename C::AffP r;
-        if (st == 4) r = pts[i];                                 // infinity: copied through byte for byte
-        else if (!fin) memset(&r, 0, sizeof r);                  // k P = O (x == 0 encodes it), or a bad point (unspecified)
-        else r = typename C::AffP{F::from_internal(F::mul(a.x, izz)), F::from_internal(F::mul(a.y, izzz))};
-        out[i] = r;
-    }
+    // one inversion per workgroup (blockDim.x == 256): every lane arrives, a lane with nothing to normalise passes 1
+    const typename C::El inv = block_inverse<F>(fin ? F::mul(a.zz, a.zzz) : F::one());
+    if (i < n) out[i] = st == 4 ? pts[i] : affine_result<C>(a, fin, inv, 1);      // infinity: copied through byte for byte
 }
 
 // ---- host ----
 namespace {
-// a wipe the compiler cannot drop: the stores are volatile
-void wipe(void* p, size_t n) {
-    volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
-    for (size_t i = 0; i < n; i++) v[i] = 0;
+template <class C> const char* scale_name() {
+    return sizeof(typename C::AffP) == 64 ? "scale_points_g1_shared_inv" : "scale_points_g2_shared_inv";
 }
-
-// k (plain, < 2^255) -> non-adjacent form: while k: odd -> digit 2 - (k mod 4) in {1, -1}, k -= digit; k >>= 1
-void recode_naf(const Fe& k, ScaleDigits* D) {
-    memset(D, 0, sizeof *D);
-    D->top = -1;
-    uint64_t w[5] = {k.l[0], k.l[1], k.l[2], k.l[3], 0};
-    for (int i = 0; i < 256 && (w[0] | w[1] | w[2] | w[3] | w[4]); i++) {
-        if (w[0] & 1) {
-            D->nz[i >> 6] |= (uint64_t)1 << (i & 63);
-            D->top = i;
-            if ((w[0] & 3) == 3) {                      // digit -1: k += 1 (the carry chain of a run of ones)
-                D->neg[i >> 6] |= (uint64_t)1 << (i & 63);
-                for (int j = 0; j < 5 && ++w[j] == 0; j++) {}
-            } else {
-                w[0] -= 1;
-            }
-        }
-        for (int j = 0; j < 4; j++) w[j] = (w[j] >> 1) | (w[j + 1] << 63);
-        w[4] >>= 1;
-    }
-    wipe(w, sizeof w);
-}
-
-inline int curve_b(G1R29::El* out) { return pk_curve_b(out, nullptr); }
-inline int curve_b(G2R29::El* out) { return pk_curve_b(nullptr, out); }
-template <class C> const char* scale_name(int norm) {
-    constexpr bool g1 = sizeof(typename C::AffP) == 64;
-    return g1 ? (norm ? "scale_points_g1_shared_inv" : "scale_points_g1") : (norm ? "scale_points_g2_shared_inv" : "scale_points_g2");
-}
-
-// the shipped normalisation: DESIGN.md section "Phase-2 contribution" has both measured
-int delta_norm() { return tuning_get("PKDELTA_NORM", 1) == 0 ? 0 : 1; }
 
 // where a scaled chunk goes: caller memory, or a file
 struct Sink {
@@ -226,7 +135,7 @@ struct ScaleRing {
 // sink[at ..] = k * src[0 .. n), chunk by chunk.  The last chunk's download is still pending when this returns (R.drain()).
 template <class C>
 int scale_stream(Context* X, ScaleRing& R, const uint8_t* src, uint64_t n, uint64_t chunk, const ScaleDigits& D, const typename C::El& cb,
-                 int norm, const Sink& sink, PkAcc* d_acc, void (*release)(const void*, size_t)) {
+                 const Sink& sink, PkAcc* d_acc, void (*release)(const void*, size_t)) {
     typedef typename C::AffP AffP;
     const size_t psz = sizeof(AffP);
     int rc;
@@ -238,8 +147,8 @@ int scale_stream(Context* X, ScaleRing& R, const uint8_t* src, uint64_t n, uint6
         if ((rc = stage_chunk(R.d_in[b].p, src + lo * psz, (size_t)m * psz, R.sc, release))) return rc;
         WS_HIP_CHECK(hipEventRecord(R.ev_up[b], R.sc));
         WS_HIP_CHECK(hipStreamWaitEvent(R.s, R.ev_up[b], 0));
-        X->timer.begin(scale_name<C>(norm), R.s);
-        hipLaunchKernelGGL(scale_points_kernel<C>, dim3(ceil_div_u64(m, 256)), dim3(256), 0, R.s, R.d_in[b].as<AffP>(), m, lo, D, cb, norm,
+        X->timer.begin(scale_name<C>(), R.s);
+        hipLaunchKernelGGL(scale_points_kernel<C>, dim3(ceil_div_u64(m, 256)), dim3(256), 0, R.s, R.d_in[b].as<AffP>(), m, lo, D, cb,
                            R.d_out[b].as<AffP>(), d_acc);
         WS_HIP_CHECK(hipGetLastError());
         X->timer.end(R.s);
@@ -249,13 +158,6 @@ int scale_stream(Context* X, ScaleRing& R, const uint8_t* src, uint64_t n, uint6
         R.pend.on = true; R.pend.sink = &sink; R.pend.at = lo * psz; R.pend.bytes = (size_t)m * psz; R.pend.b = b;
     }
     return WS_OK;
-}
-
-// k32 (plain LE, any 256-bit value) reduced mod r
-Fe load_scalar(const uint8_t* k32) {
-    Fe k;
-    memcpy(&k, k32, 32);
-    return Fr::reduce_full(k);
 }
 
 template <class C>
@@ -269,7 +171,7 @@ int scale_batch(const void* points, uint64_t n, const void* k32, void* out) {
     int rc = curve_b(&cb);
     if (rc) return rc;
     ScaleDigits D;
-    recode_naf(load_scalar((const uint8_t*)k32), &D);
+    naf_digits(load_scalar((const uint8_t*)k32), &D);
     const uint64_t chunk = key_chunk("PKDELTA_CHUNK");
     PkAcc h_acc;
     {
@@ -281,7 +183,7 @@ int scale_batch(const void* points, uint64_t n, const void* k32, void* out) {
         if ((rc = R.init(L->stream, L->stream_copy, (size_t)std::min<uint64_t>(chunk, n) * sizeof(typename C::AffP)))) return rc;
         Sink sink;
         sink.mem = (uint8_t*)out;
-        if ((rc = scale_stream<C>(X, R, (const uint8_t*)points, n, chunk, D, cb, delta_norm(), sink, d_acc.as<PkAcc>(), nullptr))) return rc;
+        if ((rc = scale_stream<C>(X, R, (const uint8_t*)points, n, chunk, D, cb, sink, d_acc.as<PkAcc>(), nullptr))) return rc;
         if ((rc = R.drain())) return rc;
         WS_HIP_CHECK(hipMemcpyAsync(&h_acc, d_acc.p, sizeof h_acc, hipMemcpyDeviceToHost, L->stream));
         WS_HIP_CHECK(hipStreamSynchronize(L->stream));
@@ -313,7 +215,7 @@ int contribute_prepare(const KeySections& S, const uint8_t* d32, Secret* K) {
     wipe(raw, sizeof raw);
     if (Fr::is_zero(K->d)) { set_last_error("contribution: d = 0 mod r"); return WS_ERR_ARG; }
     Fe dinv = Fr::from_mont(Fr::inv(Fr::to_mont(K->d)));
-    recode_naf(dinv, &K->inv_digits);
+    naf_digits(dinv, &K->inv_digits);
     wipe(&dinv, sizeof dinv);
     return WS_OK;
 }
@@ -360,9 +262,8 @@ int contribute_run(const KeySections& S, const Secret& K, const Sink& outC, cons
         ScaleRing ring;
         const uint64_t cap = key_chunk_cap(chunk, std::max(counts[0], counts[1]));
         if ((rc = ring.init(L->stream, L->stream_copy, (size_t)cap * 64))) return rc;
-        const int norm = delta_norm();
-        if ((rc = scale_stream<G1R29>(X, ring, S.Cpts, counts[0], chunk, K.inv_digits, cb, norm, outC, d_acc.as<PkAcc>(), S.release))) return rc;
-        if ((rc = scale_stream<G1R29>(X, ring, S.H, counts[1], chunk, K.inv_digits, cb, norm, outH, d_acc.as<PkAcc>() + 1, S.release))) return rc;
+        if ((rc = scale_stream<G1R29>(X, ring, S.Cpts, counts[0], chunk, K.inv_digits, cb, outC, d_acc.as<PkAcc>(), S.release))) return rc;
+        if ((rc = scale_stream<G1R29>(X, ring, S.H, counts[1], chunk, K.inv_digits, cb, outH, d_acc.as<PkAcc>() + 1, S.release))) return rc;
         if ((rc = ring.drain())) return rc;
         WS_HIP_CHECK(hipMemcpyAsync(h_acc, d_acc.p, sizeof h_acc, hipMemcpyDeviceToHost, L->stream));
         WS_HIP_CHECK(hipStreamSynchronize(L->stream));
@@ -389,10 +290,9 @@ static int scale_dev(Context* X, const void* d_in, uint64_t n, const ScaleDigits
     typename C::El cb;
     const int rc = curve_b(&cb);
     if (rc) return rc;
-    const int norm = delta_norm();
-    X->timer.begin(scale_name<C>(norm), s);
+    X->timer.begin(scale_name<C>(), s);
     hipLaunchKernelGGL(scale_points_kernel<C>, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, reinterpret_cast<const AffP*>(d_in), n, (uint64_t)0, D, cb,
-                       norm, reinterpret_cast<AffP*>(d_out), d_acc);
+                       reinterpret_cast<AffP*>(d_out), d_acc);
     WS_HIP_CHECK(hipGetLastError());
     X->timer.end(s);
     return WS_OK;

@@ -17,7 +17,7 @@
 //     first, the tree in LDS holds the 256 products, and the lane splits its inverse again.  A result at infinity contributes 1.
 //     Every addition is C::madd, WITH the corner cases: P = +/- w Q and infinity operands are ordinary inputs here (a constant
 //     input makes every first-stage butterfly a doubling and a cancellation), and the chain itself passes through +/- Q for
-//     twiddles near r, as scale_points_kernel's comment explains.
+//     twiddles near r, as naf_chain's comment explains (keybytes.h).
 //     Lanes: in the stage of half-span m there are m distinct twiddles w_n^(j n/2m), each used by the n/2m blocks.  Butterfly t is
 //     block (t mod n/2m), offset j = t / (n/2m): neighbouring lanes share j.  With n/2m >= 64 a whole wavefront shares ONE twiddle
 //     (UNIFORM): its digit masks are read through readfirstlane, the chain's "add on a non-zero digit" branch is a scalar branch as
@@ -65,8 +65,9 @@ __device__ inline uint64_t wave_u64(uint64_t v) {
 }
 
 // ---- device ----
-// (word4, naf_digits and block_inverse -- the digit masks in registers, the recoding, the shared inversion -- are keybytes.h's: the
-// phase-1 contribution's kernel, pwtau.hip, uses them too)
+// (naf_digits, naf_chain, block_inverse and affine_result -- the recoding, the chain over the digit masks in registers with the
+// argument for its guarded additions, the shared inversion, the affine output -- are keybytes.h's: scale_points_kernel and the
+// phase-1 contribution's kernel, pwtau.hip, use them too)
 struct TwiddleBase { Fe p[24]; };      // w^(2^i), Montgomery
 __global__ __launch_bounds__(256) void group_twiddle_kernel(TwiddleBase W, uint32_t count, ScaleDigits* __restrict__ out) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,25 +96,11 @@ __global__ __launch_bounds__(256) void group_load_kernel(const typename C::AffP*
     }
 }
 
-// one result of a butterfly behind its inverse 1 / (ZZ ZZZ): affine, in the internal form or (last) in reference format
-template <class C>
-__device__ inline typename C::AffP stage_result(const typename C::Pt& R, bool fin, const typename C::El& inv, int last) {
-    typedef typename C::Field F;
-    typename C::AffP r;
-    if (!fin) {
-        memset(&r, 0, sizeof r);
-    } else {
-        const typename C::El x = F::mul(R.x, F::mul(inv, R.zzz)), y = F::mul(R.y, F::mul(inv, R.zz));
-        r = last ? typename C::AffP{F::from_internal(x), F::from_internal(y)} : typename C::AffP{F::pack(x), F::pack(y)};
-    }
-    return r;
-}
-
 // the stage of half-span m = 2^log_m over the n = 2^log_n points of `a` (n >= 2, log_m < log_n); tw[k] = the digits of w^k, k < n/2.
 // last: the results leave in reference format (canonical; infinity as zero bytes) instead of the internal form.
 template <class C, bool UNIFORM>
 __global__ __launch_bounds__(256) void group_stage_kernel(typename C::AffP* __restrict__ a, uint32_t log_n, uint32_t log_m,
-                                                            const ScaleDigits* __restrict__ tw, int last, int offset_order) {
+                                                            const ScaleDigits* __restrict__ tw, int last) {
     typedef typename C::Field F;
     typedef typename C::El El;
     typedef typename C::Aff Aff;
@@ -123,20 +110,15 @@ __global__ __launch_bounds__(256) void group_stage_kernel(typename C::AffP* __re
     const bool on = t < half;                                   // (n < 512: lanes past the end only keep the barriers company)
     const uint32_t log_cnt = log_n - 1 - log_m;                 // n/2m blocks
     const uint64_t tt = on ? t : 0;
-    // block order: neighbouring lanes share the offset j, hence the twiddle; offset order (measurement only): neighbouring lanes hold
-    // neighbouring offsets of one block -- coalesced loads, 64 twiddles per wavefront
-    const uint64_t j = offset_order ? tt & (((uint64_t)1 << log_m) - 1) : tt >> log_cnt;
-    const uint64_t blk = offset_order ? tt >> log_m : tt & (((uint64_t)1 << log_cnt) - 1);
+    // block order: neighbouring lanes share the offset j, hence the twiddle
+    const uint64_t j = tt >> log_cnt, blk = tt & (((uint64_t)1 << log_cnt) - 1);
     const uint64_t i0 = (blk << (log_m + 1)) + j, i1 = i0 + ((uint64_t)1 << log_m);
     uint32_t k = (uint32_t)(j << log_cnt);                      // the twiddle w_n^(j n/2m): < n/2
     if (UNIFORM) k = WS_WAVE_U32(k);                            // n/2m >= 64: the wavefront's 64 butterflies share j
 
-    Aff P = Aff{F::zero(), F::zero()}, Q = P;
-    if (on) {
-        P = C::unpack_aff(a[i0]);
-        Q = C::unpack_aff(a[i1]);
-    }
-    // T = w^k Q.  The leading digit is +1: the chain starts as Q itself; every later addition is the guarded one (see above).
+    Aff Q = Aff{F::zero(), F::zero()};
+    if (on) Q = C::unpack_aff(a[i1]);
+    // T = w^k Q: the chain starts as Q itself
     Pt T = C::infinity();
     if (on && !C::aff_is_inf(Q)) {
         T = Pt{Q.x, Q.y, F::one(), F::one()};
@@ -148,16 +130,14 @@ __global__ __launch_bounds__(256) void group_stage_kernel(typename C::AffP* __re
                 top = (int)WS_WAVE_U32(top);
                 for (int w = 0; w < 4; w++) { nz[w] = wave_u64(nz[w]); ng[w] = wave_u64(ng[w]); }
             }
-#pragma unroll 1
-            for (int d = top - 1; d >= 0; d--) {
-                T = C::dbl(T);
-                if ((word4(nz[0], nz[1], nz[2], nz[3], d >> 6) >> (d & 63)) & 1) C::madd(T, Q, ((word4(ng[0], ng[1], ng[2], ng[3], d >> 6) >> (d & 63)) & 1) != 0);
-            }
+            naf_chain<C>(T, Q, nz[0], nz[1], nz[2], nz[3], ng[0], ng[1], ng[2], ng[3], top);
         }
     }
-    // R0 = P + T; R1 = P - T = -(T - P)
+    // R0 = P + T; R1 = P - T = -(T - P).  P is loaded here, behind the chain, and not beside Q: held across the chain it costs the
+    // G2 kernels ~100 registers parked in AGPRs (only this lane writes a[i0], and only below)
     Pt R0 = T, R1 = T;
     if (on) {
+        const Aff P = C::unpack_aff(a[i0]);
         C::madd(R0, P, false);
         C::madd(R1, P, true);
         R1 = C::neg(R1);
@@ -168,8 +148,8 @@ __global__ __launch_bounds__(256) void group_stage_kernel(typename C::AffP* __re
     const El z0 = fin0 ? F::mul(R0.zz, R0.zzz) : F::one(), z1 = fin1 ? F::mul(R1.zz, R1.zzz) : F::one();
     const El inv = block_inverse<F>(F::mul(z0, z1));
     if (!on) return;
-    a[i0] = stage_result<C>(R0, fin0, F::mul(inv, z1), last);
-    a[i1] = stage_result<C>(R1, fin1, F::mul(inv, z0), last);
+    a[i0] = affine_result<C>(R0, fin0, F::mul(inv, z1), last);
+    a[i1] = affine_result<C>(R1, fin1, F::mul(inv, z0), last);
 }
 
 // ---- the column sums and hExps (wsnark_pkey_setup) ----
@@ -221,21 +201,13 @@ __global__ __launch_bounds__(256) void column_sum_kernel(const uint64_t* __restr
             const typename C::Aff B = C::aff_to_internal(bp);
             Pt T = Pt{B.x, F::cneg(B.y, neg), F::one(), F::one()};
             const typename C::Aff Bs = typename C::Aff{T.x, T.y};
-#pragma unroll 1
-            for (int d = D.top - 1; d >= 0; d--) {
-                T = C::dbl(T);
-                if ((word4(D.nz[0], D.nz[1], D.nz[2], D.nz[3], d >> 6) >> (d & 63)) & 1) C::madd(T, Bs, ((word4(D.neg[0], D.neg[1], D.neg[2], D.neg[3], d >> 6) >> (d & 63)) & 1) != 0);
-            }
+            naf_chain<C>(T, Bs, D.nz[0], D.nz[1], D.nz[2], D.nz[3], D.neg[0], D.neg[1], D.neg[2], D.neg[3], D.top);
             acc = C::add(acc, T);
         }
     }
     const bool fin = mine && !C::is_inf(acc);
     const El inv = block_inverse<F>(fin ? F::mul(acc.zz, acc.zzz) : F::one());
-    if (!mine) return;
-    typename C::AffP r;
-    if (!fin) memset(&r, 0, sizeof r);
-    else r = typename C::AffP{F::from_internal(F::mul(acc.x, F::mul(inv, acc.zzz))), F::from_internal(F::mul(acc.y, F::mul(inv, acc.zz)))};
-    out[j] = r;
+    if (mine) out[j] = affine_result<C>(acc, fin, inv, 1);
 }
 
 // a long column's points and plain scalars, gathered for the ordinary MSM
@@ -269,17 +241,11 @@ __global__ __launch_bounds__(256) void hexps_kernel(const G1R29::AffP* __restric
     }
     const bool fin = !C::is_inf(R);
     const C::El inv = block_inverse<F>(fin ? F::mul(R.zz, R.zzz) : F::one());
-    if (i >= n) return;
-    C::AffP r;
-    if (!fin) memset(&r, 0, sizeof r);
-    else r = C::AffP{F::from_internal(F::mul(R.x, F::mul(inv, R.zzz))), F::from_internal(F::mul(R.y, F::mul(inv, R.zz)))};
-    out[i] = r;
+    if (i < n) out[i] = affine_result<C>(R, fin, inv, 1);
 }
 
 // ---- host ----
 namespace {
-inline int curve_b(G1R29::El* out) { return pk_curve_b(out, nullptr); }
-inline int curve_b(G2R29::El* out) { return pk_curve_b(nullptr, out); }
 inline int scale_dev(G1R29*, Context* X, const void* in, uint64_t n, const ScaleDigits& D, void* out, PkAcc* acc, hipStream_t s) {
     return g1_scale_dev(X, in, n, D, out, acc, s);
 }
@@ -316,20 +282,16 @@ int build_twiddles(Context* X, int bits, int inverse, ScaleDigits* d_tw, hipStre
 // the log2 n stages over d_work (bit-reversed internal form in, natural order out; the last stage leaves reference format)
 template <class C>
 int run_stages(Context* X, typename C::AffP* d_work, int bits, const ScaleDigits* d_tw, hipStream_t s) {
-    // PKSETUP_NTT_UNIFORM (the A/B of DESIGN.md section "pkeysetup.hip"; same bytes): 1 = shipped: one twiddle per wavefront where the
-    // stage has 64 blocks, per-lane digits in block order after that; 0 = per-lane digits in offset order everywhere (every wavefront
-    // holds 64 twiddles: the divergent chain); 2 = per-lane digits in block order everywhere; 3 = as 1 with the late stages in offset order
-    const long mode = tuning_get("PKSETUP_NTT_UNIFORM", 1);
-    const bool want_uniform = mode == 1 || mode == 3;
+    // one twiddle per wavefront while the stage has 64 blocks, per-lane digits in block order after that
     const uint32_t grid = ceil_div_u64((uint64_t)1 << (bits - 1), 256);
     for (int lm = 0; lm < bits; lm++) {
-        const bool uniform = want_uniform && bits - 1 - lm >= 6;
-        const int last = lm == bits - 1, offset_order = !uniform && (mode == 0 || mode == 3);
+        const bool uniform = bits - 1 - lm >= 6;
+        const int last = lm == bits - 1;
         X->timer.begin(stage_name<C>(uniform), s);
         if (uniform)
-            hipLaunchKernelGGL((group_stage_kernel<C, true>), dim3(grid), dim3(256), 0, s, d_work, (uint32_t)bits, (uint32_t)lm, d_tw, last, offset_order);
+            hipLaunchKernelGGL((group_stage_kernel<C, true>), dim3(grid), dim3(256), 0, s, d_work, (uint32_t)bits, (uint32_t)lm, d_tw, last);
         else
-            hipLaunchKernelGGL((group_stage_kernel<C, false>), dim3(grid), dim3(256), 0, s, d_work, (uint32_t)bits, (uint32_t)lm, d_tw, last, offset_order);
+            hipLaunchKernelGGL((group_stage_kernel<C, false>), dim3(grid), dim3(256), 0, s, d_work, (uint32_t)bits, (uint32_t)lm, d_tw, last);
         WS_HIP_CHECK(hipGetLastError());
         X->timer.end(s);
     }

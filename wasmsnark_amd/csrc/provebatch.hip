@@ -243,10 +243,6 @@ __global__ __launch_bounds__(256) void batch_final_kernel(Affine<Fq2> beta2, con
 
 // ---- host ----
 namespace {
-void wipe(void* p, size_t n) {      // a wipe the compiler cannot drop
-    volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
-    for (size_t i = 0; i < n; i++) v[i] = 0;
-}
 struct HostSecret {
     std::vector<uint8_t> rs;      // count x (r | s), raw
     std::vector<Fe> sc;           // count x (r mod r, s mod r, rs mod r), plain

@@ -5,13 +5,10 @@
 // multiplies power k by t^k (and by a, b): point i times scalar i, the third shape beside mul_base_kernel (one base, a scalar per
 // lane) and scale_points_kernel (a base per lane, ONE scalar, its digits in the argument block).
 //
-//   mul_points_kernel<C, MODE>: one lane per point (reference format in and out), the scalar from memory, reduced mod r by the lane.
+//   mul_points_kernel<C>: one lane per point (reference format in and out), the scalar from memory, reduced mod r by the lane.
 //     Input tests, counts and the copy-through of infinity are scale_points_kernel's (keybytes.h: pk_classify, pk_reduce); the
-//     result leaves affine behind the shared per-workgroup inversion (keybytes.h: block_inverse).
-//     MODE 0, per-lane NAF: the lane recodes its scalar (naf_digits) and runs scale_points_kernel's chain with the digit masks in
-//       registers, as group_stage_kernel<C, false>: ~253 dbl + ~85 madd per lane, but the "add on a non-zero digit" branch diverges --
-//       with 64 unrelated digit strings a wavefront executes the addition in nearly every step: ~253 x (9 + 11) products' time.
-//     MODE 1, fixed signed windows (shipped): the scalar is cut into 64 windows of 4 bits, digits in [-8, 8] (a window value above
+//     result leaves affine behind the shared per-workgroup inversion (keybytes.h: block_inverse, affine_result).
+//     Fixed signed windows: the scalar is cut into 64 windows of 4 bits, digits in [-8, 8] (a window value above
 //       8 becomes value - 16 and carries into the next window; k < r < 2^254 leaves at most 3 in the top window, bits 252..255, so
 //       the carry INTO it is absorbed there and nothing leaves it).  The lane first writes the table 1P .. 8P of ITS point (one
 //       affine doubling, six mixed additions; XYZZ, not normalised) to a global scratch array laid out [entry][lane], then walks
@@ -20,8 +17,8 @@
 //       adds nothing.  Products per finite G1 point, counted from curve.h's formulas as pkeydelta.hip counts (squarings as
 //       products, the fused Y3 as two): input tests 2 + 3, table 7 + 6 x 11, chain 252 x 9 (dbl) + ~60 x 14 (add), the shared
 //       inversion 24 + 363 / 4 (one wavefront of four inverts), normalisation 5, output 2: ~3290 (tools/pwtau_bench.py counts it over
-//       the scalars of its run) -- the count of ONE lane of the NAF chain (~3330), without the divergence that makes a wavefront of
-//       64 unrelated digit strings pay ~5200.
+//       the scalars of its run) -- the count of ONE lane of a per-lane NAF chain (~3330), without the divergence that makes a
+//       wavefront of 64 unrelated digit strings pay ~5200 there (docs/HISTORY.md has that chain measured).
 //       The table is 8 x 128 B per G1 lane, 8 x 256 B per G2 lane: in LDS that is 256 KiB for a 256-lane workgroup against the CU's
 //       160 KiB, and a runtime-indexed per-thread array would be scratch with nothing coalesced; [entry][lane] in global memory
 //       makes a wavefront's load of one row a run of neighbouring 128-byte records per distinct digit.  A lane reads ~60 x 128 B
@@ -32,7 +29,7 @@
 //   fr_powers_kernel: out[i] = c t^(first + i), plain, from the t^(2^j) in the argument block (as group_twiddle_kernel builds its
 //     twiddles); `first` is the GLOBAL index of the chunk's first power, so the scalars do not depend on the chunking.
 //   streaming: an array goes through the staging ring in chunks of PWTAU_CHUNK points (default 2^18): up, scalars, kernel, down.
-//     Device memory: (2 x 128 + 32) B x chunk, plus the table of mode 1 (2 KiB x chunk), whatever the transcript's size.
+//     Device memory: (2 x 128 + 32) B x chunk, plus the window table (2 KiB x chunk), whatever the transcript's size.
 //
 //   wsnark_powers_check: the point tests are the key audit's own kernels (pkeycheck.hip: pkcheck_g1_dev, pkcheck_g2_dev -- the
 //     latter with the order-r subgroup test, for tau_g2); the relations are random-combination sums with the audit's rho (ChaCha20,
@@ -49,7 +46,7 @@ namespace wsnark {
 using namespace hostpair;
 
 // ---- device ----
-constexpr int PW_WIN = 4;                       // window width of mode 1
+constexpr int PW_WIN = 4;                       // window width
 constexpr int PW_TAB = 1 << (PW_WIN - 1);       // table entries: 1P .. 8P
 constexpr int PW_NWIN = 256 / PW_WIN;           // windows over the 256 bits of a scalar word string
 static_assert((FrParams::P3 >> 60) + 1 <= (uint64_t)PW_TAB, "the top window of a scalar below r must absorb the carry into it");
@@ -62,7 +59,7 @@ __device__ __forceinline__ void pw_digit(const Fe& k, uint64_t carries, int j, u
     *mag = v > (unsigned)PW_TAB ? 16 - v : v;
 }
 
-template <class C, int MODE>
+template <class C>
 __global__ __launch_bounds__(256) void mul_points_kernel(const typename C::AffP* __restrict__ pts, const Fe* __restrict__ scalars, uint64_t n,
                                                            uint64_t base, typename C::El curve_b, typename C::AffP* __restrict__ out,
                                                            typename C::PtP* __restrict__ table, uint64_t lanes, PkAcc* __restrict__ acc) {
@@ -82,59 +79,42 @@ __global__ __launch_bounds__(256) void mul_points_kernel(const typename C::AffP*
     pk_reduce(st, base + i, acc);
 
     Pt a = C::infinity();
-    if (MODE == 0) {
-        // scale_points_kernel's chain on the lane's own digits.  The leading digit is +1: a starts as P itself; every later addition
-        // is the guarded C::madd (pkeydelta.hip has the argument: a == +/-P for scalars next to r, and anywhere for a G2 point
-        // outside the subgroup).
-        if (live) {
-            ScaleDigits D;
-            naf_digits(k, &D);
-            const uint64_t z0 = D.nz[0], z1 = D.nz[1], z2 = D.nz[2], z3 = D.nz[3], g0 = D.neg[0], g1 = D.neg[1], g2 = D.neg[2], g3 = D.neg[3];
-            a = Pt{P.x, P.y, F::one(), F::one()};
+    if (live) {
+        // bit j of `carries`: the carry INTO window j (none leaves window 63: the static_assert above)
+        uint64_t carries = 0;
+        unsigned c = 0;
 #pragma unroll 1
-            for (int d = D.top - 1; d >= 0; d--) {
-                a = C::dbl(a);
-                if ((word4(z0, z1, z2, z3, d >> 6) >> (d & 63)) & 1) C::madd(a, P, ((word4(g0, g1, g2, g3, d >> 6) >> (d & 63)) & 1) != 0);
-            }
+        for (int j = 0; j < PW_NWIN - 1; j++) {
+            const uint64_t word = word4(k.l[0], k.l[1], k.l[2], k.l[3], j >> 4);
+            c = ((unsigned)((word >> ((j & 15) * PW_WIN)) & 15) + c) > (unsigned)PW_TAB ? 1u : 0u;
+            carries |= (uint64_t)c << (j + 1);
         }
-    } else {
-        if (live) {
-            // bit j of `carries`: the carry INTO window j (none leaves window 63: the static_assert above)
-            uint64_t carries = 0;
-            unsigned c = 0;
+        // the table e P, e = 1 .. 8, row e - 1 of [entry][lane]; guarded additions: 2P = -P (order 3) and its like are legal on G2
+        Pt T = Pt{P.x, P.y, F::one(), F::one()};
+        table[i] = C::pack_pt(T);
+        T = C::dbl_affine(P.x, P.y);
+        table[lanes + i] = C::pack_pt(T);
 #pragma unroll 1
-            for (int j = 0; j < PW_NWIN - 1; j++) {
-                const uint64_t word = word4(k.l[0], k.l[1], k.l[2], k.l[3], j >> 4);
-                c = ((unsigned)((word >> ((j & 15) * PW_WIN)) & 15) + c) > (unsigned)PW_TAB ? 1u : 0u;
-                carries |= (uint64_t)c << (j + 1);
+        for (int e = 2; e < PW_TAB; e++) {
+            C::madd(T, P, false);
+            table[(uint64_t)e * lanes + i] = C::pack_pt(T);
+        }
+        // the windows from the top: the first one meets a == infinity and needs no doubling
+#pragma unroll 1
+        for (int j = PW_NWIN - 1; j >= 0; j--) {
+            unsigned mag;
+            bool neg;
+            pw_digit(k, carries, j, &mag, &neg);
+            if (j != PW_NWIN - 1) {
+                a = C::dbl(a);
+                a = C::dbl(a);
+                a = C::dbl(a);
+                a = C::dbl(a);
             }
-            // the table e P, e = 1 .. 8, row e - 1 of [entry][lane]; guarded additions: 2P = -P (order 3) and its like are legal on G2
-            Pt T = Pt{P.x, P.y, F::one(), F::one()};
-            table[i] = C::pack_pt(T);
-            T = C::dbl_affine(P.x, P.y);
-            table[lanes + i] = C::pack_pt(T);
-#pragma unroll 1
-            for (int e = 2; e < PW_TAB; e++) {
-                C::madd(T, P, false);
-                table[(uint64_t)e * lanes + i] = C::pack_pt(T);
-            }
-            // the windows from the top: the first one meets a == infinity and needs no doubling
-#pragma unroll 1
-            for (int j = PW_NWIN - 1; j >= 0; j--) {
-                unsigned mag;
-                bool neg;
-                pw_digit(k, carries, j, &mag, &neg);
-                if (j != PW_NWIN - 1) {
-                    a = C::dbl(a);
-                    a = C::dbl(a);
-                    a = C::dbl(a);
-                    a = C::dbl(a);
-                }
-                if (mag != 0) {      // (a zero window adds nothing)
-                    Pt E = C::unpack_pt(table[(uint64_t)(mag - 1) * lanes + i]);
-                    E.y = F::cneg(E.y, neg);
-                    a = C::add(a, E);
-                }
+            if (mag != 0) {      // (a zero window adds nothing)
+                Pt E = C::unpack_pt(table[(uint64_t)(mag - 1) * lanes + i]);
+                E.y = F::cneg(E.y, neg);
+                a = C::add(a, E);
             }
         }
     }
@@ -142,13 +122,7 @@ __global__ __launch_bounds__(256) void mul_points_kernel(const typename C::AffP*
 
     // one inversion per workgroup (blockDim.x == 256): every lane arrives, a lane with nothing to normalise passes 1
     const El inv = block_inverse<F>(fin ? F::mul(a.zz, a.zzz) : F::one());
-    if (i < n) {
-        typename C::AffP r;
-        if (st == 4) r = pts[i];                                 // infinity: copied through byte for byte
-        else if (!fin) memset(&r, 0, sizeof r);                  // k P = O (x == 0 encodes it), or a bad point (unspecified)
-        else r = typename C::AffP{F::from_internal(F::mul(a.x, F::mul(inv, a.zzz))), F::from_internal(F::mul(a.y, F::mul(inv, a.zz)))};
-        out[i] = r;
-    }
+    if (i < n) out[i] = st == 4 ? pts[i] : affine_result<C>(a, fin, inv, 1);      // infinity: copied through byte for byte
 }
 
 // out[i] = c t^(first + i), plain: the lane multiplies the t^(2^j) of the set bits of its GLOBAL index (< 2^25: tau_g1 has 2n <= 2^25 powers)
@@ -165,30 +139,19 @@ __global__ __launch_bounds__(256) void fr_powers_kernel(PowerBase W, uint64_t fi
 
 // ---- host ----
 namespace {
-// a wipe the compiler cannot drop: the stores are volatile
-void wipe(void* p, size_t n) {
-    volatile uint8_t* v = reinterpret_cast<volatile uint8_t*>(p);
-    for (size_t i = 0; i < n; i++) v[i] = 0;
-}
-inline int curve_b(G1R29::El* out) { return pk_curve_b(out, nullptr); }
-inline int curve_b(G2R29::El* out) { return pk_curve_b(nullptr, out); }
-
-// the shipped chain: DESIGN.md section "Powers of tau" has both
-int mul_mode() { return tuning_get("PWTAU_MUL", 1) == 0 ? 0 : 1; }
-
 // what a chunk in flight needs on the device; the scalars are overwritten when this goes (every exit path of a contribution)
 struct MulBufs {
     hipStream_t s = nullptr;
     DevBuf d_pts, d_out, d_sc, d_tab;
     uint64_t cap = 0;
     bool secret = false;
-    // cap points of at most point_bytes each; mode 1 needs the table: 8 XYZZ points per lane
-    int init(hipStream_t s_, uint64_t cap_, size_t point_bytes, int mode, bool secret_) {
+    // cap points of at most point_bytes each, and the window table: 8 XYZZ points per lane
+    int init(hipStream_t s_, uint64_t cap_, size_t point_bytes, bool secret_) {
         s = s_; cap = cap_; secret = secret_;
         WS_HIP_CHECK(d_pts.alloc((size_t)cap * point_bytes));
         WS_HIP_CHECK(d_out.alloc((size_t)cap * point_bytes));
         WS_HIP_CHECK(d_sc.alloc((size_t)cap * 32));
-        if (mode == 1) WS_HIP_CHECK(d_tab.alloc((size_t)cap * PW_TAB * 2 * point_bytes));
+        WS_HIP_CHECK(d_tab.alloc((size_t)cap * PW_TAB * 2 * point_bytes));
         return WS_OK;
     }
     ~MulBufs() {
@@ -200,23 +163,15 @@ struct MulBufs {
 
 // d_out[i] = d_sc[i] x d_pts[i], i < m; counts into d_acc under the global index base + i
 template <class C>
-int mul_launch(Context* X, MulBufs& B, uint64_t m, uint64_t base, int mode, PkAcc* d_acc) {
+int mul_launch(Context* X, MulBufs& B, uint64_t m, uint64_t base, PkAcc* d_acc) {
     typedef typename C::AffP AffP;
     typedef typename C::PtP PtP;
-    constexpr bool g1 = sizeof(AffP) == 64;
     typename C::El cb;
     const int rc = curve_b(&cb);
     if (rc) return rc;
-    const dim3 grid(ceil_div_u64(m, 256)), block(256);
-    if (mode == 0) {
-        X->timer.begin(g1 ? "mul_points_g1_naf" : "mul_points_g2_naf", B.s);
-        hipLaunchKernelGGL((mul_points_kernel<C, 0>), grid, block, 0, B.s, B.d_pts.as<AffP>(), B.d_sc.as<Fe>(), m, base, cb, B.d_out.as<AffP>(),
-                           (PtP*)nullptr, (uint64_t)0, d_acc);
-    } else {
-        X->timer.begin(g1 ? "mul_points_g1_win" : "mul_points_g2_win", B.s);
-        hipLaunchKernelGGL((mul_points_kernel<C, 1>), grid, block, 0, B.s, B.d_pts.as<AffP>(), B.d_sc.as<Fe>(), m, base, cb, B.d_out.as<AffP>(),
-                           B.d_tab.as<PtP>(), B.cap, d_acc);
-    }
+    X->timer.begin(sizeof(AffP) == 64 ? "mul_points_g1_win" : "mul_points_g2_win", B.s);
+    hipLaunchKernelGGL(mul_points_kernel<C>, dim3(ceil_div_u64(m, 256)), dim3(256), 0, B.s, B.d_pts.as<AffP>(), B.d_sc.as<Fe>(), m, base, cb,
+                       B.d_out.as<AffP>(), B.d_tab.as<PtP>(), B.cap, d_acc);
     WS_HIP_CHECK(hipGetLastError());
     X->timer.end(B.s);
     return WS_OK;
@@ -232,7 +187,6 @@ int mul_batch(const void* points, const void* scalars, uint64_t n, void* out) {
     if (n > ((uint64_t)1 << 24)) { set_last_error("mul_batch: n > 2^24"); return WS_ERR_SIZE; }
     const size_t psz = sizeof(AffP);
     const uint64_t chunk = key_chunk("PWTAU_CHUNK");
-    const int mode = mul_mode();
     // out stays untouched behind a bad point: one chunk is tested before it comes down; several come down into a host copy first
     std::vector<uint8_t> held;
     if (n > chunk) held.resize((size_t)n * psz);
@@ -247,12 +201,12 @@ int mul_batch(const void* points, const void* scalars, uint64_t n, void* out) {
         WS_HIP_CHECK(d_acc.alloc(sizeof(PkAcc)));
         WS_HIP_CHECK(hipMemsetAsync(d_acc.p, 0, sizeof(PkAcc), s));
         MulBufs B;
-        if ((rc = B.init(s, key_chunk_cap(chunk, n), psz, mode, false))) return rc;
+        if ((rc = B.init(s, key_chunk_cap(chunk, n), psz, false))) return rc;
         for (uint64_t lo = 0; lo < n; lo += chunk) {
             const uint64_t m = std::min<uint64_t>(chunk, n - lo);
             if ((rc = stage_chunk(B.d_pts.p, (const uint8_t*)points + lo * psz, (size_t)m * psz, s, nullptr))) return rc;
             if ((rc = stage_chunk(B.d_sc.p, (const uint8_t*)scalars + lo * 32, (size_t)m * 32, s, nullptr))) return rc;
-            if ((rc = mul_launch<C>(X, B, m, lo, mode, d_acc.as<PkAcc>()))) return rc;
+            if ((rc = mul_launch<C>(X, B, m, lo, d_acc.as<PkAcc>()))) return rc;
             WS_HIP_CHECK(hipMemcpyAsync(&h_acc, d_acc.p, sizeof h_acc, hipMemcpyDeviceToHost, s));
             WS_HIP_CHECK(hipStreamSynchronize(s));
             if (h_acc.bad) continue;      // (the later chunks are still counted: the message names the first index and the count)
@@ -304,11 +258,8 @@ int draw_secret(const uint8_t* caller32, const char* name, Fe* out) {
     uint8_t raw[32];
     int rc = draw_seed(caller32, raw);
     if (rc) return rc;
-    Fe k;
-    memcpy(&k, raw, 32);
-    *out = Fr::reduce_full(k);
+    *out = load_scalar(raw);
     wipe(raw, sizeof raw);
-    wipe(&k, sizeof k);
     if (Fr::is_zero(*out)) { set_last_error(std::string("powers contribution: ") + name + " = 0 mod r"); return WS_ERR_ARG; }
     return WS_OK;
 }
@@ -335,19 +286,15 @@ int g1_mul_dev(Context* X, const void* d_pts, const Fe* d_scalars, uint64_t n, v
     if (rc) return rc;
     // PWTAU_CHUNK points per launch: the table of the windowed chain is sized by the chunk, not by the array
     const uint64_t chunk = key_chunk("PWTAU_CHUNK"), cap = key_chunk_cap(chunk, n);
-    const int mode = mul_mode();
     DevBuf d_tab;
-    if (mode == 1) WS_HIP_CHECK(d_tab.alloc((size_t)cap * PW_TAB * sizeof(C::PtP)));
+    WS_HIP_CHECK(d_tab.alloc((size_t)cap * PW_TAB * sizeof(C::PtP)));
     const C::AffP* in = (const C::AffP*)d_pts;
     C::AffP* out = (C::AffP*)d_out;
     for (uint64_t lo = 0; lo < n; lo += chunk) {
         const uint64_t m = std::min<uint64_t>(chunk, n - lo);
-        const dim3 grid(ceil_div_u64(m, 256)), block(256);
-        X->timer.begin(mode == 0 ? "mul_points_g1_naf" : "mul_points_g1_win", s);
-        if (mode == 0)
-            hipLaunchKernelGGL((mul_points_kernel<C, 0>), grid, block, 0, s, in + lo, d_scalars + lo, m, lo, cb, out + lo, (C::PtP*)nullptr, (uint64_t)0, d_acc);
-        else
-            hipLaunchKernelGGL((mul_points_kernel<C, 1>), grid, block, 0, s, in + lo, d_scalars + lo, m, lo, cb, out + lo, d_tab.as<C::PtP>(), cap, d_acc);
+        X->timer.begin("mul_points_g1_win", s);
+        hipLaunchKernelGGL(mul_points_kernel<C>, dim3(ceil_div_u64(m, 256)), dim3(256), 0, s, in + lo, d_scalars + lo, m, lo, cb, out + lo,
+                           d_tab.as<C::PtP>(), cap, d_acc);
         WS_HIP_CHECK(hipGetLastError());
         X->timer.end(s);
     }
@@ -398,14 +345,13 @@ int powers_contribute(const wsnark_powers_t* P, const uint8_t* tau32, const uint
     if (!R.beta2_reason) {
         t0 = Clock::now();
         const uint64_t chunk = key_chunk("PWTAU_CHUNK");
-        const int mode = mul_mode();
         LaneLock L = acquire_lane(X);
         hipStream_t s = L->stream;
         DevBuf d_acc;
         WS_HIP_CHECK(d_acc.alloc(sizeof h_acc));
         WS_HIP_CHECK(hipMemsetAsync(d_acc.p, 0, sizeof h_acc, s));
         MulBufs B;
-        if ((rc = B.init(s, key_chunk_cap(chunk, A[WSNARK_PW_TAU_G1].count), 128, mode, true))) return rc;
+        if ((rc = B.init(s, key_chunk_cap(chunk, A[WSNARK_PW_TAU_G1].count), 128, true))) return rc;
         for (int a = 0; a < 4; a++) {
             K.W.c = K.coef[a];
             for (uint64_t lo = 0; lo < A[a].count; lo += chunk) {
@@ -416,8 +362,8 @@ int powers_contribute(const wsnark_powers_t* P, const uint8_t* tau32, const uint
                 hipLaunchKernelGGL(fr_powers_kernel, dim3(ceil_div_u64(m, 256)), dim3(256), 0, s, K.W, lo, m, B.d_sc.as<Fe>());
                 WS_HIP_CHECK(hipGetLastError());
                 X->timer.end(s);
-                if (A[a].psz == 64) rc = mul_launch<G1R29>(X, B, m, lo, mode, d_acc.as<PkAcc>() + a);
-                else rc = mul_launch<G2R29>(X, B, m, lo, mode, d_acc.as<PkAcc>() + a);
+                if (A[a].psz == 64) rc = mul_launch<G1R29>(X, B, m, lo, d_acc.as<PkAcc>() + a);
+                else rc = mul_launch<G2R29>(X, B, m, lo, d_acc.as<PkAcc>() + a);
                 if (rc) return rc;
                 WS_HIP_CHECK(hipMemcpyAsync(out[a] + lo * A[a].psz, B.d_out.p, (size_t)m * A[a].psz, hipMemcpyDeviceToHost, s));
                 WS_HIP_CHECK(hipStreamSynchronize(s));
