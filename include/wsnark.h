@@ -684,6 +684,47 @@ int wsnark_zkey_export(const void* pkey, size_t len, const void* vk, size_t vk_l
 int wsnark_zkey_export_sections(const wsnark_key_sections_t* key, const void* vk, size_t vk_len, uint64_t n_inputs,
                                 void* out_zkey, size_t cap, size_t* out_len, wsnark_zkey_report_t* rep);
 int wsnark_zkey_export_size(uint32_t n_vars, uint32_t n_public, uint32_t domain, uint64_t nnzA, uint64_t nnzB, size_t* out_len);
+/* ---- a .zkey straight into a resident proving key (csrc/zkey.hip: zkey_load; the seam in csrc/prove.hip) ----
+ * prove(zkey, wtns) without the way through proving_key.bin: what wsnark_zkey_import followed by wsnark_pkey_load computes, with nothing
+ * of the key coming back to the host except the verification key.
+ *   handle       a whole-key wsnark_pkey_t (rank 0 of 1): every call that takes wsnark_pkey_load's handle takes this one with the same
+ *                results -- _info, _table_info, _wait_tables, _load_stats, _shard_info, wsnark_groth16_prove[_dev], _prove_batch[_dev],
+ *                wsnark_pkey_eval_ab_dev, _prove_partial*, _prove_finish, wsnark_pkey_free.  The tables are built in the background as
+ *                for any load; WSNARK_KEY_TABLE, _TABLE_MAX_GB and _TABLE_ASYNC apply.  _load_stats: [0] the coefficients, [1] parse +
+ *                upload, [2] masks + conversion, [3] the table build, [4] the call from the first allocation on.
+ *   points       sections 5 - 8 go through the staging ring into row 0 of the handle's tables (C behind its nPublic + 1 infinities);
+ *                section 9 into H's, where the basis change above runs in place (N -> hExps), its scratch freed before the call returns.
+ *   coefficients the 44-byte records go up as they are.  The import's count / test and STABLE partition by matrix run on them, with the
+ *                value kept as the file stores it, c R^2 mod r -- what the resident matrices hold (a value >= r is reduced and counted,
+ *                no Montgomery factor is taken off).  A matrix's partition then IS col[] (the signal) and coef[] of the prover's
+ *                row-major CSR: snarkjs writes the records by ascending constraint.  Where a matrix's records are not non-decreasing in
+ *                constraint the import's stable radix passes over the constraint bits run first.  row_ptr[k], k = 0 .. domainSize, is
+ *                the number of records with constraint < k: one lane per k, a binary search, plain stores.  No order comes from an
+ *                atomic: inside a row the entries are in file order.  Rows without records, a matrix without records and nCoeffs = 0
+ *                give valid matrices.
+ *   out_vk       wsnark_groth16_verify's layout, as wsnark_zkey_import writes it; NULL with vk_cap == 0: not wanted.  Its length,
+ *                448 + 64 (nPublic + 1), comes from wsnark_zkey_vk_len / _vk_len_file: host only, no wsnark_init, read from the container
+ *                and section 2 ALONE -- wsnark_zkey_info gives it too, but counts section 4's records on the host, which would fault
+ *                the largest section of a mapped file into the process.  Their errors are the container's, with the texts above.
+ *   rep          wsnark_zkey_report_t as on import, or NULL; ms: parse + upload, coefficients, H basis, 0 (nothing is downloaded), the
+ *                whole call up to "proofs may start".
+ *   errors       wsnark_zkey_import's, codes and texts, the "zkey import:" prefix of two of them included (the container, the sizes, matrix > 1, signal >= nVars and constraint >=
+ *                domainSize with the record, a bad H point with its index); WSNARK_ERR_SIZE: a domainSize that is no power of two in
+ *                [2, 2^24], vk_cap too small; WSNARK_ERR_ARG: a file that cannot be opened, zkey / path / out_handle NULL;
+ *                WSNARK_ERR_NOINIT before wsnark_init.  On every error *out_handle, out_vk and rep are untouched and nothing stays
+ *                allocated.
+ *   _file        the file is mapped read-only; the sections are found by type, in any order, unknown types skipped; every range is
+ *                staged in pieces (WSNARK_POLS_PIECE_KB) and handed back to the kernel piece by piece, so the process never holds the
+ *                key: keys past 4 GiB, up to domainSize 2^24.  An empty or too short file is the container's "truncated file".
+ *   NOT audited  as on import: sections 3 and 5 - 8 and the fixed points are taken as they are (wsnark_pkey_check on imported bytes is
+ *                the audit); H gets the two cheap tests of its basis change.  The .zkey reading has still not met a file written by
+ *                snarkjs: the model file of the tests follows README.md's "zkey" section.  Out of scope: shards, groups (multi-GPU). */
+int wsnark_pkey_load_zkey(const void* zkey, size_t len, wsnark_pkey_t** out_handle,
+                          void* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep);
+int wsnark_pkey_load_zkey_file(const char* path, wsnark_pkey_t** out_handle,
+                               void* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep);
+int wsnark_zkey_vk_len(const void* zkey, size_t len, size_t* out_len);
+int wsnark_zkey_vk_len_file(const char* path, size_t* out_len);
 /* ---- powers of tau: contribute to a transcript, audit one (csrc/pwtau.hip; snarkjs: `powersoftau contribute` / `powersoftau verify`) ----
  * Phase 1 itself: the transcript wsnark_pkey_setup builds a key on.  A contribution by secrets t, a, b (non-zero mod r) turns the
  * transcript of (tau, alpha, beta) into the one of (t tau, a alpha, b beta):

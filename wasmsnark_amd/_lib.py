@@ -21,7 +21,7 @@ SYMBOLS = [
     "wsnark_fr_ntt", "wsnark_fr_ntt_dev", "wsnark_fr_ntt_batch_dev", "wsnark_fr_dist_scale_dev",
     "wsnark_pkey_eval_ab_dev", "wsnark_fr_mul_dev", "wsnark_fr_dist_combine_dev", "wsnark_fr_to_montgomery", "wsnark_fr_from_montgomery",
     "wsnark_calc_h", "wsnark_pkey_load", "wsnark_pkey_free", "wsnark_pkey_info", "wsnark_pkey_table_info",
-    "wsnark_groth16_prove", "wsnark_groth16_prove_dev", "wsnark_groth16_prove_batch", "wsnark_groth16_prove_batch_dev", "wsnark_pkey_load_sections", "wsnark_pkey_load_shard", "wsnark_pkey_load_file", "wsnark_pkey_file_info", "wsnark_pkey_check", "wsnark_pkey_check_sections", "wsnark_pkey_check_file", "wsnark_g1_scale_batch", "wsnark_g2_scale_batch", "wsnark_pkey_contribute", "wsnark_pkey_contribute_sections", "wsnark_pkey_contribute_file", "wsnark_pkey_delta_verify", "wsnark_pkey_delta_verify_sections", "wsnark_pkey_delta_verify_file", "wsnark_g1_ntt", "wsnark_g2_ntt", "wsnark_pkey_setup", "wsnark_pkey_setup_pkey", "wsnark_pkey_setup_size", "wsnark_g1_mul_batch", "wsnark_g2_mul_batch", "wsnark_powers_contribute", "wsnark_powers_check", "wsnark_pkey_circuit_check", "wsnark_pkey_circuit_check_sections", "wsnark_pkey_circuit_check_file", "wsnark_circuit_row_sums", "wsnark_circuit_load", "wsnark_circuit_free", "wsnark_circuit_info", "wsnark_witness_check", "wsnark_circuit_witness_check", "wsnark_circuit_witness_check_dev", "wsnark_circuit_witness_check_batch", "wsnark_circuit_witness_check_batch_dev", "wsnark_circuit_from_rows_size", "wsnark_circuit_from_rows", "wsnark_circuit_load_rows", "wsnark_g1_h_basis", "wsnark_zkey_info", "wsnark_zkey_import", "wsnark_zkey_import_sections", "wsnark_zkey_export", "wsnark_zkey_export_sections", "wsnark_zkey_export_size", "wsnark_pkey_shard_info", "wsnark_pkey_load_stats", "wsnark_pkey_wait_tables", "wsnark_pkey_h_msm_dev", "wsnark_last_blinding", "wsnark_groth16_verify", "wsnark_groth16_verify_batch", "wsnark_groth16_verify_batch_dev",
+    "wsnark_groth16_prove", "wsnark_groth16_prove_dev", "wsnark_groth16_prove_batch", "wsnark_groth16_prove_batch_dev", "wsnark_pkey_load_sections", "wsnark_pkey_load_shard", "wsnark_pkey_load_file", "wsnark_pkey_file_info", "wsnark_pkey_check", "wsnark_pkey_check_sections", "wsnark_pkey_check_file", "wsnark_g1_scale_batch", "wsnark_g2_scale_batch", "wsnark_pkey_contribute", "wsnark_pkey_contribute_sections", "wsnark_pkey_contribute_file", "wsnark_pkey_delta_verify", "wsnark_pkey_delta_verify_sections", "wsnark_pkey_delta_verify_file", "wsnark_g1_ntt", "wsnark_g2_ntt", "wsnark_pkey_setup", "wsnark_pkey_setup_pkey", "wsnark_pkey_setup_size", "wsnark_g1_mul_batch", "wsnark_g2_mul_batch", "wsnark_powers_contribute", "wsnark_powers_check", "wsnark_pkey_circuit_check", "wsnark_pkey_circuit_check_sections", "wsnark_pkey_circuit_check_file", "wsnark_circuit_row_sums", "wsnark_circuit_load", "wsnark_circuit_free", "wsnark_circuit_info", "wsnark_witness_check", "wsnark_circuit_witness_check", "wsnark_circuit_witness_check_dev", "wsnark_circuit_witness_check_batch", "wsnark_circuit_witness_check_batch_dev", "wsnark_circuit_from_rows_size", "wsnark_circuit_from_rows", "wsnark_circuit_load_rows", "wsnark_g1_h_basis", "wsnark_zkey_info", "wsnark_zkey_import", "wsnark_zkey_import_sections", "wsnark_zkey_export", "wsnark_zkey_export_sections", "wsnark_zkey_export_size", "wsnark_pkey_load_zkey", "wsnark_pkey_load_zkey_file", "wsnark_zkey_vk_len", "wsnark_zkey_vk_len_file", "wsnark_pkey_shard_info", "wsnark_pkey_load_stats", "wsnark_pkey_wait_tables", "wsnark_pkey_h_msm_dev", "wsnark_last_blinding", "wsnark_groth16_verify", "wsnark_groth16_verify_batch", "wsnark_groth16_verify_batch_dev",
     "wsnark_g1_compress", "wsnark_g2_compress", "wsnark_g1_decompress", "wsnark_g2_decompress", "wsnark_proof_compress", "wsnark_proof_decompress",
     "wsnark_groth16_verify_batch_compressed", "wsnark_groth16_verify_batch_compressed_dev",
     "wsnark_groth16_prove_partial", "wsnark_groth16_prove_partial_dev", "wsnark_groth16_prove_finish", "wsnark_groth16_prove_dist",
@@ -146,6 +146,10 @@ class Lib:
         c.wsnark_zkey_export.argtypes = [vp, sz, vp, sz, u64, vp, sz, C.POINTER(sz), vp]
         c.wsnark_zkey_export_sections.argtypes = [vp, vp, sz, u64, vp, sz, C.POINTER(sz), vp]
         c.wsnark_zkey_export_size.argtypes = [u32, u32, u32, u64, u64, C.POINTER(sz)]
+        c.wsnark_pkey_load_zkey.argtypes = [vp, sz, C.POINTER(vp), vp, sz, vp]
+        c.wsnark_pkey_load_zkey_file.argtypes = [C.c_char_p, C.POINTER(vp), vp, sz, vp]
+        c.wsnark_zkey_vk_len.argtypes = [vp, sz, C.POINTER(sz)]
+        c.wsnark_zkey_vk_len_file.argtypes = [C.c_char_p, C.POINTER(sz)]
         c.wsnark_group_pkey_load_file.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
         c.wsnark_pkey_shard_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
         c.wsnark_peak_probe.argtypes = [C.c_int, C.POINTER(C.c_double)]

@@ -569,8 +569,11 @@ def first_finding(report):
 class ProvingKey:
     """Device-resident proving key (wsnark_pkey_load, or wsnark_pkey_load_sections for `sections`)."""
 
-    def __init__(self, lib, data=None, sections=None, shard=None, h_interleave_log=0, wait_tables=True, path=None):
-        """path: a key FILE -- proving_key.bin or the WSNARK64 container for keys beyond 4 GiB (wsnark_pkey_load_file: mapped,
+    def __init__(self, lib, data=None, sections=None, shard=None, h_interleave_log=0, wait_tables=True, path=None, zkey=None, zkey_path=None,
+                 zkey_report=None):
+        """zkey / zkey_path: a snarkjs .zkey as bytes or as a file, straight into the resident key (wsnark_pkey_load_zkey[_file]; whole keys
+        only); the handle then carries `vk`, the file's verification key object, and zkey_report (a dict) receives the report.
+        path: a key FILE -- proving_key.bin or the WSNARK64 container for keys beyond 4 GiB (wsnark_pkey_load_file: mapped,
         only the share's pages are read); shard / h_interleave_log apply to it as to `sections`.
         shard=(rank, world) with `sections`: only that rank's share of the points becomes resident
         (wsnark_pkey_load_shard; h_interleave_log: the layout of its hExps share, see include/wsnark.h).
@@ -582,7 +585,12 @@ class ProvingKey:
         self._h = C.c_void_p()
         if shard is not None and sections is None and path is None:
             raise ValueError("a points shard is loaded from sections or from a key file")
-        if path is not None:
+        self.vk = None
+        if zkey is not None or zkey_path is not None:
+            if data is not None or sections is not None or path is not None or shard is not None:
+                raise ValueError("a .zkey is loaded as a whole key, and instead of data, sections or path")
+            self._load_zkey(lib, zkey, zkey_path, zkey_report)
+        elif path is not None:
             rank, world = shard if shard is not None else (0, 1)
             lib.check(lib.c.wsnark_pkey_load_file(os.fsencode(path), rank, world, h_interleave_log, C.byref(self._h)))
         elif sections is not None:
@@ -620,6 +628,26 @@ class ProvingKey:
         # which share of the points this handle holds (a whole key: rank 0 of 1, all nVars signals, all hExps)
         self.shard = {"rank": rk.value, "world": wd.value, "first_signal": lo.value, "n_signals": nl.value, "n_hexps": nh.value,
                       "h_interleave_log": hl.value}
+
+    def _load_zkey(self, lib, zkey, zkey_path, report):
+        if (zkey is None) == (zkey_path is None):
+            raise ValueError("exactly one of zkey, path")
+        # the verification key's length from the container and section 2 alone (wsnark_zkey_vk_len*): nothing here maps the file or
+        # walks its records -- the library maps a file itself and hands every range back as it is staged
+        vk_len, rep = C.c_size_t(), _ZkeyReport()
+        if zkey_path is not None:
+            fs_path = os.fsencode(zkey_path)
+            lib.check(lib.c.wsnark_zkey_vk_len_file(fs_path, C.byref(vk_len)))
+            vk = (C.c_uint8 * vk_len.value)()
+            lib.check(lib.c.wsnark_pkey_load_zkey_file(fs_path, C.byref(self._h), vk, len(vk), C.byref(rep)))
+        else:
+            ptr, n = _ro(zkey)
+            lib.check(lib.c.wsnark_zkey_vk_len(ptr, n, C.byref(vk_len)))
+            vk = (C.c_uint8 * vk_len.value)()
+            lib.check(lib.c.wsnark_pkey_load_zkey(ptr, n, C.byref(self._h), vk, len(vk), C.byref(rep)))
+        self.vk = vk_from_bytes(bytes(vk), (len(vk) - 448) // 64 - 1)
+        if report is not None:
+            report.update(_zkey_report_dict(rep))
 
     def wait_tables(self):
         """Block until the background build of the table rows is over (wsnark_pkey_wait_tables)."""
@@ -1448,6 +1476,30 @@ class Bn128:
                                  "one of this circuit")
         return key, vk_obj
 
+    def load_zkey(self, zkey=None, path=None, wait_tables=True, wtns=None, report=None):
+        """A snarkjs .zkey (bytes, or path=: the library maps the file and never holds it) straight into a resident key
+        (wsnark_pkey_load_zkey / _file): returns (ProvingKey, the verification key object).  What load_key(import_zkey(z)[0]) gives,
+        without the key's bytes ever existing on the host: the points go up once, H changes basis where it will stay, the coefficient
+        records become the prover's row-major matrices directly.  NOT audited, as import_zkey.  wait_tables: see ProvingKey.
+        wtns: .wtns bytes of a witness of the circuit -- the TRIAL PROOF of import_zkey on the new handle, verified against the
+        returned verification key; ValueError, with the handle freed, if it does not verify.  report: a dict that receives
+        {records, unreduced, zero: (A, B), sorted, H: {...}, ms} (ms["download"] is 0: nothing comes back)."""
+        key = ProvingKey(self.lib, zkey=zkey, zkey_path=path, wait_tables=wait_tables, zkey_report=report)
+        if wtns is not None:
+            try:
+                from .formats import wtns_to_witness_bin
+                wit = wtns_to_witness_bin(wtns)
+                proof = self.groth16GenProof(wit, key)
+                pub = [int.from_bytes(wit[32 * i:32 * i + 32], "little") for i in range(1, key.n_public + 1)]
+                if not self.groth16Verify(key.vk, pub, proof):
+                    raise ValueError("load_zkey: the trial proof of the given witness does not verify against the file's verification key "
+                                     "-- the file's coefficients or H section follow another convention than this reader's, or the "
+                                     "witness is not one of this circuit")
+            except Exception:
+                key.free()
+                raise
+        return key, key.vk
+
     def export_zkey(self, pkey=None, sections=None, vk=None, report=None):
         """A key of this library (proving_key.bin bytes, or sections=) and its verification key object as a snarkjs .zkey
         (wsnark_zkey_export / _export_sections): gamma2 and IC come from vk.  Section 10 holds no contributions and a zero circuit
@@ -1532,13 +1584,18 @@ class Bn128:
 
     # --- src/bn128.js:580-720 ---
     def groth16GenProof(self, signals, pkey, r=None, s=None, circuit=None):
-        """signals: witness.bin bytes; pkey: proving_key.bin bytes or a ProvingKey.
-        r, s: optional 32-byte blinding values (the reference draws them with
+        """signals: witness.bin bytes; pkey: proving_key.bin bytes, the bytes of a snarkjs .zkey (they begin with b"zkey"), or a
+        ProvingKey.  r, s: optional 32-byte blinding values (the reference draws them with
         crypto.randomBytes, src/bn128.js:642-661). Returns {pi_a, pi_b, pi_c} of decimal strings.
         circuit: a ResidentCircuit (load_circuit) whose nVars, nPublic and domain are the key's, else ValueError before anything
         runs.  The witness is checked against it first; one that breaks a constraint raises ValueError naming the first bad
         constraint with its a, b, c, and no proof is computed.  None: nothing is checked, as in the reference."""
-        key = pkey if isinstance(pkey, ProvingKey) else ProvingKey(self.lib, pkey)
+        if isinstance(pkey, ProvingKey):
+            key = pkey
+        elif bytes(pkey[:4]) == b"zkey":      # a snarkjs .zkey: straight into a resident key (load_zkey)
+            key = ProvingKey(self.lib, zkey=pkey)
+        else:
+            key = ProvingKey(self.lib, pkey)
         w, nw = _ro(signals)
         out = (C.c_uint8 * 384)()
         rb = _ro(r)[0] if r is not None else None

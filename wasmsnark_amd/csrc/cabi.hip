@@ -423,6 +423,25 @@ int wsnark_zkey_import_sections(const void* zkey, size_t len, void* const out[12
     if (!out || !caps) return WSNARK_ERR_ARG;
     return zkey_import((const uint8_t*)zkey, len, out, caps, nullptr, 0, nullptr, (uint8_t*)out_vk, vk_cap, rep);
 }
+// ... and straight into a resident key: the handle is wsnark_pkey_load's.  Nothing is written before the load has succeeded.
+int wsnark_pkey_load_zkey(const void* zkey, size_t len, wsnark_pkey_t** out_handle, void* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep) {
+    REQUIRE_CTX();
+    ProvingKey* K = nullptr;
+    int rc = zkey_load((const uint8_t*)zkey, len, nullptr, out_handle ? &K : nullptr, (uint8_t*)out_vk, vk_cap, rep);
+    if (rc) return rc;
+    *out_handle = reinterpret_cast<wsnark_pkey_t*>(K);
+    return WSNARK_OK;
+}
+int wsnark_pkey_load_zkey_file(const char* path, wsnark_pkey_t** out_handle, void* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep) {
+    REQUIRE_CTX();
+    ProvingKey* K = nullptr;
+    int rc = zkey_load_file(path, out_handle ? &K : nullptr, (uint8_t*)out_vk, vk_cap, rep);
+    if (rc) return rc;
+    *out_handle = reinterpret_cast<wsnark_pkey_t*>(K);
+    return WSNARK_OK;
+}
+int wsnark_zkey_vk_len(const void* zkey, size_t len, size_t* out_len) { return zkey_vk_len((const uint8_t*)zkey, len, out_len); }
+int wsnark_zkey_vk_len_file(const char* path, size_t* out_len) { return zkey_vk_len_file(path, out_len); }
 int wsnark_zkey_export(const void* pkey, size_t len, const void* vk, size_t vk_len, uint64_t n_inputs, void* out_zkey, size_t cap,
                        size_t* out_len, wsnark_zkey_report_t* rep) {
     REQUIRE_CTX();

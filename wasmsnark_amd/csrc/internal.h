@@ -1,6 +1,7 @@
 // internal.h -- C++ interfaces between the translation units of libwsnark.
 #pragma once
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <map>
@@ -414,7 +415,26 @@ struct KeyFile {
     ~KeyFile();
 };
 int keyfile_open(const char* path, KeyFile* F, KeySections* S);      // maps the file read-only, bounds-checks the header; S points into the map
+int keyfile_map(const char* path, KeyFile* F, size_t min_len);        // the mapping alone, of a file of at least min_len bytes (zkey.hip: a .zkey file); an empty file: base null, len 0
+void keyfile_release(const void* p, size_t n);                        // hands the whole pages inside [p, p + n) of a mapping back (KeySections::release)
 int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard);      // on the calling thread's context
+// The halves of a load around "sections resident" (prove.hip), shared by pkey_load_sections and the loader of a .zkey (zkey.hip).
+// The load's clock: lap() drains queue s and gives the ms since the last lap (a fault of the drained work is noted in lap_failed).
+struct KeyLoadClock {
+    typedef std::chrono::steady_clock Clock;
+    hipStream_t s = nullptr;
+    Clock::time_point t_begin, t_phase;
+    bool lap_failed = false, trace = false;      // trace: WSNARK_TRACE=1
+    double lap();
+    double since() const;                        // ms since the load began
+};
+// begin: the rank's share, which sections become tables, the five buffers allocated (rows x section); starts the clock on queue s.
+// The caller then makes row 0 of every buffer resident in reference format (C padded in front: prove.hip) and fills in the fixed points.
+// convert: the infinity masks and the conversion to the device field's domain (load_ms[2]).  The caller then builds polsA / polsB.
+// finish: the last drain (load_ms[0]), the table build on the context's build queue, load_ms[3] and [4].
+int pkey_load_begin(Context* C, ProvingKey* K, uint32_t nv, uint32_t np, uint32_t dom, KeyShard shard, hipStream_t s, KeyLoadClock* T);
+int pkey_load_convert(ProvingKey* K, KeyLoadClock* T);
+int pkey_load_finish(Context* C, ProvingKey* K, KeyLoadClock* T);
 void pkey_free(ProvingKey* K);
 int pkey_wait_tables(ProvingKey* K);
 Context* pkey_context(const ProvingKey* K);

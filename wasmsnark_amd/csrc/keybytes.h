@@ -389,6 +389,12 @@ int zkey_import(const uint8_t* zkey, size_t len, void* const out[12], const uint
                 uint8_t* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep);
 int zkey_export(const KeySections& S, const uint8_t* vk, size_t vk_len, uint64_t n_inputs, uint8_t* out, size_t cap, size_t* out_len,
                 wsnark_zkey_report_t* rep);
+// ... straight into a resident key (release: a mapped file's, see KeySections::release; out_vk and rep may be nullptr)
+int zkey_load(const uint8_t* zkey, size_t len, void (*release)(const void*, size_t), ProvingKey** out, uint8_t* out_vk, size_t vk_cap,
+              wsnark_zkey_report_t* rep);
+int zkey_load_file(const char* path, ProvingKey** out, uint8_t* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep);
+int zkey_vk_len(const uint8_t* zkey, size_t len, size_t* out_len);      // host only, from the container and section 2 alone
+int zkey_vk_len_file(const char* path, size_t* out_len);
 int zkey_export_size(uint32_t n_vars, uint32_t n_public, uint32_t domain, uint64_t nnzA, uint64_t nnzB, size_t* out_len);
 
 }  // namespace wsnark

@@ -38,7 +38,7 @@ KeyFile::~KeyFile() {
 }
 
 // hand the whole pages inside [p, p + n) back (the partial pages at either end may still be needed by a neighbouring range)
-static void release_pages(const void* p, size_t n) {
+void keyfile_release(const void* p, size_t n) {
     const uintptr_t pg = (uintptr_t)sysconf(_SC_PAGESIZE);
     const uintptr_t lo = ((uintptr_t)p + pg - 1) & ~(pg - 1), hi = ((uintptr_t)p + n) & ~(pg - 1);
     if (hi > lo) (void)madvise((void*)lo, hi - lo, MADV_DONTNEED);
@@ -70,16 +70,23 @@ static int parse_container(const uint8_t* b, size_t len, KeySections* S) {
     return WS_OK;
 }
 
-int keyfile_open(const char* path, KeyFile* F, KeySections* S) {
-    if (!path || !F || !S) return WS_ERR_ARG;
+int keyfile_map(const char* path, KeyFile* F, size_t min_len) {
+    if (!path || !F) return WS_ERR_ARG;
     F->fd = open(path, O_RDONLY | O_CLOEXEC);
     if (F->fd < 0) { set_last_error(std::string("key file: cannot open ") + path + ": " + strerror(errno)); return WS_ERR_ARG; }
     struct stat st;
-    if (fstat(F->fd, &st) != 0 || st.st_size < 8) { set_last_error(std::string("key file: cannot stat / too short: ") + path); return WS_ERR_FORMAT; }
+    if (fstat(F->fd, &st) != 0 || (uint64_t)st.st_size < min_len) { set_last_error(std::string("key file: cannot stat / too short: ") + path); return WS_ERR_FORMAT; }
     F->len = (size_t)st.st_size;
+    if (F->len == 0) return WS_OK;      // (nothing to map: base stays null)
     void* m = mmap(nullptr, F->len, PROT_READ, MAP_PRIVATE, F->fd, 0);
     if (m == MAP_FAILED) { set_last_error(std::string("key file: mmap failed: ") + strerror(errno)); return WS_ERR_HIP; }
     F->base = (const uint8_t*)m;
+    return WS_OK;
+}
+
+int keyfile_open(const char* path, KeyFile* F, KeySections* S) {
+    if (!path || !F || !S) return WS_ERR_ARG;
+    if (int rc = keyfile_map(path, F, 8)) return rc;
     int rc;
     if (memcmp(F->base, "WSNARK64", 8) == 0) {
         F->format = 2;
@@ -88,7 +95,7 @@ int keyfile_open(const char* path, KeyFile* F, KeySections* S) {
         F->format = 1;                                   // the reference's own file (its first word is nVars: never "WSNA")
         rc = pkey_parse(F->base, F->len, S);
     }
-    if (rc == WS_OK) S->release = release_pages;
+    if (rc == WS_OK) S->release = keyfile_release;
     return rc;
 }
 

@@ -59,13 +59,18 @@ int pkey_wait_tables(ProvingKey* K) {
 
 static bool range_ok(uint64_t off, uint64_t bytes, size_t len) { return off <= len && bytes <= len - off; }
 
-int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
-    Context* C = ctx();
-    if (!C) return WS_ERR_NOINIT;
-    const uint32_t nv = S.n_vars, np = S.n_public, dom = S.domain;
-    if (shard.world == 0 || shard.rank >= shard.world) return WS_ERR_ARG;
-    if (int bad = key_shape_check(S)) return bad;
-    std::unique_ptr<ProvingKey> K(new ProvingKey());
+// ---- the two halves of a load around "sections resident": pkey_load_sections below and the loader of a .zkey (zkey.hip) share them ----
+double KeyLoadClock::lap() {
+    if (hipStreamSynchronize(s) != hipSuccess) { lap_failed = true; (void)hipGetLastError(); }
+    const auto now = Clock::now();
+    const double ms = std::chrono::duration<double, std::milli>(now - t_phase).count();
+    t_phase = now;
+    return ms;
+}
+double KeyLoadClock::since() const { return std::chrono::duration<double, std::milli>(Clock::now() - t_begin).count(); }
+
+// the plan and the allocation: the rank's share, which sections become tables, the five buffers (rows x section)
+int pkey_load_begin(Context* C, ProvingKey* K, uint32_t nv, uint32_t np, uint32_t dom, KeyShard shard, hipStream_t s, KeyLoadClock* T) {
     K->owner = C;
     K->n_vars = nv; K->n_public = np; K->domain = dom;
     // the rank's share: floor(n / world) pairs per rank, the remainder to the last one (src/bn128.js:354-361)
@@ -87,14 +92,7 @@ int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
             K->h_local = dom / shard.world;
         }
     }
-    const uint32_t nl = K->n_local, hl = K->h_local, lo = K->lo;
-    memcpy(&K->alfa1, S.alfa1, 64);
-    memcpy(&K->beta1, S.beta1, 64);
-    memcpy(&K->delta1, S.delta1, 64);
-    memcpy(&K->beta2, S.beta2, 128);
-    memcpy(&K->delta2, S.delta2, 128);
-    hipStream_t s = C->stream;
-    size_t used = 0;
+    const uint32_t nl = K->n_local, hl = K->h_local;
     // Which sections become fixed-base tables -- what the key's resident memory buys (the sweep: profiles/r05_table_sweep.txt):
     // WSNARK_KEY_TABLE=1 (default) all five, 0 none (plain sections), 2 the hExps only, 3 A / B1 / B2 / C only.  Tables must fit:
     // at most WSNARK_TABLE_MAX_GB (default 160) and half of the memory that is free now.
@@ -113,37 +111,19 @@ int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
             }
         }
     }
-    typedef std::chrono::steady_clock Clock;
-    const auto t_begin = Clock::now();
-    bool lap_failed = false;                       // an asynchronous fault of the uploads / conversion kernels surfaces in these drains
-    auto lap = [&](Clock::time_point& from) {      // ms since `from`, after the queue has drained; `from` moves on
-        if (hipStreamSynchronize(s) != hipSuccess) { lap_failed = true; (void)hipGetLastError(); }
-        const auto now = Clock::now();
-        const double ms = std::chrono::duration<double, std::milli>(now - from).count();
-        from = now;
-        return ms;
-    };
-    auto t_phase = t_begin;
-    int rc;
-    // the rank's slice of every section.  C holds points for signals nPublic+1.. only (src/bn128.js:620 slices the scalars
-    // instead).  Resident copy: padded in front with infinities (x == 0) for the signals 0..nPublic, so that the C sum uses
-    // the SAME scalar vector -- and the same digit/sort plan -- as A, B1 and B2: local index i = signal lo + i everywhere.
-    const uint64_t c_front = lo < np + 1 ? std::min<uint64_t>(nl, (uint64_t)np + 1 - lo) : 0;      // leading infinities of the local C array
-    const uint64_t c_first = (lo > np + 1 ? lo - (np + 1) : 0);                                     // first C point of the file that is mine
-    struct Sec { DevBuf* d; const uint8_t* src; uint64_t bytes, row_bytes, rows; } secs[5] = {
-        {&K->pointsA, S.A + (uint64_t)lo * 64, (uint64_t)nl * 64, (uint64_t)nl * 64, 0},
-        {&K->pointsB1, S.B1 + (uint64_t)lo * 64, (uint64_t)nl * 64, (uint64_t)nl * 64, 0},
-        {&K->pointsB2, S.B2 + (uint64_t)lo * 128, (uint64_t)nl * 128, (uint64_t)nl * 128, 0},
-        {&K->pointsC, S.Cpts + c_first * 64, ((uint64_t)nl - c_front) * 64, (uint64_t)nl * 64, 0},
-        {&K->pointsH, S.H + (uint64_t)K->hlo * 64, (uint64_t)hl * 64, (uint64_t)hl * 64, 0}};
+    T->s = s;
+    T->t_begin = T->t_phase = KeyLoadClock::Clock::now();
+    T->trace = tuning_get("TRACE", 0) == 1;
     // the five buffers: rows x section.  Should the device refuse a table after all (fragmentation, another process), the
     // key falls back to plain sections instead of failing
+    struct Sec { DevBuf* d; uint64_t row_bytes; } secs[5] = {{&K->pointsA, (uint64_t)nl * 64}, {&K->pointsB1, (uint64_t)nl * 64},
+        {&K->pointsB2, (uint64_t)nl * 128}, {&K->pointsC, (uint64_t)nl * 64}, {&K->pointsH, (uint64_t)hl * 64}};
     for (int attempt = 0; attempt < 2; attempt++) {
         const uint64_t rowsW = msm_table_rows(K->table_cw), rowsH = msm_table_rows(K->table_ch);
         hipError_t err = hipSuccess;
         for (auto& sc : secs) {
-            sc.rows = sc.d == &K->pointsH ? rowsH : rowsW;
-            if ((err = sc.d->alloc((size_t)std::max<uint64_t>(sc.row_bytes * sc.rows, 64))) != hipSuccess) break;
+            const uint64_t rows = sc.d == &K->pointsH ? rowsH : rowsW;
+            if ((err = sc.d->alloc((size_t)std::max<uint64_t>(sc.row_bytes * rows, 64))) != hipSuccess) break;
         }
         if (err == hipSuccess) break;
         (void)hipGetLastError();
@@ -151,32 +131,15 @@ int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
         for (auto& sc : secs) sc.d->release();
         K->table_cw = K->table_ch = 0;
     }
-    const bool trace_load = tuning_get("TRACE", 0) == 1;
-    auto since = [&](Clock::time_point from) { return std::chrono::duration<double, std::milli>(Clock::now() - from).count(); };
-    if (trace_load) fprintf(stderr, "[wsnark trace] key load: device buffers allocated at %.2f ms\n", since(t_begin));
-    std::vector<uint8_t> h_gather;
-    if (K->h_log_m) {
-        // the rank's rows of the m-interleaved layout, row-major (m / world) x (domain / m): local (r, j) = hExps[(rank m/world + r) + m j]
-        const uint64_t m = (uint64_t)1 << K->h_log_m, per = m / shard.world, cols = dom / m;
-        h_gather.resize((size_t)hl * 64);
-        for (uint64_t r = 0; r < per; r++)
-            for (uint64_t j = 0; j < cols; j++)
-                memcpy(&h_gather[(size_t)(r * cols + j) * 64], S.H + ((uint64_t)shard.rank * per + r + m * j) * 64, 64);
-        secs[4].src = h_gather.data();
-        if (S.release) S.release(S.H, (size_t)dom * 64);      // (the gather touched a 1 / world share of the section's pages)
-    }
-    for (auto& sc : secs) {
-        size_t front = 0;
-        if (sc.d == &K->pointsC && c_front) {
-            front = (size_t)c_front * 64;
-            WS_HIP_CHECK(hipMemsetAsync(sc.d->p, 0, front, s));
-        }
-        if (sc.bytes && (rc = upload_staged((uint8_t*)sc.d->p + front, sc.src, (size_t)sc.bytes, s))) return rc;
-        if (S.release && sc.bytes && sc.src != h_gather.data()) S.release(sc.src, (size_t)sc.bytes);
-        if (trace_load) fprintf(stderr, "[wsnark trace] key load: section of %llu bytes handed to the copy queue at %.2f ms\n", (unsigned long long)sc.bytes, since(t_begin));
-    }
-    K->load_ms[1] = lap(t_phase);
-    if (trace_load) fprintf(stderr, "[wsnark trace] key load: sections resident at %.2f ms\n", since(t_begin));
+    if (T->trace) fprintf(stderr, "[wsnark trace] key load: device buffers allocated at %.2f ms\n", T->since());
+    return WS_OK;
+}
+
+// everything after "sections resident", first half: the infinity masks and the conversion to the device field's domain
+int pkey_load_convert(ProvingKey* K, KeyLoadClock* T) {
+    hipStream_t s = T->s;
+    const uint32_t nl = K->n_local, hl = K->h_local;
+    int rc;
     // Variables that do not occur in matrix A (resp. B) have A (resp. B1 = B2) = infinity -- common: real circuits put
     // far fewer terms on the B side.  Their pairs cost a lane slot each in those sums, so when there are enough of
     // them the sums run on a plan VARIANT that leaves them out (msm_plan_variant: the per-bin sort and the task list
@@ -184,7 +147,7 @@ int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
     // WSNARK_PROVE_SPARSE: 0 never, 2 always.
     WS_HIP_CHECK(K->maskA.alloc((size_t)std::max<uint32_t>(nl, 1)));
     WS_HIP_CHECK(K->maskB.alloc((size_t)std::max<uint32_t>(nl, 1)));
-    if (trace_load) fprintf(stderr, "[wsnark trace] key load: mask buffers allocated at %.2f ms\n", since(t_begin));
+    if (T->trace) fprintf(stderr, "[wsnark trace] key load: mask buffers allocated at %.2f ms\n", T->since());
     if ((rc = msm_points_mask(K->pointsA.as<Affine<Fq>>(), nullptr, nl, K->maskA.as<uint8_t>(), &K->infA, s))) return rc;
     if ((rc = msm_points_mask(K->pointsB1.as<Affine<Fq>>(), K->pointsB2.as<Affine<Fq2>>(), nl, K->maskB.as<uint8_t>(), &K->infB, s))) return rc;
     {
@@ -193,45 +156,25 @@ int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
         K->sparseA = mode == 2 || (mode == 1 && big && (uint64_t)K->infA * 100 >= (uint64_t)nl * 15);   // saves a share of one G1 sum
         K->sparseB = mode == 2 || (mode == 1 && big && (uint64_t)K->infB * 100 >= (uint64_t)nl * 5);    // ... of a G1 and a G2 sum
     }
-    if (trace_load) fprintf(stderr, "[wsnark trace] key load: infinity masks taken at %.2f ms\n", since(t_begin));
+    if (T->trace) fprintf(stderr, "[wsnark trace] key load: infinity masks taken at %.2f ms\n", T->since());
     // resident keys are kept in the device field's internal domain: no per-proof conversion pass
     if ((rc = msm_prepare_points(0, K->pointsA.p, nl, s))) return rc;
     if ((rc = msm_prepare_points(0, K->pointsB1.p, nl, s))) return rc;
     if ((rc = msm_prepare_points(1, K->pointsB2.p, nl, s))) return rc;
     if ((rc = msm_prepare_points(0, K->pointsC.p, nl, s))) return rc;
     if ((rc = msm_prepare_points(0, K->pointsH.p, hl, s))) return rc;
-    K->load_ms[2] = lap(t_phase);
-    if (trace_load) fprintf(stderr, "[wsnark trace] key load: sections converted at %.2f ms\n", since(t_begin));
-    // The two record streams are transposed side by side (calch.hip: pols_to_csr -- a header walk on the host, upload, three kernels
-    // each, on queues of their own; round 3 did the two passes over the records on host threads: 56-65 ms of a 2^20 key's 214).
-    // BEFORE the table build is launched: under it the transposition's small kernels wait for issue slots behind kernels that
-    // use 0.95 of them (measured: 133 ms instead of 20), and the load must not return before the matrices are in.
-    {
-        hipStream_t sa = C->load_q[0], sb = C->load_q[1];       // (the context's: creating and destroying two queues per load cost milliseconds under ROCm 7.2)
-        size_t used_b = 0;
-        const int device = C->device;
-        std::string err_b;                      // (the error text is per thread: carried back by hand)
-        std::future<int> fb = std::async(std::launch::async, [&, device, sb]() {
-            // THIS context on the helper thread, not just its device (round 6): a new thread's selection is the process's DEFAULT
-            // context, so the records of matrix B went up through the default context's staging ring whatever context was loading --
-            // a group member's load left the default ring's slot events recorded on ITS queue, and once the group was gone the next
-            // upload through the default ring queried events whose queue had been destroyed (hipEventQuery dereferences the event's
-            // last queue: "operation not permitted on an event last recorded in a capturing stream", one GPU suite in five); on a
-            // real second GPU the record itself fails (an event of device 0 on a queue of device 1).
-            CtxScope helper_scope(C);
-            if (hipSetDevice(device) != hipSuccess) return (int)WS_ERR_HIP;
-            const int r = pols_to_csr(S.polsB, (size_t)S.lenB, nv, dom, &K->polsB, &used_b, sb, S.release);
-            if (r) err_b = get_last_error();
-            return r;
-        });
-        rc = pols_to_csr(S.polsA, (size_t)S.lenA, nv, dom, &K->polsA, &used, sa, S.release);
-        const int rcb = fb.get();
-        if (rc) return rc;                      // (~ProvingKey waits for the build queue)
-        if (rcb) { set_last_error(err_b); return rcb; }
-    }
-    K->load_ms[0] = lap(t_phase);               // (also drains `s`: sections resident and converted -- proofs may start)
-    if (lap_failed) { set_last_error("proving key: a HIP error surfaced while the sections were uploaded and converted"); return WS_ERR_HIP; }
-    if (trace_load) fprintf(stderr, "[wsnark trace] key load: matrices transposed at %.2f ms\n", since(t_begin));
+    K->load_ms[2] = T->lap();
+    if (T->trace) fprintf(stderr, "[wsnark trace] key load: sections converted at %.2f ms\n", T->since());
+    return WS_OK;
+}
+
+// ... second half, once the matrices are in: the last drain, the table build on the context's build queue, the statistics
+int pkey_load_finish(Context* C, ProvingKey* K, KeyLoadClock* T) {
+    const uint32_t nl = K->n_local, hl = K->h_local;
+    int rc;
+    K->load_ms[0] = T->lap();               // (also drains `s`: sections resident and converted -- proofs may start)
+    if (T->lap_failed) { set_last_error("proving key: a HIP error surfaced while the sections were uploaded and converted"); return WS_ERR_HIP; }
+    if (T->trace) fprintf(stderr, "[wsnark trace] key load: matrices transposed at %.2f ms\n", T->since());
     if (K->table_cw || K->table_ch) {
         // Rows 1.. of the tables, from row 0, in that domain: queued on the CONTEXT's build queue (lowest stream priority; `s` is
         // drained by the lap above), one key's build after the other, in short launches (a row per launch) through the context's
@@ -282,9 +225,93 @@ int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
             WS_HIP_CHECK(hipEventSynchronize(K->ev_tables));
             K->tables_ready.store(1);
         }
-        K->load_ms[3] = lap(t_phase);           // the table build, waited for
+        K->load_ms[3] = T->lap();           // the table build, waited for
     }
-    K->load_ms[4] = std::chrono::duration<double, std::milli>(Clock::now() - t_begin).count();
+    K->load_ms[4] = T->since();
+    return WS_OK;
+}
+
+int pkey_load_sections(const KeySections& S, ProvingKey** out, KeyShard shard) {
+    Context* C = ctx();
+    if (!C) return WS_ERR_NOINIT;
+    const uint32_t nv = S.n_vars, np = S.n_public, dom = S.domain;
+    if (shard.world == 0 || shard.rank >= shard.world) return WS_ERR_ARG;
+    if (int bad = key_shape_check(S)) return bad;
+    std::unique_ptr<ProvingKey> K(new ProvingKey());
+    hipStream_t s = C->stream;
+    KeyLoadClock T;
+    int rc;
+    if ((rc = pkey_load_begin(C, K.get(), nv, np, dom, shard, s, &T))) return rc;
+    const uint32_t nl = K->n_local, hl = K->h_local, lo = K->lo;
+    memcpy(&K->alfa1, S.alfa1, 64);
+    memcpy(&K->beta1, S.beta1, 64);
+    memcpy(&K->delta1, S.delta1, 64);
+    memcpy(&K->beta2, S.beta2, 128);
+    memcpy(&K->delta2, S.delta2, 128);
+    size_t used = 0;
+    // the rank's slice of every section.  C holds points for signals nPublic+1.. only (src/bn128.js:620 slices the scalars
+    // instead).  Resident copy: padded in front with infinities (x == 0) for the signals 0..nPublic, so that the C sum uses
+    // the SAME scalar vector -- and the same digit/sort plan -- as A, B1 and B2: local index i = signal lo + i everywhere.
+    const uint64_t c_front = lo < np + 1 ? std::min<uint64_t>(nl, (uint64_t)np + 1 - lo) : 0;      // leading infinities of the local C array
+    const uint64_t c_first = (lo > np + 1 ? lo - (np + 1) : 0);                                     // first C point of the file that is mine
+    struct Sec { DevBuf* d; const uint8_t* src; uint64_t bytes; } secs[5] = {
+        {&K->pointsA, S.A + (uint64_t)lo * 64, (uint64_t)nl * 64},
+        {&K->pointsB1, S.B1 + (uint64_t)lo * 64, (uint64_t)nl * 64},
+        {&K->pointsB2, S.B2 + (uint64_t)lo * 128, (uint64_t)nl * 128},
+        {&K->pointsC, S.Cpts + c_first * 64, ((uint64_t)nl - c_front) * 64},
+        {&K->pointsH, S.H + (uint64_t)K->hlo * 64, (uint64_t)hl * 64}};
+    std::vector<uint8_t> h_gather;
+    if (K->h_log_m) {
+        // the rank's rows of the m-interleaved layout, row-major (m / world) x (domain / m): local (r, j) = hExps[(rank m/world + r) + m j]
+        const uint64_t m = (uint64_t)1 << K->h_log_m, per = m / shard.world, cols = dom / m;
+        h_gather.resize((size_t)hl * 64);
+        for (uint64_t r = 0; r < per; r++)
+            for (uint64_t j = 0; j < cols; j++)
+                memcpy(&h_gather[(size_t)(r * cols + j) * 64], S.H + ((uint64_t)shard.rank * per + r + m * j) * 64, 64);
+        secs[4].src = h_gather.data();
+        if (S.release) S.release(S.H, (size_t)dom * 64);      // (the gather touched a 1 / world share of the section's pages)
+    }
+    for (auto& sc : secs) {
+        size_t front = 0;
+        if (sc.d == &K->pointsC && c_front) {
+            front = (size_t)c_front * 64;
+            WS_HIP_CHECK(hipMemsetAsync(sc.d->p, 0, front, s));
+        }
+        if (sc.bytes && (rc = upload_staged((uint8_t*)sc.d->p + front, sc.src, (size_t)sc.bytes, s))) return rc;
+        if (S.release && sc.bytes && sc.src != h_gather.data()) S.release(sc.src, (size_t)sc.bytes);
+        if (T.trace) fprintf(stderr, "[wsnark trace] key load: section of %llu bytes handed to the copy queue at %.2f ms\n", (unsigned long long)sc.bytes, T.since());
+    }
+    K->load_ms[1] = T.lap();
+    if (T.trace) fprintf(stderr, "[wsnark trace] key load: sections resident at %.2f ms\n", T.since());
+    if ((rc = pkey_load_convert(K.get(), &T))) return rc;
+    // The two record streams are transposed side by side (calch.hip: pols_to_csr -- a header walk on the host, upload, three kernels
+    // each, on queues of their own; round 3 did the two passes over the records on host threads: 56-65 ms of a 2^20 key's 214).
+    // BEFORE the table build is launched: under it the transposition's small kernels wait for issue slots behind kernels that
+    // use 0.95 of them (measured: 133 ms instead of 20), and the load must not return before the matrices are in.
+    {
+        hipStream_t sa = C->load_q[0], sb = C->load_q[1];       // (the context's: creating and destroying two queues per load cost milliseconds under ROCm 7.2)
+        size_t used_b = 0;
+        const int device = C->device;
+        std::string err_b;                      // (the error text is per thread: carried back by hand)
+        std::future<int> fb = std::async(std::launch::async, [&, device, sb]() {
+            // THIS context on the helper thread, not just its device (round 6): a new thread's selection is the process's DEFAULT
+            // context, so the records of matrix B went up through the default context's staging ring whatever context was loading --
+            // a group member's load left the default ring's slot events recorded on ITS queue, and once the group was gone the next
+            // upload through the default ring queried events whose queue had been destroyed (hipEventQuery dereferences the event's
+            // last queue: "operation not permitted on an event last recorded in a capturing stream", one GPU suite in five); on a
+            // real second GPU the record itself fails (an event of device 0 on a queue of device 1).
+            CtxScope helper_scope(C);
+            if (hipSetDevice(device) != hipSuccess) return (int)WS_ERR_HIP;
+            const int r = pols_to_csr(S.polsB, (size_t)S.lenB, nv, dom, &K->polsB, &used_b, sb, S.release);
+            if (r) err_b = get_last_error();
+            return r;
+        });
+        rc = pols_to_csr(S.polsA, (size_t)S.lenA, nv, dom, &K->polsA, &used, sa, S.release);
+        const int rcb = fb.get();
+        if (rc) return rc;                      // (~ProvingKey waits for the build queue)
+        if (rcb) { set_last_error(err_b); return rcb; }
+    }
+    if ((rc = pkey_load_finish(C, K.get(), &T))) return rc;
     *out = K.release();
     return WS_OK;
 }

@@ -1,5 +1,6 @@
-// zkey.hip -- snarkjs' .zkey in and out (wsnark_zkey_info, wsnark_zkey_import*, wsnark_zkey_export*) and the basis change of the H
-// section (wsnark_g1_h_basis); include/wsnark.h has the contracts, README.md section "zkey" the file format as this file reads it.
+// zkey.hip -- snarkjs' .zkey in and out (wsnark_zkey_info, wsnark_zkey_import*, wsnark_zkey_export*), straight into a resident proving
+// key (wsnark_pkey_load_zkey*: zkey_load at the end of this file) and the basis change of the H section (wsnark_g1_h_basis);
+// include/wsnark.h has the contracts, README.md section "zkey" the file format as this file reads it.
 //
 // A .zkey is no re-packing of proving_key.bin: two of its sections are in another form.
 //   H.  Section 9 holds N_i = (L^{2n}_{2i+1}(tau) / delta) G1, the odd Lagrange points of the doubled domain; CALC_H's sum
@@ -36,7 +37,8 @@ namespace wsnark {
 
 // ---- device ----
 // ~index of the smallest bad record per test (0 = none), the records >= r per matrix, and whether a matrix's constraints decrease
-struct ZkAcc { unsigned long long bad_matrix, bad_signal, bad_constraint, unreduced[2], unsorted[2]; };
+// (zero[]: the values that are 0 mod r, counted by the partition of the resident path alone -- the import's come from its emit)
+struct ZkAcc { unsigned long long bad_matrix, bad_signal, bad_constraint, unreduced[2], unsorted[2], zero[2]; };
 static constexpr uint32_t kRecWords = 11;      // u32 matrix, u32 constraint, u32 signal, 8 words of value
 
 __global__ __launch_bounds__(256) void zk_count_kernel(const uint32_t* __restrict__ rec, uint32_t n, uint32_t tile, uint32_t n_vars, uint32_t domain,
@@ -59,7 +61,10 @@ __global__ __launch_bounds__(256) void zk_count_kernel(const uint32_t* __restric
 }
 
 // base0[t]: matrix 0's records before tile t.  per_lane = tile / 256.  sig / row / coef: the two matrices' arrays, n0 and n - n0 long.
+// kKeep (the resident path, zkey_load): the value stays as the file has it, c R^2 -- what the prover's CSR holds (calch.hip) -- reduced
+// below r where it is not, and the zero values are counted here.
 struct ZkParts { uint32_t* sig[2]; uint32_t* row[2]; Fe* coef[2]; };
+template <bool kKeep>
 __global__ __launch_bounds__(256) void zk_partition_kernel(const uint32_t* __restrict__ rec, uint32_t n, uint32_t per_lane,
                                                            const uint32_t* __restrict__ base0, ZkParts out, ZkAcc* __restrict__ acc) {
     __shared__ uint32_t part[256];
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(256) void zk_partition_kernel(const uint32_t* __res
     const uint32_t b0 = base0[blockIdx.x];
     uint64_t p0 = (uint64_t)b0 + part[l] - zeros;                      // matrix 0: records before this lane's run
     uint64_t p1 = (tile0 - b0) + ((e0 - tile0) - (part[l] - zeros));   // matrix 1 (e0 >= tile0: a lane past the end has an empty run)
-    uint32_t big0 = 0, big1 = 0;
+    uint32_t big0 = 0, big1 = 0, zero0 = 0, zero1 = 0;
     for (uint64_t e = e0; e < e1; e++) {
         const uint32_t* w = rec + kRecWords * e;
         const bool m = (w[0] & 1) != 0;                                // (matrix > 1 fails the call before anything is read back)
@@ -92,10 +97,20 @@ __global__ __launch_bounds__(256) void zk_partition_kernel(const uint32_t* __res
         const uint64_t p = m ? p1++ : p0++;
         (m ? out.sig[1] : out.sig[0])[p] = w[2];
         (m ? out.row[1] : out.row[0])[p] = w[1];
-        (m ? out.coef[1] : out.coef[0])[p] = Fr::from_mont(Fr::from_mont(v));      // c R^2 -> c: canonical for any 256-bit value
+        if (kKeep) {
+            const Fe c = ge ? Fr::reduce_full(v) : v;                              // canonical for any 256-bit value (2^256 < 6 r)
+            const bool z = pk_zero(c);
+            zero0 += (!m && z) ? 1u : 0u;
+            zero1 += (m && z) ? 1u : 0u;
+            (m ? out.coef[1] : out.coef[0])[p] = c;
+        } else {
+            (m ? out.coef[1] : out.coef[0])[p] = Fr::from_mont(Fr::from_mont(v));      // c R^2 -> c: canonical for any 256-bit value
+        }
     }
     if (big0) atomicAdd(&acc->unreduced[0], (unsigned long long)big0);
     if (big1) atomicAdd(&acc->unreduced[1], (unsigned long long)big1);
+    if (kKeep && zero0) atomicAdd(&acc->zero[0], (unsigned long long)zero0);
+    if (kKeep && zero1) atomicAdd(&acc->zero[1], (unsigned long long)zero1);
 }
 
 __global__ __launch_bounds__(256) void zk_order_kernel(const uint32_t* __restrict__ row, uint32_t n, unsigned long long* __restrict__ unsorted) {
@@ -154,6 +169,26 @@ __global__ __launch_bounds__(256) void zk_emit_kernel(const uint32_t* __restrict
     __syncthreads();
     const uint32_t n_rec = n - p0 < 256 ? (uint32_t)(n - p0) : 256;
     for (uint32_t w = l; w < kRecWords * n_rec; w += 256) words[kRecWords * p0 + w] = rec[w];
+}
+
+// ---- the resident path (zkey_load): one matrix's records, non-decreasing in the constraint, as the prover's row-major CSR ----
+// row_ptr[k], k = 0 .. domain: the records with constraint < k.  One lane per k, a binary search in the constraints: every entry is
+// written by exactly one lane with a plain store, rows without records and a matrix without records (n = 0) included.
+__global__ __launch_bounds__(256) void zk_rowptr_kernel(const uint32_t* __restrict__ row, uint32_t n, uint32_t domain, uint32_t* __restrict__ row_ptr) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > domain) return;
+    uint32_t lo = 0, hi = n;                            // the first p with row[p] >= k
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (row[mid] < k) lo = mid + 1; else hi = mid; }
+    row_ptr[k] = lo;
+}
+// a matrix that had to be sorted: entry p of the result is entry val[p] of the partition's
+__global__ __launch_bounds__(256) void zk_gather_kernel(const uint32_t* __restrict__ val, uint32_t n, const uint32_t* __restrict__ sig_in,
+                                                        const Fe* __restrict__ coef_in, uint32_t* __restrict__ sig_out, Fe* __restrict__ coef_out) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t e = val[p];
+    sig_out[p] = sig_in[e];
+    coef_out[p] = coef_in[e];
 }
 
 // ---- host ----
@@ -278,8 +313,8 @@ struct HBufs {
     Fe* sc = nullptr;
     ScaleDigits* tw = nullptr;
     PkAcc* acc = nullptr;      // two, to be zeroed
-    void add(Slab& S, uint64_t n) {
-        S.add(&a, (size_t)n * 64);
+    void add(Slab& S, uint64_t n, bool with_a = true) {      // (without a: the caller's own buffer holds the input and takes the result)
+        if (with_a) S.add(&a, (size_t)n * 64);
         S.add(&b, (size_t)n * 64);
         S.add(&sc, (size_t)n * 32);
         S.add(&tw, (size_t)std::max<uint64_t>(n / 2, 1) * sizeof(ScaleDigits));
@@ -463,7 +498,7 @@ int zkey_import(const uint8_t* zkey, size_t len, void* const out[12], const uint
     if (nrec) {
         const ZkParts parts{{m_sig[0], m_sig[1]}, {m_row[0], m_row[1]}, {m_coef[0], m_coef[1]}};
         T.begin("zkey_partition", s);
-        hipLaunchKernelGGL(zk_partition_kernel, dim3(n_tiles), dim3(256), 0, s, rec, nrec, tile / 256, d_base, parts, acc);
+        hipLaunchKernelGGL(zk_partition_kernel<false>, dim3(n_tiles), dim3(256), 0, s, rec, nrec, tile / 256, d_base, parts, acc);
         WS_HIP_CHECK(hipGetLastError());
         T.end(s);
         T.begin("zkey_order", s);
@@ -694,6 +729,233 @@ int zkey_export(const KeySections& S, const uint8_t* vk, size_t vk_len, uint64_t
     R.ms[0] = ms_up; R.ms[1] = ms_coef; R.ms[2] = ms_h; R.ms[3] = ms_since(t_down); R.ms[4] = ms_since(t_call);
     *rep = R;
     return WS_OK;
+}
+
+// ---- a .zkey straight into a resident proving key (wsnark_pkey_load_zkey*) ----
+// What wsnark_zkey_import followed by wsnark_pkey_load computes, without the way through a key's bytes: nothing but the verification
+// key comes back to the host.
+//   points        sections 5 - 8 go through the staging ring into row 0 of the handle's buffers (C behind its nPublic + 1 infinities),
+//                 section 9 into H's, where the basis change runs in place: h_basis_dev leaves its result in its input buffer.
+//   coefficients  the records are counted, tested and partitioned as for the import, but the value stays c R^2 -- the prover's CSR
+//                 holds exactly that (calch.hip: csr_fill_kernel) -- and a matrix's partition IS col[] and coef[] once its constraints
+//                 are non-decreasing, which snarkjs' files are.  Where they are not, the import's stable sort by constraint runs and
+//                 zk_gather_kernel applies it.  row_ptr is zk_rowptr_kernel's.  No order comes from an atomic: the arrays are in file
+//                 order inside a row and the same for the same file.
+// Then prove.hip's second half of a load: masks, conversion, tables.  release (a mapped file): every range is staged in pieces and
+// handed back piece by piece, so the process never holds the file.
+namespace {
+int stage_pieces(void* d_dst, const uint8_t* src, size_t bytes, hipStream_t s, void (*release)(const void*, size_t)) {
+    const size_t piece = release ? std::max<size_t>((size_t)tuning_get("POLS_PIECE_KB", 32768) << 10, 4096) : std::max<size_t>(bytes, 1);
+    for (size_t at = 0; at < bytes; at += piece)
+        if (int rc = stage_chunk((uint8_t*)d_dst + at, src + at, std::min(piece, bytes - at), s, release)) return rc;
+    return WS_OK;
+}
+}  // namespace
+
+int zkey_load(const uint8_t* zkey, size_t len, void (*release)(const void*, size_t), ProvingKey** out, uint8_t* out_vk, size_t vk_cap,
+              wsnark_zkey_report_t* rep) {
+    Context* X = ctx();
+    if (!X) return WS_ERR_NOINIT;
+    const auto t_call = Clock::now();
+    if (!zkey || !out || (!out_vk && vk_cap)) return WS_ERR_ARG;
+    ZkFile F;
+    int rc;
+    if ((rc = zk_parse(zkey, len, &F))) return rc;
+    const uint64_t nv = F.n_vars, n = F.domain, nC = F.nC;
+    const uint32_t nrec = F.n_coeffs;
+    const int bits = log2_of(n);
+    if (out_vk && vk_cap < vk_len_of(F.n_public)) { set_last_error("zkey import: the capacity of the verification key is too small")      /* (the import's texts throughout) */; return WS_ERR_SIZE; }
+    uint32_t tile;
+    if ((rc = rows_tile(&tile))) return rc;
+    const uint32_t n_tiles = ceil_div_u64(std::max<uint32_t>(nrec, 1), tile);
+
+    LaneLock L = acquire_lane(X);
+    hipStream_t s = L->stream;
+    KernelTimer& T = X->timer;
+    std::unique_ptr<ProvingKey> K(new ProvingKey());
+    KeyLoadClock clock;
+    if ((rc = pkey_load_begin(X, K.get(), F.n_vars, F.n_public, F.domain, KeyShard{}, s, &clock))) return rc;
+    const uint8_t* fx = F.fixed();      // alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2
+    memcpy(&K->alfa1, fx, 64);
+    memcpy(&K->beta1, fx + 64, 64);
+    memcpy(&K->delta1, fx + 384, 64);
+    memcpy(&K->beta2, fx + 128, 128);
+    memcpy(&K->delta2, fx + 448, 128);
+
+    // 1. everything goes up once.  The temporaries in ONE allocation (the sort's only where a matrix needs them, below).
+    // Deliberately BEFORE the tests that only the device can make (signal, constraint, the H points): the allocation above is what
+    // decides between tables and plain sections, H changes basis inside its table, and the uploads are the small part of the call
+    // (20 ms of 264 at 2^20: profiles/zkey_load_bench.json).  A malformed file pays them before its error; the error path frees all of it.
+    uint32_t *d_rec, *d_cnt, *d_base, *d_cursor, *d_tiles, *d_row;
+    ZkAcc* acc;
+    HBufs H;
+    Slab slab;
+    slab.add(&d_rec, (size_t)nrec * 44);
+    slab.add(&d_cnt, ((size_t)n_tiles + 1) * 4);
+    slab.add(&d_base, ((size_t)n_tiles + 1) * 4);
+    slab.add(&d_cursor, ((size_t)n_tiles + 1) * 4);
+    slab.add(&d_tiles, (size_t)ceil_div_u64((uint64_t)n_tiles + 1, 1024) * 4);
+    slab.add(&acc, sizeof(ZkAcc));
+    slab.add(&d_row, (size_t)nrec * 4);
+    H.add(slab, n, false);
+    H.a = K->pointsH.p;
+    WS_HIP_CHECK(slab.alloc());
+    WS_HIP_CHECK(hipMemsetAsync(d_cnt, 0, ((size_t)n_tiles + 1) * 4, s));
+    WS_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(ZkAcc), s));
+    WS_HIP_CHECK(hipMemsetAsync(H.acc, 0, 2 * sizeof(PkAcc), s));
+    if (nrec && (rc = stage_pieces(d_rec, F.sec[4].p + 4, (size_t)nrec * 44, s, release))) return rc;
+    if ((rc = stage_pieces(H.a, F.sec[9].p, (size_t)n * 64, s, release))) return rc;
+    if ((rc = stage_pieces(K->pointsA.p, F.sec[5].p, (size_t)nv * 64, s, release))) return rc;
+    if ((rc = stage_pieces(K->pointsB1.p, F.sec[6].p, (size_t)nv * 64, s, release))) return rc;
+    if ((rc = stage_pieces(K->pointsB2.p, F.sec[7].p, (size_t)nv * 128, s, release))) return rc;
+    // C holds points for the signals nPublic + 1 .. only: the resident copy is padded in front with infinities (prove.hip)
+    const size_t c_front = ((size_t)F.n_public + 1) * 64;
+    WS_HIP_CHECK(hipMemsetAsync(K->pointsC.p, 0, c_front, s));
+    if (nC && (rc = stage_pieces((uint8_t*)K->pointsC.p + c_front, F.sec[8].p, (size_t)nC * 64, s, release))) return rc;
+    WS_HIP_CHECK(hipStreamSynchronize(s));
+    const double ms_up = ms_since(t_call);
+
+    // 2. the coefficients: counts and tests, the partition into the matrices' own arrays, the order, the row pointers
+    const auto t_coef = Clock::now();
+    if (nrec) {
+        T.begin("zkey_count", s);
+        hipLaunchKernelGGL(zk_count_kernel, dim3(n_tiles), dim3(256), 0, s, (const uint32_t*)d_rec, nrec, tile, F.n_vars, F.domain, d_cnt, acc);
+        WS_HIP_CHECK(hipGetLastError());
+        T.end(s);
+    }
+    if ((rc = scan_exclusive_dev(d_cnt, n_tiles + 1, d_tiles, d_base, d_cursor, s))) return rc;
+    ZkAcc h_acc;
+    uint32_t n0 = 0;
+    WS_HIP_CHECK(hipMemcpyAsync(&h_acc, acc, sizeof h_acc, hipMemcpyDeviceToHost, s));
+    WS_HIP_CHECK(hipMemcpyAsync(&n0, d_base + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    WS_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_acc.bad_matrix) return fmt("matrix > 1 in a coefficient record, first at record " + std::to_string(~h_acc.bad_matrix));
+    if (h_acc.bad_signal) return fmt("signal >= nVars in a coefficient record, first at record " + std::to_string(~h_acc.bad_signal));
+    if (h_acc.bad_constraint) return fmt("constraint >= domainSize in a coefficient record, first at record " + std::to_string(~h_acc.bad_constraint));
+    const uint32_t cnt[2] = {n0, nrec - n0};
+    CsrMatrix* const M[2] = {&K->polsA, &K->polsB};
+    uint32_t* const m_row[2] = {d_row, d_row + n0};
+    for (int m = 0; m < 2; m++) {
+        const size_t nz = std::max<uint32_t>(cnt[m], 1);
+        M[m]->n_rows = F.domain; M[m]->n_cols = F.n_vars; M[m]->nnz = cnt[m];
+        WS_HIP_CHECK(M[m]->row_ptr.alloc(((size_t)n + 1) * 4));
+        WS_HIP_CHECK(M[m]->col.alloc(nz * 4));
+        WS_HIP_CHECK(M[m]->coef.alloc(nz * sizeof(Fe)));
+    }
+    if (nrec) {
+        const ZkParts parts{{M[0]->col.as<uint32_t>(), M[1]->col.as<uint32_t>()}, {m_row[0], m_row[1]}, {M[0]->coef.as<Fe>(), M[1]->coef.as<Fe>()}};
+        T.begin("zkey_partition", s);
+        hipLaunchKernelGGL(zk_partition_kernel<true>, dim3(n_tiles), dim3(256), 0, s, (const uint32_t*)d_rec, nrec, tile / 256, (const uint32_t*)d_base, parts, acc);
+        WS_HIP_CHECK(hipGetLastError());
+        T.end(s);
+        T.begin("zkey_order", s);
+        for (int m = 0; m < 2; m++)
+            if (cnt[m] > 1) hipLaunchKernelGGL(zk_order_kernel, dim3(ceil_div_u64(cnt[m], 256)), dim3(256), 0, s, (const uint32_t*)m_row[m], cnt[m], &acc->unsorted[m]);
+        WS_HIP_CHECK(hipGetLastError());
+        T.end(s);
+        WS_HIP_CHECK(hipMemcpyAsync(&h_acc, acc, sizeof h_acc, hipMemcpyDeviceToHost, s));
+        WS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    {
+        SortBufs SB;
+        Slab sort_slab;
+        DevBuf col2[2], coef2[2];      // (what a sorted matrix's arrays were: freed behind the queue's last reader, at the end of this block)
+        if (nrec && (h_acc.unsorted[0] || h_acc.unsorted[1])) {
+            SB.add(sort_slab, std::max(h_acc.unsorted[0] ? cnt[0] : 0u, h_acc.unsorted[1] ? cnt[1] : 0u), tile);
+            WS_HIP_CHECK(sort_slab.alloc());
+        }
+        for (int m = 0; m < 2; m++) {
+            const uint32_t c = cnt[m];
+            const uint32_t* rows = m_row[m];
+            if (c && h_acc.unsorted[m]) {
+                const dim3 grid(ceil_div_u64(c, 256)), block(256);
+                int cur = 0;
+                hipLaunchKernelGGL(zk_keys_kernel, grid, block, 0, s, (const uint32_t*)m_row[m], (const uint32_t*)nullptr, c, SB.B.key[0], SB.B.val[0]);
+                WS_HIP_CHECK(hipGetLastError());
+                if ((rc = rows_sort_dev(X, SB.B, c, 0, (uint32_t)bits, &cur, s))) return rc;
+                WS_HIP_CHECK(col2[m].alloc((size_t)c * 4));
+                WS_HIP_CHECK(coef2[m].alloc((size_t)c * sizeof(Fe)));
+                T.begin("zkey_gather", s);
+                hipLaunchKernelGGL(zk_gather_kernel, grid, block, 0, s, (const uint32_t*)SB.B.val[cur], c, (const uint32_t*)M[m]->col.as<uint32_t>(),
+                                   (const Fe*)M[m]->coef.as<Fe>(), col2[m].as<uint32_t>(), coef2[m].as<Fe>());
+                WS_HIP_CHECK(hipGetLastError());
+                T.end(s);
+                std::swap(M[m]->col.p, col2[m].p); std::swap(M[m]->col.bytes, col2[m].bytes);
+                std::swap(M[m]->coef.p, coef2[m].p); std::swap(M[m]->coef.bytes, coef2[m].bytes);
+                rows = SB.B.key[cur];
+            }
+            T.begin("zkey_rowptr", s);
+            hipLaunchKernelGGL(zk_rowptr_kernel, dim3(ceil_div_u64(n + 1, 256)), dim3(256), 0, s, rows, c, F.domain, M[m]->row_ptr.as<uint32_t>());
+            WS_HIP_CHECK(hipGetLastError());
+            T.end(s);
+            // (the next matrix's sort reuses the pairs: this one's row pointers are read out of them first, on the same queue)
+        }
+        WS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    const double ms_coef = ms_since(t_coef);
+
+    // 3. H: the forward transform, then -2 w_2n^k per point, where the section lies
+    const auto t_h = Clock::now();
+    PkAcc h_in;
+    void* d_res = nullptr;
+    if ((rc = h_basis_dev(X, H.a, H.b, H.sc, H.tw, n, bits, 0, H.acc, &h_in, &d_res, s))) return rc;
+    if (h_in.bad) return h_bad_error("zkey import", h_in);
+    if (d_res != K->pointsH.p) WS_HIP_CHECK(hipMemcpyAsync(K->pointsH.p, d_res, (size_t)n * 64, hipMemcpyDeviceToDevice, s));
+    WS_HIP_CHECK(hipStreamSynchronize(s));
+    const double ms_h = ms_since(t_h);
+    slab.buf.release();      // (before the table build is queued: a free waits for the whole device)
+
+    // 4. sections resident: the masks, the conversion, the tables (prove.hip)
+    clock.t_phase = Clock::now();
+    if ((rc = pkey_load_convert(K.get(), &clock))) return rc;
+    if ((rc = pkey_load_finish(X, K.get(), &clock))) return rc;
+    K->load_ms[0] = ms_coef;
+    K->load_ms[1] = ms_up;
+    if (out_vk) {
+        q_from_mont(fx, out_vk, 2);                       // alfa1
+        q_from_mont(fx + 128, out_vk + 64, 4);            // beta2
+        q_from_mont(fx + 256, out_vk + 192, 4);           // gamma2
+        q_from_mont(fx + 448, out_vk + 320, 4);           // delta2
+        q_from_mont(F.sec[3].p, out_vk + 448, 2 * ((size_t)F.n_public + 1));
+    }
+    if (rep) {
+        wsnark_zkey_report_t R;
+        memset(&R, 0, sizeof R);
+        for (int m = 0; m < 2; m++) { R.records[m] = cnt[m]; R.unreduced[m] = nrec ? h_acc.unreduced[m] : 0; R.zero[m] = nrec ? h_acc.zero[m] : 0; }
+        R.sorted = nrec == 0 || (!h_acc.unsorted[0] && !h_acc.unsorted[1]);
+        h_report(h_in, n, &R);
+        R.ms[0] = ms_up; R.ms[1] = ms_coef; R.ms[2] = ms_h; R.ms[3] = 0; R.ms[4] = ms_since(t_call);
+        *rep = R;
+    }
+    *out = K.release();
+    return WS_OK;
+}
+
+int zkey_load_file(const char* path, ProvingKey** out, uint8_t* out_vk, size_t vk_cap, wsnark_zkey_report_t* rep) {
+    if (!ctx()) return WS_ERR_NOINIT;
+    if (!path || !out || (!out_vk && vk_cap)) return WS_ERR_ARG;
+    KeyFile file;
+    if (int rc = keyfile_map(path, &file, 0)) return rc;      // (whatever is shorter than a container, an empty file included, is zk_parse's to name)
+    static const uint8_t kNoBytes[1] = {0};
+    return zkey_load(file.len ? file.base : kNoBytes, file.len, keyfile_release, out, out_vk, vk_cap, rep);
+}
+
+// The length of the verification key from the container and section 2 ALONE: what a caller needs to size out_vk of the calls above.
+// zk_parse reads the section table and the small sections' payloads; no byte of sections 3 - 9 is touched (zkey_info counts section 4's
+// records on the host, which a mapped file of a large key must not pay).
+int zkey_vk_len(const uint8_t* zkey, size_t len, size_t* out_len) {
+    if (!out_len) return WS_ERR_ARG;
+    ZkFile F;
+    if (int rc = zk_parse(zkey, len, &F)) return rc;
+    *out_len = (size_t)vk_len_of(F.n_public);
+    return WS_OK;
+}
+int zkey_vk_len_file(const char* path, size_t* out_len) {
+    if (!path || !out_len) return WS_ERR_ARG;
+    KeyFile file;
+    if (int rc = keyfile_map(path, &file, 0)) return rc;
+    static const uint8_t kNoBytes[1] = {0};
+    return zkey_vk_len(file.len ? file.base : kNoBytes, file.len, out_len);
 }
 
 }  // namespace wsnark

@@ -31,6 +31,34 @@ function proofFromBytes(ab) { return addon.proofToObject(ab); }
  * digest taken when that handle was loaded, loads the new bytes and proves again (the stale proof is never returned).  Callers who
  * know their key bytes do not change opt into the sampled check alone with {trustCache: true}; callers who want no check at all hold
  * the handle of loadKey() and pass that. */
+/* the verifier's plain layout (alfa1 | beta2 | gamma2 | delta2 | IC[0 .. nPublic]) -> the verification key object */
+function vkFromBytes(vkb) {
+    const nPublic = (vkb.length - 448) / 64 - 1;
+    const dec = (o) => { let x = 0n; for (let i = 31; i >= 0; i--) x = (x << 8n) | BigInt(vkb[o + i]); return x.toString(); };
+    const g1 = (o) => [dec(o), dec(o + 32), "1"], g2 = (o) => [[dec(o), dec(o + 32)], [dec(o + 64), dec(o + 96)], ["1", "0"]];
+    const vk = { protocol: "groth", nPublic, vk_alfa_1: g1(0), vk_beta_2: g2(64), vk_gamma_2: g2(192), vk_delta_2: g2(320), IC: [] };
+    for (let i = 0; i <= nPublic; i++) vk.IC.push(g1(448 + 64 * i));
+    return vk;
+}
+/* do these bytes, or does this file, begin with a .zkey's magic?  (decided by the first four bytes, never by a file's name) */
+function isZkey(x) {
+    if (typeof x === "string") {
+        const fs = require("fs"), b = Buffer.alloc(4), fd = fs.openSync(x, "r");
+        try { return fs.readSync(fd, b, 0, 4, 0) === 4 && b.toString("latin1") === "zkey"; } finally { fs.closeSync(fd); }
+    }
+    const u8 = asBytes(x);
+    return u8.byteLength >= 4 && u8[0] === 0x7a && u8[1] === 0x6b && u8[2] === 0x65 && u8[3] === 0x79;
+}
+/* the addon's handle of a .zkey load: zkeyOut (the report, the vk's bytes) becomes .report and .vk */
+async function zkeyHandle(load) {
+    const h = await load;
+    if (h.zkeyOut) {
+        h.report = zkeyReport(new DataView(h.zkeyOut), 0);
+        h.vk = vkFromBytes(Buffer.from(h.zkeyOut, 136));
+        delete h.zkeyOut;
+    }
+    return h;
+}
 async function digest(u8) {
     return Buffer.from(await addon.hashBytes(u8)).toString("hex");
 }
@@ -281,6 +309,9 @@ class Bn128 {
         return hit && hit.byteOffset === u8.byteOffset && hit.byteLength === u8.byteLength && hit.fp === fingerprint(u8) ? hit : null;
     }
     /* pkey bytes -> device-resident key handle (stays in HBM across proofs; freed by the GC).
+     * Bytes (or a file: _loadKeyFile) that begin with "zkey" are a snarkjs .zkey: it is loaded straight into the resident key
+     * (include/wsnark.h: wsnark_pkey_load_zkey*), the handle carries .vk -- the file's verification key object -- and .report, and
+     * groth16GenProof(witness | wtns, zkey bytes | that handle) follows, digest cache included.  NOT audited, like importZkey; one GPU.
      * A cached handle is returned when the digest of ALL bytes equals the one taken when it was loaded; opts.trustCache === true: when
      * the sampled fingerprint does.  Concurrent callers with the same key object share ONE load: the entry is in the map before it is awaited. */
     async loadKey(pkey, opts) {
@@ -302,7 +333,10 @@ class Bn128 {
         // key, a quarter of the load) and loadKey() resolves only when BOTH are done: a caller who rewrites bytes in place as
         // soon as the first call returns must find them compared against the bytes that were loaded, not against a digest that
         // was still being taken while they changed.
-        const load = this._group ? addon.groupLoadKey(this._group, pkey) : addon.loadKey(pkey);
+        // a snarkjs .zkey goes straight into the resident key (wsnark_pkey_load_zkey): the handle carries .vk and .report
+        const zkey = isZkey(u8);
+        if (zkey && this._group) throw new Error("wsnark: a .zkey is loaded on a single GPU (build a Bn128 without {devices}, or importZkey it first)");
+        const load = zkey ? zkeyHandle(addon.loadKeyZkey(pkey)) : this._group ? addon.groupLoadKey(this._group, pkey) : addon.loadKey(pkey);
         const entry = { byteOffset: u8.byteOffset, byteLength: u8.byteLength, fp: fingerprint(u8), handle: load, digest: digest(u8) };
         this.fullDigests++;
         this._keys.set(pkey, entry);
@@ -561,11 +595,7 @@ class Bn128 {
         const keyLen = Number(v.getBigUint64(0, true)), vkLen = Number(v.getBigUint64(8, true));
         const report = zkeyReport(v, 16);
         const vkb = Buffer.from(ab, 152, vkLen), pkey = Buffer.from(ab, 152 + vkLen, keyLen);
-        const nPublic = (vkLen - 448) / 64 - 1;
-        const dec = (o) => { let x = 0n; for (let i = 31; i >= 0; i--) x = (x << 8n) | BigInt(vkb[o + i]); return x.toString(); };
-        const g1 = (o) => [dec(o), dec(o + 32), "1"], g2 = (o) => [[dec(o), dec(o + 32)], [dec(o + 64), dec(o + 96)], ["1", "0"]];
-        const vk = { protocol: "groth", nPublic, vk_alfa_1: g1(0), vk_beta_2: g2(64), vk_gamma_2: g2(192), vk_delta_2: g2(320), IC: [] };
-        for (let i = 0; i <= nPublic; i++) vk.IC.push(g1(448 + 64 * i));
+        const vk = vkFromBytes(vkb), nPublic = vk.nPublic;
         if (opts && opts.wtns) {
             const wit = formats.isWtns(opts.wtns) ? formats.wtnsToWitness(opts.wtns) : Buffer.from(asBytes(opts.wtns));
             const proof = await this.groth16GenProof(wit, pkey, { trustCache: false });
@@ -596,7 +626,10 @@ class Bn128 {
         const st = fs.statSync(path);
         const hit = this._files.get(path);
         if (hit && hit.size === st.size && hit.mtimeMs === st.mtimeMs) return hit.handle;
-        const entry = { size: st.size, mtimeMs: st.mtimeMs, handle: this._group ? addon.groupLoadKeyFile(this._group, path) : addon.loadKeyFile(path) };
+        const zkey = isZkey(path);
+        if (zkey && this._group) throw new Error("wsnark: a .zkey is loaded on a single GPU (build a Bn128 without {devices}, or importZkey it first)");
+        const entry = { size: st.size, mtimeMs: st.mtimeMs,
+                        handle: zkey ? zkeyHandle(addon.loadKeyZkeyFile(path)) : this._group ? addon.groupLoadKeyFile(this._group, path) : addon.loadKeyFile(path) };
         this._files.set(path, entry);
         try { return await entry.handle; } catch (e) { if (this._files.get(path) === entry) this._files.delete(path); throw e; }
     }

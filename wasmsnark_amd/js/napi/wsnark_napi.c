@@ -83,6 +83,11 @@ static struct {
     int (*zkey_import)(const void*, size_t, void*, size_t, size_t*, void*, size_t, void*);
     int (*zkey_export)(const void*, size_t, const void*, size_t, uint64_t, void*, size_t, size_t*, void*);
     int (*zkey_export_size)(uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, size_t*);
+    /* ... and straight into a resident key (wsnark_pkey_load_zkey*) */
+    int (*pkey_load_zkey)(const void*, size_t, wsnark_pkey_t**, void*, size_t, void*);
+    int (*pkey_load_zkey_file)(const char*, wsnark_pkey_t**, void*, size_t, void*);
+    int (*zkey_vk_len)(const void*, size_t, size_t*);
+    int (*zkey_vk_len_file)(const char*, size_t*);
     /* powers of tau (include/wsnark.h: wsnark_g{1,2}_mul_batch, wsnark_powers_contribute, wsnark_powers_check) */
     int (*g1_mul)(const void*, const void*, uint64_t, void*);
     int (*g2_mul)(const void*, const void*, uint64_t, void*);
@@ -165,6 +170,7 @@ static int load_lib(char* err, size_t errlen) {
     SYM(g2_decompress, "wsnark_g2_decompress") SYM(proof_compress, "wsnark_proof_compress") SYM(proof_decompress, "wsnark_proof_decompress")
     SYM(verify_batch_compressed, "wsnark_groth16_verify_batch_compressed")
     SYM(zkey_info, "wsnark_zkey_info") SYM(zkey_import, "wsnark_zkey_import") SYM(zkey_export, "wsnark_zkey_export") SYM(zkey_export_size, "wsnark_zkey_export_size")
+    SYM(pkey_load_zkey, "wsnark_pkey_load_zkey") SYM(pkey_load_zkey_file, "wsnark_pkey_load_zkey_file") SYM(zkey_vk_len, "wsnark_zkey_vk_len") SYM(zkey_vk_len_file, "wsnark_zkey_vk_len_file")
 #undef SYM
     return 0;
 }
@@ -192,7 +198,7 @@ static int get_bytes(napi_env env, napi_value v, uint8_t** p, size_t* n) {
 
 enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH, OP_WAIT_TABLES,
        OP_GROUP_G1, OP_GROUP_G2, OP_GROUP_LOADKEY, OP_GROUP_PROVE, OP_GROUP_WAIT_TABLES, OP_POINTS_LOAD, OP_POINTS_MSM,
-       OP_LOADKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
+       OP_LOADKEY_FILE, OP_LOADKEY_ZKEY, OP_LOADKEY_ZKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
        OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
        OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH, OP_CIRCUIT_FROM_ROWS, OP_CIRCUIT_LOAD_ROWS, OP_ZKEY_IMPORT, OP_ZKEY_EXPORT,
        OP_CODEC_POINTS, OP_CODEC_PROOFS, OP_VERIFY_BATCH_COMPRESSED };
@@ -214,10 +220,20 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
 typedef struct { uint64_t tag; void* p; } handle_t;                 /* a key (wsnark_pkey_t*), a point set (wsnark_points_t*) or a resident circuit */
 typedef struct { uint64_t tag; wsnark_group_t* g; int live; int inflight; int refs; } group_ref_t;
 typedef struct { uint64_t tag; wsnark_group_pkey_t* k; group_ref_t* gr; } gkey_ref_t;
+#define KEY_OBJECT_MARK "wsnarkKeyObject"      /* own property of the object that wraps a key handle: nothing else is unwrapped */
 static void* get_handle(napi_env env, napi_value v, uint64_t tag) {
     void* p = NULL;
     napi_valuetype t;
-    if (napi_typeof(env, v, &t) != napi_ok || t != napi_external || napi_get_value_external(env, v, &p) != napi_ok || !p) return NULL;
+    if (napi_typeof(env, v, &t) != napi_ok) return NULL;
+    if (t == napi_object) {      /* the key handle of a .zkey: an object that carries .vk, the handle_t wrapped inside (js_loadkey_zkey) */
+        bool ours = false;
+        napi_value mark;
+        if (napi_create_string_utf8(env, KEY_OBJECT_MARK, NAPI_AUTO_LENGTH, &mark) != napi_ok || napi_has_own_property(env, v, mark, &ours) != napi_ok ||
+            !ours || napi_unwrap(env, v, &p) != napi_ok || !p)
+            return NULL;
+        return *(const uint64_t*)p == tag ? p : NULL;
+    }
+    if (t != napi_external || napi_get_value_external(env, v, &p) != napi_ok || !p) return NULL;
     return *(const uint64_t*)p == tag ? p : NULL;
 }
 static void* get_plain(napi_env env, napi_value v, uint64_t tag) {   /* the library pointer inside a key / points handle */
@@ -382,6 +398,17 @@ static void job_execute(napi_env env, void* data) {
     }
     case OP_LOADKEY: j->rc = L.pkey_load(j->a, j->na, &j->key); break;
     case OP_LOADKEY_FILE: j->rc = L.pkey_load_file(j->path, 0, 1, 0, &j->key); break;
+    case OP_LOADKEY_ZKEY:
+    case OP_LOADKEY_ZKEY_FILE: {   /* out (sized here, from the file's container and section 2 alone: wsnark_zkey_vk_len*): the wsnark_zkey_report_t, the vk */
+        size_t vk_len = 0;
+        if ((j->rc = j->op == OP_LOADKEY_ZKEY_FILE ? L.zkey_vk_len_file(j->path, &vk_len) : L.zkey_vk_len(j->a, j->na, &vk_len))) break;
+        j->nout = ZKEY_REPORT_BYTES + vk_len;
+        j->out = (uint8_t*)calloc(j->nout, 1);
+        if (!j->out) { j->rc = -1; snprintf(j->err, sizeof j->err, "wsnark: out of memory for the verification key"); return; }
+        j->rc = j->op == OP_LOADKEY_ZKEY_FILE ? L.pkey_load_zkey_file(j->path, &j->key, j->out + ZKEY_REPORT_BYTES, vk_len, j->out)
+                                              : L.pkey_load_zkey(j->a, j->na, &j->key, j->out + ZKEY_REPORT_BYTES, vk_len, j->out);
+        break;
+    }
     case OP_GROUP_LOADKEY_FILE: j->rc = L.group_pkey_load_file(j->gr->g, j->path, &j->gk->k); break;
     case OP_VERIFY: j->rc = L.verify(j->a, j->na, j->b, j->nb / 32, j->c, &j->i0); break;
     case OP_VERIFY_BATCH: j->rc = L.verify_batch(j->a, j->na, j->nb ? j->b : NULL, j->u0, j->c, j->nc / 384, j->out); break;
@@ -625,6 +652,27 @@ static void job_complete(napi_env env, napi_status status, void* data) {
     } else if (j->op == OP_LOADKEY || j->op == OP_LOADKEY_FILE) {
         napi_create_external(env, new_handle(TAG_KEY, j->key), key_finalize, NULL, &res);
         napi_resolve_deferred(env, j->deferred, res);
+    } else if (j->op == OP_LOADKEY_ZKEY || j->op == OP_LOADKEY_ZKEY_FILE) {
+        /* an OBJECT as the handle (it carries .vk: js/index.js), the handle_t wrapped inside; zkeyOut: the report, the vk's bytes */
+        handle_t* h = new_handle(TAG_KEY, j->key);
+        napi_value ab, yes;
+        void* dst;
+        const napi_property_descriptor mark = {KEY_OBJECT_MARK, NULL, NULL, NULL, NULL, NULL, napi_default, NULL};      /* (read-only, not enumerable) */
+        napi_property_descriptor marks[1] = {mark};
+        if (!h || napi_create_object(env, &res) != napi_ok || napi_get_boolean(env, true, &yes) != napi_ok || ((marks[0].value = yes), 0) ||
+            napi_define_properties(env, res, 1, marks) != napi_ok || napi_wrap(env, res, h, key_finalize, NULL, NULL) != napi_ok) {      /* nothing would ever free the key */
+            napi_value msg, e;
+            L.pkey_free(j->key);
+            free(h);
+            napi_create_string_utf8(env, "wsnark_napi: cannot create the key handle", NAPI_AUTO_LENGTH, &msg);
+            napi_create_error(env, NULL, msg, &e);
+            napi_reject_deferred(env, j->deferred, e);
+        } else {
+            napi_create_arraybuffer(env, j->nout, &dst, &ab);
+            memcpy(dst, j->out, j->nout);
+            napi_set_named_property(env, res, "zkeyOut", ab);
+            napi_resolve_deferred(env, j->deferred, res);
+        }
     } else {
         void* dst;
         napi_create_arraybuffer(env, j->nout, &dst, &res);   /* results are fresh ArrayBuffers, as in the reference */
@@ -730,6 +778,26 @@ static napi_value js_loadkey_file(napi_env env, napi_callback_info info) {
     j->op = OP_LOADKEY_FILE;
     if (argc < 1 || !(j->path = get_path(env, argv[0]))) FAIL(env, j, "expected the path of a key file");
     return start_job(env, j, "wsnark_pkey_load_file");
+}
+/* loadKeyZkey(zkey bytes) / loadKeyZkeyFile(path) -> Promise<key handle>: a snarkjs .zkey straight into a resident key
+ * (wsnark_pkey_load_zkey / _file).  The handle is an object every call that takes loadKey's handle takes; its zkeyOut holds the
+ * wsnark_zkey_report_t and the verification key in the verifier's layout (js/index.js turns them into .report and .vk) */
+static napi_value js_loadkey_zkey(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_LOADKEY_ZKEY;
+    if (argc < 1 || !get_bytes(env, argv[0], &j->a, &j->na)) FAIL(env, j, "expected a .zkey byte buffer");
+    keep(env, j, argv[0]);
+    return start_job(env, j, "wsnark_pkey_load_zkey");
+}
+static napi_value js_loadkey_zkey_file(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_LOADKEY_ZKEY_FILE;
+    if (argc < 1 || !(j->path = get_path(env, argv[0]))) FAIL(env, j, "expected the path of a .zkey file");
+    return start_job(env, j, "wsnark_pkey_load_zkey_file");
 }
 /* keyFileInfo(path) -> {nVars, nPublic, domainSize, fileBytes, format: "proving_key.bin" | "WSNARK64"} (synchronous: reads the header) */
 static napi_value js_keyfile_info(napi_env env, napi_callback_info info) {
@@ -1620,6 +1688,8 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"calcH", NULL, js_calch, NULL, NULL, NULL, napi_default, NULL},
         {"loadKey", NULL, js_loadkey, NULL, NULL, NULL, napi_default, NULL},
         {"loadKeyFile", NULL, js_loadkey_file, NULL, NULL, NULL, napi_default, NULL},
+        {"loadKeyZkey", NULL, js_loadkey_zkey, NULL, NULL, NULL, napi_default, NULL},
+        {"loadKeyZkeyFile", NULL, js_loadkey_zkey_file, NULL, NULL, NULL, napi_default, NULL},
         {"keyFileInfo", NULL, js_keyfile_info, NULL, NULL, NULL, napi_default, NULL},
         {"groupLoadKeyFile", NULL, js_group_loadkey_file, NULL, NULL, NULL, napi_default, NULL},
         {"hashBytes", NULL, js_hash, NULL, NULL, NULL, napi_default, NULL},
