@@ -1141,7 +1141,14 @@ int wsnark_selftest_field(int which, int impl, int op, const void* a, const void
  *   but a little-endian scalar in bytes [0, 64) and its length -- 32 or 64 -- in byte 64 (impl 0-3),
  *   10 and 11 (9 is not an operation) = the reduction tail's straight-path addition (curve.h / curve_pair.h: add_fast), which refuses
  *   what is not the sum of two finite, distinct, non-opposite points: 10 = the accumulator after the call (p + q where it accepts, p
- *   where it refuses), 11 = q where it accepts, infinity where it refuses.
+ *   where it refuses), 11 = q where it accepts, infinity where it refuses,
+ *   12 - 15 = one step of the ACCUMULATION LOOP's fast half as msm.hip takes it (q affine: z == 1, or infinity): q at infinity is
+ *   refused by the loop's own test, every other q goes to the straight-path mixed addition (curve.h), which refuses a q that may be
+ *   equal or opposite to p -- a cheap necessary test, so a refusal of another pair is allowed -- without touching the accumulator:
+ *   12 = madd_fast(p, q): the accumulator after the step, narrowed (p + q where it accepts, p unchanged where it refuses),
+ *   13 = the same step: q where it accepts, infinity where it refuses; 14 / 15 = the same two for mmadd_fast, the affine + affine
+ *   form of a task's second entry: every p must be affine with z == 1, any other p is WSNARK_ERR_ARG.  impl 0-3; the tails' paired
+ *   and lane-split curves (impl 4, 5, 6) do not have these functions: WSNARK_ERR_ARG.
  *   impl 5 (g = 1) and 6 (g = 2): the lane-split tail curves (one point on two / four lanes), ops 0, 1, 3, 10, 11. */
 int wsnark_selftest_curve(int g, int impl, int op, const void* p, const void* q, void* out, uint64_t n);
 /* The radix-2^29 field (csrc/field29.h) on RAW limbs, one lane per case: the operand bounds its contracts allow cannot be reached
@@ -1227,6 +1234,24 @@ int wsnark_selftest_fp12(int impl, int op, const void* a, const void* b, void* o
 int wsnark_selftest_msm_plan(const void* scalars, uint64_t n, uint32_t table_c, uint32_t w_off, uint32_t w_stride, const void* mask,
                              uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
                              uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot);
+/* The MSM's accumulation kernel (csrc/msm.hip: msm_accumulate, the __global__ function every sum launches) on tasks the caller wrote,
+ * so that a test decides which entry meets which running sum (tests/accumulate_patterns.py holds the model of the loop's branches).
+ *   g       : 1 or 2
+ *   points  : n_points affine points in the reference's Montgomery format (64 / 128 B, as wsnark_g{1,2}_multiexp takes them; an
+ *             all-zero record is infinity), brought to the device form by the conversion every sum uses
+ *   vals    : n_vals words index | sign << 31, exactly what the grouping pass writes (sign: the point is subtracted)
+ *   tasks   : n_tasks x (start, len): task t sums vals[start .. start + len); ranges may overlap; len 0 gives infinity
+ *   out     : n_tasks affine-normalised Jacobian-Montgomery points ((x, y, 1) or (0, 1, 0); 96 / 192 B) like every group element this
+ *             ABI returns
+ * Task t is stored to bucket t when t is even and to partial slot t when t is odd, so both stores of the kernel run; the task count
+ * sits in device memory and the grid is whole workgroups of 256, as a sum's.  Both result arrays carry a workgroup of extra slots and
+ * are pre-filled with a byte pattern: a slot that no task names and does not hold the pattern afterwards, or a named slot that still
+ * does, fails the call with WSNARK_ERR_FORMAT (wsnark_last_error names the slot).  Everything is checked on the host BEFORE anything is
+ * launched: an index >= n_points, start + len > n_vals, n_points or n_vals > 2^20, n_tasks > 2^16, g not 1 or 2, a null pointer
+ * with a non-zero count: WSNARK_ERR_ARG, and out is not written.  The hook allocates and frees its own buffers, waits for the queue
+ * and leaves nothing behind that a later sum reads. */
+int wsnark_selftest_msm_accumulate(int g, const void* points, uint64_t n_points, const uint32_t* vals, uint64_t n_vals, const uint32_t* tasks,
+                                   uint64_t n_tasks, void* out);
 
 /* ---- measurement hooks (bench.py) ---- */
 /* A/B switches of the library (queue arrangement of a proof, reduction-tail geometry, ...; the names are the WSNARK_<name>

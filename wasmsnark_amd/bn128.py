@@ -1093,6 +1093,23 @@ class Bn128:
         return {"info": w2, "bstart": bs[:w2["nbuckets"]], "bend": be[:w2["nbuckets"]], "vals": vals[:w2["nvals"]],
                 "tasks": rec(tasks, 3, w2["tasks"]), "multi": rec(multi, 3, w2["multi_buckets"]), "hot": rec(hot, 8, w2["hot_buckets"])}
 
+    # --- test hook (no reference counterpart): the accumulation kernel itself on tasks the caller wrote ---
+    def selftest_msm_accumulate(self, g, points, vals, tasks, out=None):
+        """wsnark_selftest_msm_accumulate: msm_accumulate over `points` (affine Montgomery bytes, 64 / 128 B each), `vals` (words
+        index | sign << 31) and `tasks` [(start, len)]; returns one normalised point (96 / 192 B) per task.  out: a ctypes buffer to
+        write into (a test that checks what a failed call leaves).  Bad arguments raise WsnarkError (WSNARK_ERR_ARG) before anything
+        is launched."""
+        p, np_ = _ro(points)
+        sz, osz = (64, 96) if g == 1 else (128, 192)
+        nv, nt = len(vals), len(tasks)
+        v = (C.c_uint32 * max(nv, 1))(*vals)
+        t = (C.c_uint32 * max(2 * nt, 1))(*[w for task in tasks for w in task])
+        if out is None:
+            out = (C.c_uint8 * max(nt * osz, 1))()
+        self.lib.check(self.lib.c.wsnark_selftest_msm_accumulate(g, p, np_ // sz, v, nv, t, nt, out))
+        o = bytes(out)
+        return [o[i * osz:(i + 1) * osz] for i in range(nt)]
+
     def load_points(self, g, points):
         """Make a point set resident as fixed-base tables (no reference counterpart): see ResidentPoints."""
         return ResidentPoints(self.lib, g, points)

@@ -772,6 +772,12 @@ int wsnark_selftest_msm_plan(const void* scalars, uint64_t n, uint32_t table_c, 
                              vals, cap_vals, tasks, cap_tasks, multi, cap_multi, hot, cap_hot);
 }
 
+int wsnark_selftest_msm_accumulate(int g, const void* points, uint64_t n_points, const uint32_t* vals, uint64_t n_vals, const uint32_t* tasks,
+                                   uint64_t n_tasks, void* out) {
+    REQUIRE_CTX();
+    return selftest_msm_accumulate(g, points, n_points, vals, n_vals, tasks, n_tasks, out);      // (every argument is checked there)
+}
+
 int wsnark_selftest_field29(int which, int impl, int op, const uint32_t* operands, uint32_t* out, uint64_t n) {
     REQUIRE_CTX();
     if (n && (!operands || !out)) return WSNARK_ERR_ARG;

@@ -294,6 +294,10 @@ static const uint32_t kMsmPlanInfoWords = 24;
 int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table_c, WindowShard sh, const uint8_t* h_mask,
                       uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
                       uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot);
+// test hook (wsnark_selftest_msm_accumulate): msm_accumulate itself on caller-written tasks (g: 1 or 2; tasks: n_tasks x (start, len));
+// arguments are checked on the host before anything is launched; own buffers; waits for the queue
+int selftest_msm_accumulate(int g, const void* h_points, uint64_t n_points, const uint32_t* h_vals, uint64_t n_vals, const uint32_t* h_tasks,
+                            uint64_t n_tasks, void* out);
 bool msm_ready(Lane& L, int slot);     // the launch's window sums have reached the host (finish will not block)
 int msm_g1_finish(Lane& L, int slot, XYZZ<Fq>* out_host);
 int msm_g2_finish(Lane& L, int slot, XYZZ<Fq2>* out_host);

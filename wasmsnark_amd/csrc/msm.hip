@@ -2383,6 +2383,114 @@ int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table
     return WS_OK;
 }
 
+// ---- test hook (wsnark_selftest_msm_accumulate): the accumulation kernel itself on tasks the caller wrote ----
+// msm_accumulate<C> -- the __global__ function every sum launches -- over one set: the caller's points (converted by msm_prepare_points
+// as every sum's are), vals and (start, len) ranges; task t is stored to bucket t (t even) or to partial slot t (t odd).  The task
+// count sits in device memory (counters[3]) and the grid is whole workgroups, as the product sizes it.  Both result arrays carry a
+// workgroup of extra slots and are pre-filled with a byte pattern: a slot no task names must still hold it afterwards, and a slot a
+// task names must not.  Everything is checked on the host before anything is launched -- the kernel is never handed a range or an
+// index it could read outside of.  Buffers are the hook's own (hipMalloc / hipFree); the queue is waited for.
+static const uint8_t kAccHookFill = 0xA5;
+template <class C>
+__global__ __launch_bounds__(256) void acc_hook_export(const typename C::PtP* __restrict__ buckets, const typename C::PtP* __restrict__ partials,
+                                                         typename C::PtP* __restrict__ out, uint32_t ntasks) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntasks) return;
+    out[t] = C::pt_from_internal(C::unpack_pt((t & 1) ? partials[t] : buckets[t]));      // reference format, for the host's normalisation
+}
+template <class C, class H>
+static int selftest_msm_accumulate_t(int which, const void* h_points, uint64_t n_points, const uint32_t* h_vals, uint64_t n_vals,
+                                     const uint32_t* h_tasks, uint64_t n_tasks, uint8_t* out, hipStream_t s) {
+    typedef typename C::PtP PtP;
+    static_assert(sizeof(PtP) == sizeof(typename H::Pt), "layouts");
+    const uint32_t nt = (uint32_t)n_tasks;
+    const size_t slots = (size_t)nt + 256;
+    std::vector<Task> tasks(nt);
+    for (uint32_t t = 0; t < nt; t++) tasks[t] = Task{(t & 1) ? (PARTIAL_FLAG | t) : t, h_tasks[2 * t], h_tasks[2 * t + 1]};
+    uint32_t counters[8] = {0, 0, 0, nt, 0, 0, 0, 0};
+    DevBuf points, vals, dtasks, cnt, buckets, partials, dout;
+    WS_HIP_CHECK(points.alloc((size_t)n_points * sizeof(typename C::AffP)));
+    WS_HIP_CHECK(vals.alloc((size_t)n_vals * 4));
+    WS_HIP_CHECK(dtasks.alloc((size_t)nt * sizeof(Task)));
+    WS_HIP_CHECK(cnt.alloc(sizeof counters));
+    WS_HIP_CHECK(buckets.alloc(slots * sizeof(PtP)));
+    WS_HIP_CHECK(partials.alloc(slots * sizeof(PtP)));
+    WS_HIP_CHECK(dout.alloc((size_t)nt * sizeof(PtP)));
+    // (blocking copies: the host arrays are pageable; everything after them is ordered on s)
+    if (n_points) WS_HIP_CHECK(hipMemcpy(points.p, h_points, (size_t)n_points * sizeof(typename C::AffP), hipMemcpyHostToDevice));
+    if (n_vals) WS_HIP_CHECK(hipMemcpy(vals.p, h_vals, (size_t)n_vals * 4, hipMemcpyHostToDevice));
+    WS_HIP_CHECK(hipMemcpy(dtasks.p, tasks.data(), (size_t)nt * sizeof(Task), hipMemcpyHostToDevice));
+    WS_HIP_CHECK(hipMemcpy(cnt.p, counters, sizeof counters, hipMemcpyHostToDevice));
+    WS_HIP_CHECK(hipMemsetAsync(buckets.p, kAccHookFill, slots * sizeof(PtP), s));
+    WS_HIP_CHECK(hipMemsetAsync(partials.p, kAccHookFill, slots * sizeof(PtP), s));
+    int rc = msm_prepare_points(which, points.p, n_points, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    AccSets<C> as = {};
+    as.points[0] = points.as<typename C::AffP>();
+    as.vals[0] = vals.as<uint32_t>();
+    as.tasks[0] = dtasks.as<Task>();
+    as.counters[0] = cnt.as<uint32_t>();
+    as.buckets[0] = buckets.as<PtP>();
+    as.partials[0] = partials.as<PtP>();
+    hipLaunchKernelGGL(msm_accumulate<C>, dim3(ceil_div_u64(nt, 256), 1), dim3(256), 0, s, as);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(acc_hook_export<C>, dim3(ceil_div_u64(nt, 256)), dim3(256), 0, s, buckets.as<PtP>(), partials.as<PtP>(), dout.as<PtP>(), nt);
+        e = hipGetLastError();
+    }
+    std::vector<uint8_t> hb(slots * sizeof(PtP)), hp(slots * sizeof(PtP));
+    std::vector<typename H::Pt> host(nt);
+    const hipError_t e2 = hipStreamSynchronize(s);          // (always: the buffers are freed on return)
+    if (e == hipSuccess) e = e2;
+    if (e == hipSuccess) e = hipMemcpy(hb.data(), buckets.p, hb.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hp.data(), partials.p, hp.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(host.data(), dout.p, (size_t)nt * sizeof(PtP), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        set_last_error(std::string("selftest_msm_accumulate: ") + hipGetErrorString(e));
+        return WS_ERR_HIP;
+    }
+    auto filled = [](const uint8_t* p) {
+        for (size_t i = 0; i < sizeof(PtP); i++)
+            if (p[i] != kAccHookFill) return false;
+        return true;
+    };
+    for (size_t i = 0; i < slots; i++) {
+        const bool named_b = i < nt && !(i & 1), named_p = i < nt && (i & 1);
+        const bool fb = filled(hb.data() + i * sizeof(PtP)), fp = filled(hp.data() + i * sizeof(PtP));
+        if (fb == named_b || fp == named_p) {
+            set_last_error("selftest_msm_accumulate: " + std::string(fb == named_b ? "bucket" : "partial") + " slot " + std::to_string(i) +
+                           ((fb == named_b ? named_b : named_p) ? " was not written by its task" : " was written and no task names it"));
+            return WS_ERR_FORMAT;
+        }
+    }
+    for (uint32_t t = 0; t < nt; t++) {
+        auto j = H::to_affine_jac(host[t]);
+        memcpy(out + (size_t)t * sizeof j, &j, sizeof j);
+    }
+    return WS_OK;
+}
+int selftest_msm_accumulate(int g, const void* h_points, uint64_t n_points, const uint32_t* h_vals, uint64_t n_vals, const uint32_t* h_tasks,
+                            uint64_t n_tasks, void* out) {
+    Context* X = ctx();
+    if (!X) return WS_ERR_NOINIT;
+    if (g != 1 && g != 2) return WS_ERR_ARG;
+    if (n_points > (1u << 20) || n_vals > (1u << 20) || n_tasks > (1u << 16)) return WS_ERR_ARG;
+    if ((n_points && !h_points) || (n_vals && !h_vals) || (n_tasks && (!h_tasks || !out))) return WS_ERR_ARG;
+    for (uint64_t i = 0; i < n_vals; i++)
+        if ((h_vals[i] & 0x7FFFFFFFu) >= n_points) {
+            set_last_error("selftest_msm_accumulate: vals[" + std::to_string(i) + "] names a point past n_points");
+            return WS_ERR_ARG;
+        }
+    for (uint64_t t = 0; t < n_tasks; t++)
+        if ((uint64_t)h_tasks[2 * t] + h_tasks[2 * t + 1] > n_vals) {
+            set_last_error("selftest_msm_accumulate: task " + std::to_string(t) + " ends past n_vals");
+            return WS_ERR_ARG;
+        }
+    if (n_tasks == 0) return WS_OK;
+    if (g == 1) return selftest_msm_accumulate_t<G1R29, G1>(0, h_points, n_points, h_vals, n_vals, h_tasks, n_tasks, (uint8_t*)out, X->stream);
+    return selftest_msm_accumulate_t<G2R29, G2>(1, h_points, n_points, h_vals, n_vals, h_tasks, n_tasks, (uint8_t*)out, X->stream);
+}
+
 WS_DEFINE_WARM(msm)
 
 }  // namespace wsnark

@@ -230,6 +230,9 @@ int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t*
 // ---- curves ----
 // p, q: Jacobian-Montgomery triples in the reference format; result: XYZZ in the reference format (the form in
 // which every kernel hands its sums to the host), normalised by the host like an MSM result.
+// madd_fast / mmadd_fast exist where the field has the accumulation loop's wide forms: every one-lane curve but the paired G2 of the tails
+template <class C> struct StHasMaddFast { static constexpr bool value = true; };
+template <> struct StHasMaddFast<G2P29> { static constexpr bool value = false; };
 template <class C>
 __host__ __device__ inline typename C::PtP st_curve_op(int op, const typename C::Field::Packed* pj, const typename C::Field::Packed* qj, bool* ok) {
     typedef typename C::Field F;
@@ -267,6 +270,22 @@ __host__ __device__ inline typename C::PtP st_curve_op(int op, const typename C:
         // where it refuses), 11 = q where it accepts, infinity where it refuses
         case 10: r = from_jac(pj); (void)C::add_fast(r, from_jac(qj)); break;
         case 11: { Pt a = from_jac(pj); const Pt b = from_jac(qj); r = C::add_fast(a, b) ? b : C::infinity(); break; }
+        // one step of the accumulation loop's fast half as accumulate_range (msm.hip) takes it: an entry at infinity is refused by the
+        // loop's own test, every other one goes to madd_fast (12 / 13) or, p affine with z = 1, to mmadd_fast (14 / 15).  12 / 14 = the
+        // accumulator after the step, narrowed; 13 / 15 = q where the step accepted, infinity where it refused
+        case 12: case 13: case 14: case 15:
+            if constexpr (StHasMaddFast<C>::value) {
+                const Pt p0 = from_jac(pj);
+                const typename C::Aff a = affine_of(qj);
+                Pt acc = p0;
+                bool took = false;
+                if (!C::aff_is_inf(a)) took = op < 14 ? C::madd_fast(acc, a, false) : C::mmadd_fast(acc, typename C::Aff{p0.x, p0.y}, a, false);
+                C::narrow_x(acc);
+                r = (op & 1) ? (took ? C::from_affine(a) : C::infinity()) : acc;
+            } else {
+                *ok = false;
+            }
+            break;
         default: *ok = false; break;
     }
     return C::pt_from_internal(r);
@@ -429,7 +448,19 @@ int selftest_curve(int g, int impl, int op, const uint8_t* p, const uint8_t* q, 
     Context* X = ctx();
     if (!X) return WS_ERR_NOINIT;
     if (n == 0) return WS_OK;
-    if (n > (1u << 20) || op < 0 || op > 11 || op == 9 || (op == 8 && impl == 4)) return WS_ERR_ARG;
+    if (n > (1u << 20) || op < 0 || op > 15 || op == 9 || (op == 8 && impl == 4) || (op >= 12 && impl >= 4)) return WS_ERR_ARG;
+    if (op == 14 || op == 15) {          // mmadd_fast: the sum is still an affine point, z == 1 exactly
+        if (g != 1 && g != 2) return WS_ERR_ARG;
+        const Fq::El one1 = Fq::one();
+        const Fq2::El one2 = Fq2::one();
+        const size_t fs = g == 1 ? sizeof one1 : sizeof one2;
+        const void* one = g == 1 ? (const void*)&one1 : (const void*)&one2;
+        for (uint64_t i = 0; i < n; i++)
+            if (memcmp(p + (3 * i + 2) * fs, one, fs) != 0) {
+                set_last_error("selftest: ops 14 / 15 (mmadd_fast) take an affine p, z == 1");
+                return WS_ERR_ARG;
+            }
+    }
     if (g == 1 && impl == 5) return (op == 0 || op == 1 || op == 3 || op == 10 || op == 11) ? st_curve_pair_g1_dev(op, p, q, out, n, X->stream) : (int)WS_ERR_ARG;
     if (g == 2 && impl == 6) return (op == 0 || op == 1 || op == 3 || op == 10 || op == 11) ? st_curve_quad_g2_dev(op, p, q, out, n, X->stream) : (int)WS_ERR_ARG;
     hipStream_t s = X->stream;
