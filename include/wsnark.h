@@ -1234,6 +1234,27 @@ int wsnark_selftest_fp12(int impl, int op, const void* a, const void* b, void* o
 int wsnark_selftest_msm_plan(const void* scalars, uint64_t n, uint32_t table_c, uint32_t w_off, uint32_t w_stride, const void* mask,
                              uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
                              uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot);
+/* The geometry the MSM's host driver decides for a plan (csrc/msm.hip: msm_plan_geometry) -- the sum's shape, the grouping pass, the
+ * reduction tail --, from the size, the shard, the table's window width and the library's switches alone.  Pure host arithmetic: no
+ * device, no wsnark_init (tests/golden/msm_geometry.json pins the production shapes and both sides of every rule).
+ *   n        : pairs
+ *   table_c  : 0 = a per-window plan; 4 .. 22 = a flat fixed-base table plan of that window width; WSNARK_MSM_TABLE_C_AUTO = a table
+ *              plan of the width the library gives a resident key of n pairs (msm_table_window; WSNARK_TABLE_C overrides)
+ *   rank, world : the window shard; 0, 1 = every window
+ *   words    : WSNARK_MSM_GEOMETRY_WORDS words.
+ *              the sum's shape: [0] n, [1] c, [2] windows of the whole scalar, [3] owned windows, [4] w_off, [5] w_stride, [6] NB = 2^(c-1),
+ *                [7] buckets, [8] flat, [9] task cap lmax, [10] hot-bucket threshold, [11] capacity of the task list;
+ *              the grouping pass: [12] low bucket bits per bin, [13] index bits of an entry, [14] bins, [15] threads of the per-bin sort (0:
+ *                msm_plan_finish sets it), [16] bins per bucket set, [17] scalars per workgroup, [18] its threads, [19] the plan has a grouping pass (1), [20] 4-byte entries;
+ *              the reduction tail: [21] pieces, [22] buckets per piece, [23] pieces per group, [24] groups, [25] buckets per chunk,
+ *                [26] chunks folded by the second level (1: none), [27] their product m, [28] chunk pairs per piece, [29] pairs the trees
+ *                see J, [30] ceil(log2 J), [31] rows per piece, [32] rows per group that reach the host, [33] rows folded on the GPU.
+ *              All zero on an error, for n == 0 and for a shard that owns no window.
+ * Returns what msm_plan_geometry returns: WSNARK_ERR_SIZE (n > 2^28, n x owned windows >= 2^32, table rows x n >= 2^31, more bins
+ * than the grouping pass has counters for), WSNARK_ERR_ARG (world == 0, a width outside 2 .. 22). */
+#define WSNARK_MSM_GEOMETRY_WORDS 34
+#define WSNARK_MSM_TABLE_C_AUTO 0xFFFFFFFFu
+int wsnark_selftest_msm_geometry(uint64_t n, uint32_t table_c, uint32_t rank, uint32_t world, uint32_t* words);
 /* The MSM's accumulation kernel (csrc/msm.hip: msm_accumulate, the __global__ function every sum launches) on tasks the caller wrote,
  * so that a test decides which entry meets which running sum (tests/accumulate_patterns.py holds the model of the loop's branches).
  *   g       : 1 or 2

@@ -29,7 +29,7 @@ SYMBOLS = [
     "wsnark_synth_new", "wsnark_synth_free", "wsnark_synth_info", "wsnark_synth_witness", "wsnark_synth_pols",
     "wsnark_synth_key_scalars", "wsnark_synth_expected",
     "wsnark_selftest_field", "wsnark_selftest_curve", "wsnark_selftest_fp12", "wsnark_selftest_field29", "wsnark_selftest_msm_plan",
-    "wsnark_selftest_msm_accumulate",
+    "wsnark_selftest_msm_geometry", "wsnark_selftest_msm_accumulate",
     "wsnark_timing_enable", "wsnark_timing_reset", "wsnark_timing_report", "wsnark_peak_probe", "wsnark_tuning_set", "wsnark_host_alloc", "wsnark_host_free",
     "wsnark_points_load", "wsnark_points_free", "wsnark_points_info", "wsnark_points_msm", "wsnark_points_msm_dev",
     "wsnark_group_create", "wsnark_group_free", "wsnark_group_size", "wsnark_group_pkey_load", "wsnark_group_pkey_load_sections", "wsnark_group_pkey_load_file", "wsnark_group_pkey_free",
@@ -184,7 +184,8 @@ class Lib:
         c.wsnark_selftest_curve.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, u64]
         c.wsnark_selftest_field29.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, u64]
         c.wsnark_selftest_msm_plan.argtypes = [vp, u64, u32, u32, u32, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64]
-        c.wsnark_selftest_msm_accumulate.argtypes = [C.c_int, vp, u64, vp, u64, vp, u64, vp]
+        c.wsnark_selftest_msm_geometry.argtypes = [u64, u32, u32, u32, vp]
+        c.wsnark_selftest_msm_accumulate.argtypes =[C.c_int, vp, u64, vp, u64, vp, u64, vp]
         c.wsnark_groth16_prove_finish.argtypes = [vp, vp, u64, vp, vp, vp]
         c.wsnark_g1_mul_base_batch.argtypes = [vp, vp, u64, vp]
         c.wsnark_g2_mul_base_batch.argtypes = [vp, vp, u64, vp]

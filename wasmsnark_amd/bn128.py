@@ -1093,6 +1093,20 @@ class Bn128:
         return {"info": w2, "bstart": bs[:w2["nbuckets"]], "bend": be[:w2["nbuckets"]], "vals": vals[:w2["nvals"]],
                 "tasks": rec(tasks, 3, w2["tasks"]), "multi": rec(multi, 3, w2["multi_buckets"]), "hot": rec(hot, 8, w2["hot_buckets"])}
 
+    # --- test hook (no reference counterpart): the geometry the MSM's host driver decides for a plan; no device, no init ---
+    MSM_GEOMETRY = ("n", "c", "Wall", "W", "w_off", "w_stride", "NB", "nbuckets", "flat", "lmax", "hot_min", "hot_cap",
+                    "lo_bits", "idx_bits", "nbins", "bthr", "HB", "tile", "thr", "ps_valid", "e32",
+                    "tW", "tNB", "tP", "groups", "m1", "m2", "m", "J1", "J", "logJ", "nsum", "nrows", "reduce")
+    MSM_TABLE_C_AUTO = 0xFFFFFFFF
+
+    def msm_geometry(self, n, table_c=0, shard=None):
+        """wsnark_selftest_msm_geometry: (rc, {name: word}) for a plan of n pairs -- rc is the library's code (0 = WSNARK_OK), not
+        raised: the error rows are part of what a test pins.  table_c: 0, a width, or MSM_TABLE_C_AUTO; shard=(rank, world)."""
+        off, stride = shard or (0, 1)
+        words = (C.c_uint32 * len(self.MSM_GEOMETRY))()
+        rc = self.lib.c.wsnark_selftest_msm_geometry(n, table_c, off, stride, words)
+        return rc, dict(zip(self.MSM_GEOMETRY, words[:]))
+
     # --- test hook (no reference counterpart): the accumulation kernel itself on tasks the caller wrote ---
     def selftest_msm_accumulate(self, g, points, vals, tasks, out=None):
         """wsnark_selftest_msm_accumulate: msm_accumulate over `points` (affine Montgomery bytes, 64 / 128 B each), `vals` (words

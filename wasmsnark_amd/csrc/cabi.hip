@@ -772,6 +772,12 @@ int wsnark_selftest_msm_plan(const void* scalars, uint64_t n, uint32_t table_c, 
                              vals, cap_vals, tasks, cap_tasks, multi, cap_multi, hot, cap_hot);
 }
 
+int wsnark_selftest_msm_geometry(uint64_t n, uint32_t table_c, uint32_t rank, uint32_t world, uint32_t* words) {
+    static_assert(WSNARK_MSM_GEOMETRY_WORDS == kMsmGeometryWords && WSNARK_MSM_TABLE_C_AUTO == kMsmTableAuto, "words of the geometry hook");
+    if (!words) return WSNARK_ERR_ARG;
+    return selftest_msm_geometry(n, table_c, WindowShard{rank, world}, words);      // (no context: the geometry is host arithmetic)
+}
+
 int wsnark_selftest_msm_accumulate(int g, const void* points, uint64_t n_points, const uint32_t* vals, uint64_t n_vals, const uint32_t* tasks,
                                    uint64_t n_tasks, void* out) {
     REQUIRE_CTX();

@@ -374,8 +374,6 @@ int calc_h_dev(Lane& L, const Fe* d_signals_plain, uint32_t n_signals, const Csr
     // inverse of the reference needs 2*domain <= 2^28
     if (domain < 2 || (domain & (domain - 1)) || domain > (1u << 27)) return WS_ERR_SIZE;
     if (A.n_rows != domain || B.n_rows != domain || A.n_cols != n_signals || B.n_cols != n_signals) return WS_ERR_ARG;
-    int bits = 0;
-    while ((1u << bits) < domain) bits++;
     const size_t nb = (size_t)domain * sizeof(Fe);
     ScratchGuard scratch_turn(L.calch_chain, s);   // the work arrays below are shared by every CALC_H on this lane
     // a and b back to back: their two inverse and their two coset transforms run as ONE batch of two each (round 6: a 2^20 pass

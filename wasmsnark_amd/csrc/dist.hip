@@ -139,8 +139,7 @@ static int dist_ntt_native(Lane& L, const DistComm& cm, Fe* x, Fe* y, uint32_t l
 // grow-only reserves of the lane's buffers.  groth16_prove_dist calls it before its first collective and ships the result.
 int calc_h_dist_reserve(Lane& L, const DistComm& cm, uint32_t n_signals, uint32_t domain, uint32_t l2_expected) {
     if (domain < 2 || (domain & (domain - 1)) || domain > (1u << 27)) return WS_ERR_SIZE;
-    uint32_t log_n = 0;
-    while ((1u << log_n) < domain) log_n++;
+    const uint32_t log_n = ceil_log2(domain);
     const uint32_t l1 = (log_n + 1) / 2, l2 = log_n - l1, P = cm.world;
     if ((P & (P - 1)) || ((uint64_t)1 << l2) < P) { set_last_error("prove_dist: needs a power-of-two world size <= 2^floor(log2(domain)/2)"); return WS_ERR_SIZE; }
     if (l2 != l2_expected) { set_last_error("prove_dist: the handle's hExps interleave does not match this domain (load the shard with h_interleave_log = floor(log2(domain) / 2))"); return WS_ERR_ARG; }
@@ -160,8 +159,7 @@ int calc_h_dist(Lane& L, const DistComm& cm, const Fe* d_signals_plain, uint32_t
     if (A.n_rows != domain || B.n_rows != domain || A.n_cols != n_signals || B.n_cols != n_signals) return WS_ERR_ARG;
     int rc0 = calc_h_dist_reserve(L, cm, n_signals, domain, l2_expected);      // (no-ops after the caller's preflight)
     if (rc0) return rc0;
-    uint32_t log_n = 0;
-    while ((1u << log_n) < domain) log_n++;
+    const uint32_t log_n = ceil_log2(domain);
     const uint32_t l1 = (log_n + 1) / 2, l2 = log_n - l1, P = cm.world;
     const uint64_t n_loc = domain / P;
     ScratchGuard scratch_turn(L.calch_chain, s);

@@ -54,6 +54,9 @@ struct ScratchGuard {
     }
 };
 
+// ceil(log2 v): the least x with 2^x >= v (0 for v <= 1)
+static inline uint32_t ceil_log2(uint64_t v) { uint32_t x = 0; while (((uint64_t)1 << x) < v) x++; return x; }
+
 struct NttPlan;       // ntt.hip
 struct MsmWorkspace;  // msm.hip
 
@@ -294,6 +297,9 @@ static const uint32_t kMsmPlanInfoWords = 24;
 int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table_c, WindowShard sh, const uint8_t* h_mask,
                       uint32_t* info, uint32_t* bstart, uint32_t* bend, uint64_t cap_buckets, uint32_t* vals, uint64_t cap_vals,
                       uint32_t* tasks, uint64_t cap_tasks, uint32_t* multi, uint64_t cap_multi, uint32_t* hot, uint64_t cap_hot);
+// test hook (wsnark_selftest_msm_geometry): what msm_plan_geometry decides, as words; no context.  kMsmTableAuto: msm_table_window(n)
+static const uint32_t kMsmGeometryWords = 34, kMsmTableAuto = 0xFFFFFFFFu;
+int selftest_msm_geometry(uint64_t n, uint32_t table_c, WindowShard sh, uint32_t* words);
 // test hook (wsnark_selftest_msm_accumulate): msm_accumulate itself on caller-written tasks (g: 1 or 2; tasks: n_tasks x (start, len));
 // arguments are checked on the host before anything is launched; own buffers; waits for the queue
 int selftest_msm_accumulate(int g, const void* h_points, uint64_t n_points, const uint32_t* h_vals, uint64_t n_vals, const uint32_t* h_tasks,

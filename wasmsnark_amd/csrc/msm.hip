@@ -1118,29 +1118,44 @@ static uint32_t pick_window(uint64_t n) {
 }
 
 // ---- phase 1 (independent of the points and of the curve): digits, sort, bounds, task list ----
-struct MsmPlanInfo {
+// A plan's description, by what owns each field; msm_plan_geometry decides the first three parts.
+struct MsmShape {                 // the sum's shape
     uint64_t n = 0;
-    uint32_t c = 0, W = 0, NB = 0, nbuckets = 0, m = 0, J = 0, logJ = 0, nsum = 0, lmax = 0, hot_cap = 0;
-    uint32_t hot_min = 1024;
-    uint32_t ps_lo_bits = 0, ps_idx_bits = 0, ps_nbins = 0, ps_bthr = 0;   // grouping pass geometry (presort plans)
-    uint32_t ps_HB = 0, ps_tile = 0, ps_thr = 0;
-    bool ps_valid = false, ps_e32 = false;
-    bool building = false;        // between msm_plan_begin and msm_plan_finish: the digit histogram is being taken
-    uint32_t Wall = 0, w_off = 0, w_stride = 1;   // W = owned windows; Wall = windows of the whole scalar
+    uint32_t c = 0, Wall = 0, W = 0, w_off = 0, w_stride = 1;   // W = owned windows; Wall = windows of the whole scalar
+    uint32_t NB = 0, nbuckets = 0, lmax = 0, hot_min = 1024, hot_cap = 0;
     // fixed-base table plans (flat): the points array holds Wall rows of n points, row w = 2^(c w) * row 0, so every window's
-    // digits go into ONE set of NB buckets and no doubling is left for the tail.  For the reduction tail the bucket set is
-    // cut into tW pieces of tNB buckets ("windows" of the chunk/tree kernels; classic plans: tW = W, tNB = NB).
+    // digits go into ONE set of NB buckets and no doubling is left for the tail.
     bool flat = false;
+};
+static const uint32_t PRESORT_TILE = 1024, PRESORT_THREADS = 1024;      // scalars per workgroup of presort_count / presort_scatter*, and its threads
+struct MsmGrouping {              // grouping pass geometry (presort plans); bthr: msm_plan_finish's, threads of the per-bin sort
+    uint32_t lo_bits = 0, idx_bits = 0, nbins = 0, bthr = 0, HB = 0;
+    uint32_t tile = PRESORT_TILE, thr = PRESORT_THREADS;
+    bool valid = false, e32 = false;
+};
+struct MsmTail {                  // reduction-tail geometry
+    // the bucket set is cut into tW pieces of tNB buckets ("windows" of the chunk/tree kernels; classic plans: tW = W, tNB = NB)
     uint32_t tW = 0, tNB = 0;
     // round 4: a group (the one bucket set of a table plan; a window of a per-window plan) is cut into tP pieces of tNB buckets;
     // with `reduce` the pieces' rows are folded on the GPU (msm_rows) and nrows = logJ + 1 + log2(tP) rows per GROUP reach the
     // host, otherwise nsum rows per PIECE do (the round-2 / 3 arrangement, TAIL_REDUCE=0)
     uint32_t tP = 1, groups = 1, nrows = 0;
-    bool reduce = false;
+    uint32_t reduce = 0;          // 0 / 1 (a word like the rest: no padding, see operator==)
     // round 6 (closing): a SECOND chunk level (msm_chunks2).  msm_chunks leaves J1 = tNB / m1 chunk pairs per piece; msm_chunks2 folds m2
     // of them into one, so that the trees see J = J1 / m2 pairs of m = m1 m2 buckets.  m2 = 1: no second level (m = m1, J = J1).
-    uint32_t m1 = 0, m2 = 1, J1 = 0;
-    uint32_t ntasks = 0, nmulti = 0;
+    uint32_t m1 = 0, m2 = 1, m = 0, J1 = 0, J = 0, logJ = 0, nsum = 0;
+    // every byte: a field added above cannot be forgotten here (two launches share a tail only if their geometries are equal)
+    bool operator==(const MsmTail& o) const {
+        static_assert(std::has_unique_object_representations<MsmTail>::value, "bytewise comparison: integer fields, no padding");
+        return memcmp(this, &o, sizeof *this) == 0;
+    }
+};
+struct MsmPlanInfo {
+    MsmShape shape;
+    MsmGrouping ps;
+    MsmTail tail;
+    bool building = false;        // between msm_plan_begin and msm_plan_finish: the digit histogram is being taken
+    uint32_t ntasks = 0;
     bool valid = false;
 };
 // ---- asynchronous completion: the last kernel's W x nsum window sums are copied to pinned host memory
@@ -1208,113 +1223,103 @@ void msm_abort_slots(Lane& L, const int* slots, int nslots, hipStream_t a, hipSt
         if (slots[k] >= 0 && slots[k] < kPendingSlots) L.msm->slot[slots[k]].active = false;
 }
 
+// ---- the host's Horner chains over the rows a tail has left in pinned memory (msm_finish_t picks one).  Three forms, kept apart on
+// purpose: the XYZZ coordinates the host returns depend on the exact sequence of H::dbl / H::add, not only on the group element. ----
+// table plans with the pieces folded on the GPU (msm_rows): R_A + m sum_q 2^q R_q + tNB sum_p 2^p V_p -- two short Horner
+// chains over logJ + 1 + log2(tP) rows, c - 1 doublings in all
+template <class H, class HPt = typename H::Pt>
+static HPt horner_table_folded(const MsmTail& G, const HPt* sums) {
+    const uint32_t logm = ceil_log2(G.m), logt = ceil_log2(G.tNB), logP = ceil_log2(G.tP);
+    HPt acc = H::infinity();
+    for (int q = (int)G.logJ - 1; q >= 0; q--) acc = H::add(H::dbl(acc), sums[q]);
+    if (G.m2 > 1) {
+        // second chunk level: R_A' + m1 R_W + m sum_q 2^q R_q -- the W row (the last one) joins the chain at weight m1
+        const uint32_t logm1 = ceil_log2(G.m1);
+        for (uint32_t k = logm1; k < logm; k++) acc = H::dbl(acc);
+        acc = H::add(acc, sums[G.logJ + 1 + logP]);
+        for (uint32_t k = 0; k < logm1; k++) acc = H::dbl(acc);
+    } else {
+        for (uint32_t k = 0; k < logm; k++) acc = H::dbl(acc);
+    }
+    acc = H::add(acc, sums[G.logJ]);
+    HPt tot = H::infinity();
+    for (int pb = (int)logP - 1; pb >= 0; pb--) tot = H::add(H::dbl(tot), sums[G.logJ + 1 + (uint32_t)pb]);
+    for (uint32_t k = 0; k < logt; k++) tot = H::dbl(tot);
+    return H::add(acc, tot);
+}
+// table plans by pieces: sum_b (b+1) B_b over ONE bucket set, b = v*tNB + u:  sum_v [ A_v + m sum_q 2^q U_{v,q} ] + tNB sum_v v T_v
+// (rows per piece v: U_{v,0..logJ-1}, A_v, T_v = sum of the piece's buckets).  The pieces are summed row-wise first,
+// so the doubling chain is c - 1 long whatever the number of pieces.
+template <class H, class HPt = typename H::Pt>
+static HPt horner_table_pieces(const MsmTail& G, const HPt* sums) {
+    const uint32_t logm = ceil_log2(G.m), logt = ceil_log2(G.tNB);
+    HPt acc = H::infinity();
+    for (int q = (int)G.logJ - 1; q >= 0; q--) {
+        acc = H::dbl(acc);
+        for (uint32_t v = 0; v < G.tW; v++) acc = H::add(acc, sums[(size_t)v * G.nsum + q]);
+    }
+    for (uint32_t k = 0; k < logm; k++) acc = H::dbl(acc);
+    for (uint32_t v = 0; v < G.tW; v++) acc = H::add(acc, sums[(size_t)v * G.nsum + G.logJ]);
+    if (G.tW > 1) {
+        HPt run = H::infinity(), tot = H::infinity();
+        for (uint32_t v = G.tW - 1; v >= 1; v--) {
+            run = H::add(run, sums[(size_t)v * G.nsum + G.logJ + 1]);
+            tot = H::add(tot, run);
+        }
+        for (uint32_t k = 0; k < logt; k++) tot = H::dbl(tot);
+        acc = H::add(acc, tot);
+    }
+    return acc;
+}
+// 8. per-window plans: result = sum_w 2^(c w) [ A_w + m * sum_q 2^q U_{w,q} ].  ONE Horner chain over the bit
+// positions of the whole scalar (MSB first): U_{w,q} sits at bit c*w + log2(m) + q, A_w at bit c*w, and
+// log2(m) + logJ = c - 1, so every window's terms fall inside its own c positions: c*Wall doublings and
+// (logJ + 1) additions per owned window -- no per-window inner chain.
+template <class H, class HPt = typename H::Pt>
+static HPt horner_windows(const MsmShape& Sh, const MsmTail& G, const HPt* sums) {
+    const uint32_t logm = ceil_log2(G.m), logt = ceil_log2(G.tNB), logP = ceil_log2(G.tP);
+    // (windows cut into pieces, rows folded by msm_rows: V_{w,p} = sum_{v: bit p} T_{w,v} sits at bit c*w + log2(tNB) + p)
+    const uint32_t rows_per_window = G.reduce ? G.nrows : G.nsum;
+    HPt acc = H::infinity();
+    bool started = false;                                  // leading doublings of infinity are skipped
+    for (int wg = (int)Sh.Wall - 1; wg >= 0; wg--) {      // global window index; rows exist for the owned ones
+        const bool owned = (uint32_t)wg >= Sh.w_off && ((uint32_t)wg - Sh.w_off) % Sh.w_stride == 0;
+        const uint32_t krow = owned ? ((uint32_t)wg - Sh.w_off) / Sh.w_stride : 0;
+        const HPt* row = owned ? &sums[(size_t)krow * rows_per_window] : nullptr;
+        for (int k = (int)Sh.c - 1; k >= 0; k--) {
+            if (started) acc = H::dbl(acc);
+            if (!owned) continue;
+            if (G.reduce && (uint32_t)k >= logt && (uint32_t)k - logt < logP) { acc = H::add(acc, row[G.logJ + 1 + (uint32_t)k - logt]); started = true; }
+            if ((uint32_t)k >= logm && (uint32_t)k - logm < G.logJ) { acc = H::add(acc, row[(uint32_t)k - logm]); started = true; }
+            if (k == 0) { acc = H::add(acc, row[G.logJ]); started = true; }
+        }
+    }
+    return acc;
+}
+
 template <class H>
 static int msm_finish_t(MsmPending& P, typename H::Pt* out_host) {
     typedef typename H::Pt HPt;
-    const MsmPlanInfo& I = P.info;
-    if (I.n == 0) { *out_host = H::infinity(); P.active = false; return WS_OK; }
+    const MsmShape& Sh = P.info.shape;
+    const MsmTail& G = P.info.tail;
+    if (Sh.n == 0) { *out_host = H::infinity(); P.active = false; return WS_OK; }
     struct Done { MsmPending& p; ~Done() { p.active = false; } } done{P};   // the slot is free again whatever happens
-    const bool trace = tuning_get("TRACE", 0) == 1;
     const auto t_wait = std::chrono::steady_clock::now();
     WS_HIP_CHECK(hipEventSynchronize(P.ev));
     const auto t_tail = std::chrono::steady_clock::now();
     const HPt* sums = reinterpret_cast<const HPt*>(P.h_sums);
-    if (I.flat && I.reduce) {
-        // table plans with the pieces folded on the GPU (msm_rows): R_A + m sum_q 2^q R_q + tNB sum_p 2^p V_p -- two short Horner
-        // chains over logJ + 1 + log2(tP) rows, c - 1 doublings in all
-        uint32_t logm = 0, logt = 0, logP = 0;
-        while ((1u << logm) < I.m) logm++;
-        while ((1u << logt) < I.tNB) logt++;
-        while ((1u << logP) < I.tP) logP++;
-        HPt acc = H::infinity();
-        for (int q = (int)I.logJ - 1; q >= 0; q--) acc = H::add(H::dbl(acc), sums[q]);
-        if (I.m2 > 1) {
-            // second chunk level: R_A' + m1 R_W + m sum_q 2^q R_q -- the W row (the last one) joins the chain at weight m1
-            uint32_t logm1 = 0;
-            while ((1u << logm1) < I.m1) logm1++;
-            for (uint32_t k = logm1; k < logm; k++) acc = H::dbl(acc);
-            acc = H::add(acc, sums[I.logJ + 1 + logP]);
-            for (uint32_t k = 0; k < logm1; k++) acc = H::dbl(acc);
-        } else {
-            for (uint32_t k = 0; k < logm; k++) acc = H::dbl(acc);
-        }
-        acc = H::add(acc, sums[I.logJ]);
-        HPt tot = H::infinity();
-        for (int pb = (int)logP - 1; pb >= 0; pb--) tot = H::add(H::dbl(tot), sums[I.logJ + 1 + (uint32_t)pb]);
-        for (uint32_t k = 0; k < logt; k++) tot = H::dbl(tot);
-        *out_host = H::add(acc, tot);
-        if (trace)
-            fprintf(stderr, "[wsnark trace]   msm finish (%s, table, rows folded on the GPU): waited %.3f ms for the GPU, host tail %.3f ms\n", sizeof(HPt) > 128 ? "G2" : "G1",
-                    std::chrono::duration<double, std::milli>(t_tail - t_wait).count(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count());
-        return WS_OK;
-    }
-    if (I.flat) {
-        // table plans: sum_b (b+1) B_b over ONE bucket set, b = v*tNB + u:  sum_v [ A_v + m sum_q 2^q U_{v,q} ] + tNB sum_v v T_v
-        // (rows per piece v: U_{v,0..logJ-1}, A_v, T_v = sum of the piece's buckets).  The pieces are summed row-wise first,
-        // so the doubling chain is c - 1 long whatever the number of pieces.
-        uint32_t logm = 0, logt = 0;
-        while ((1u << logm) < I.m) logm++;
-        while ((1u << logt) < I.tNB) logt++;
-        HPt acc = H::infinity();
-        for (int q = (int)I.logJ - 1; q >= 0; q--) {
-            acc = H::dbl(acc);
-            for (uint32_t v = 0; v < I.tW; v++) acc = H::add(acc, sums[(size_t)v * I.nsum + q]);
-        }
-        for (uint32_t k = 0; k < logm; k++) acc = H::dbl(acc);
-        for (uint32_t v = 0; v < I.tW; v++) acc = H::add(acc, sums[(size_t)v * I.nsum + I.logJ]);
-        if (I.tW > 1) {
-            HPt run = H::infinity(), tot = H::infinity();
-            for (uint32_t v = I.tW - 1; v >= 1; v--) {
-                run = H::add(run, sums[(size_t)v * I.nsum + I.logJ + 1]);
-                tot = H::add(tot, run);
-            }
-            for (uint32_t k = 0; k < logt; k++) tot = H::dbl(tot);
-            acc = H::add(acc, tot);
-        }
-        *out_host = acc;
-        if (trace)
-            fprintf(stderr, "[wsnark trace]   msm finish (%s, table): waited %.3f ms for the GPU, host tail %.3f ms\n", sizeof(HPt) > 128 ? "G2" : "G1",
-                    std::chrono::duration<double, std::milli>(t_tail - t_wait).count(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count());
-        return WS_OK;
-    }
-    // 8. host tail: result = sum_w 2^(c w) [ A_w + m * sum_q 2^q U_{w,q} ].  ONE Horner chain over the bit
-    // positions of the whole scalar (MSB first): U_{w,q} sits at bit c*w + log2(m) + q, A_w at bit c*w, and
-    // log2(m) + logJ = c - 1, so every window's terms fall inside its own c positions: c*Wall doublings and
-    // (logJ + 1) additions per owned window -- no per-window inner chain.
-    uint32_t logm = 0, logt = 0, logP = 0;
-    while ((1u << logm) < I.m) logm++;
-    while ((1u << logt) < I.tNB) logt++;
-    while ((1u << logP) < I.tP) logP++;
-    // (windows cut into pieces, rows folded by msm_rows: V_{w,p} = sum_{v: bit p} T_{w,v} sits at bit c*w + log2(tNB) + p)
-    const uint32_t rows_per_window = I.reduce ? I.nrows : I.nsum;
-    HPt acc = H::infinity();
-    bool started = false;                                  // leading doublings of infinity are skipped
-    for (int wg = (int)I.Wall - 1; wg >= 0; wg--) {      // global window index; rows exist for the owned ones
-        const bool owned = (uint32_t)wg >= I.w_off && ((uint32_t)wg - I.w_off) % I.w_stride == 0;
-        const uint32_t krow = owned ? ((uint32_t)wg - I.w_off) / I.w_stride : 0;
-        const HPt* row = owned ? &sums[(size_t)krow * rows_per_window] : nullptr;
-        for (int k = (int)I.c - 1; k >= 0; k--) {
-            if (started) acc = H::dbl(acc);
-            if (!owned) continue;
-            if (I.reduce && (uint32_t)k >= logt && (uint32_t)k - logt < logP) { acc = H::add(acc, row[I.logJ + 1 + (uint32_t)k - logt]); started = true; }
-            if ((uint32_t)k >= logm && (uint32_t)k - logm < I.logJ) { acc = H::add(acc, row[(uint32_t)k - logm]); started = true; }
-            if (k == 0) { acc = H::add(acc, row[I.logJ]); started = true; }
-        }
-    }
-    *out_host = acc;
-    if (trace)
-        fprintf(stderr, "[wsnark trace]   msm finish (%s): waited %.3f ms for the GPU, host Horner %.3f ms\n", sizeof(HPt) > 128 ? "G2" : "G1",
-                std::chrono::duration<double, std::milli>(t_tail - t_wait).count(),
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count());
+    *out_host = (Sh.flat && G.reduce) ? horner_table_folded<H>(G, sums) : Sh.flat ? horner_table_pieces<H>(G, sums) : horner_windows<H>(Sh, G, sums);
+    if (tuning_get("TRACE", 0) == 1)
+        fprintf(stderr, "[wsnark trace]   msm finish (%s%s): waited %.3f ms for the GPU, host %s %.3f ms\n", sizeof(HPt) > 128 ? "G2" : "G1",
+                (Sh.flat && G.reduce) ? ", table, rows folded on the GPU" : Sh.flat ? ", table" : "", std::chrono::duration<double, std::milli>(t_tail - t_wait).count(),
+                Sh.flat ? "tail" : "Horner", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count());
     return WS_OK;
 }
 
 // launches that still read plan `plan_id`'s buffers on their own streams must finish before the buffers are rewritten
 static int wait_plan_users(MsmWorkspace& M, int plan_id, hipStream_t s) {
     for (auto& p : M.slot)
-        if (p.active && p.ev && p.info.n && p.plan_id == plan_id) WS_HIP_CHECK(hipStreamWaitEvent(s, p.ev, 0));
+        if (p.active && p.ev && p.info.shape.n && p.plan_id == plan_id) WS_HIP_CHECK(hipStreamWaitEvent(s, p.ev, 0));
     return WS_OK;
 }
 
@@ -1340,19 +1345,19 @@ uint32_t msm_table_window(uint64_t n) {
 
 // The plan in three steps, so that the FIRST pass over the scalars -- the digit histogram -- can run on parts of the vector
 // while the rest is still on its way to the device (prove.hip: a witness uploaded chunk by chunk):
-//   msm_plan_begin   geometry, buffers, cleared counters
+//   msm_plan_begin   geometry (msm_plan_geometry), buffers, cleared counters
 //   msm_plan_count   histogram of the scalars [i0, i1) (any number of calls that together cover [0, n), on queues ordered
 //                    before the one msm_plan_finish runs on)
 //   msm_plan_finish  scan, scatter, per-bin sort, task list
 // msm_plan_dev is the three in a row.
-int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t table_c) {
-    Context* X = ctx();
-    if (!X) return WS_ERR_NOINIT;
-    if (!s) s = L.stream;
-    MsmWorkspace& M = ws(L);
-    MsmPlanInfo& I = M.plan[M.cur].info;
-    I = MsmPlanInfo();
-    if (n == 0) { I.valid = true; return WS_OK; }
+// msm_plan_geometry: every decision about a plan's shape, grouping pass and reduction tail, from the size, the shard, the table's
+// window width and the runtime switches alone -- no HIP call, no lane, no workspace (wsnark_selftest_msm_geometry returns it as is;
+// tests/golden/msm_geometry.json pins it).  An empty plan (n == 0, or a rank that owns no window) comes back valid with n == 0.
+static int msm_plan_geometry(uint64_t n, WindowShard sh, uint32_t table_c, MsmPlanInfo* info) {
+    *info = MsmPlanInfo();
+    MsmShape& I = info->shape;
+    MsmTail& G = info->tail;
+    if (n == 0) { info->valid = true; return WS_OK; }
     if (n > ((uint64_t)1 << 28)) return WS_ERR_SIZE;
     if (sh.stride == 0) return WS_ERR_ARG;
     I.n = n;
@@ -1364,7 +1369,7 @@ int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t 
     I.w_off = sh.off;
     I.w_stride = sh.stride;
     I.W = I.w_off < I.Wall ? (I.Wall - I.w_off + I.w_stride - 1) / I.w_stride : 0;
-    if (I.W == 0) { I.n = 0; I.valid = true; return WS_OK; }   // this rank owns no window: partial = infinity
+    if (I.W == 0) { I.n = 0; info->valid = true; return WS_OK; }   // this rank owns no window: partial = infinity
     I.NB = 1u << (I.c - 1);
     I.nbuckets = I.flat ? I.NB : I.W * I.NB;
     const uint64_t total = n * I.W;
@@ -1378,37 +1383,28 @@ int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t 
     const bool big_set = I.NB >= (1u << 18);
     uint32_t chunk = (I.flat && !big_set) ? 4u : CHUNK;
     { const long v = tuning_get("MSM_CHUNK", 0); if (v == 2 || v == 4 || v == 8 || v == 16 || v == 32) chunk = (uint32_t)v; }
-    {
-        uint32_t tbits = I.flat ? (big_set ? 15u : 11u) : 31u;      // buckets per tail piece; per-window plans: the whole window
-        { const long v = tuning_get("TAIL_BITS", 0); if (v >= 3 && v <= 20) tbits = (uint32_t)v; }
-        I.tNB = (tbits >= 31 || I.NB < (1u << tbits)) ? I.NB : (1u << tbits);
-        I.tP = I.NB / I.tNB;
-        if (I.tP > 256) { I.tP = 256; I.tNB = I.NB / 256; }        // (msm_rows folds a group's pieces in one workgroup)
-        I.groups = I.flat ? 1 : I.W;
-        I.tW = I.groups * I.tP;
-    }
-    I.m1 = I.tNB < chunk ? I.tNB : chunk;
-    I.J1 = I.tNB / I.m1;
-    I.m2 = 1;
-    {
-        // Second chunk level for the bucket sets of table plans from 2^17 buckets on: the masked tree rows cost (logJ / 2 + 2) J additions per piece,
-        // i.e. half of what msm_chunks itself does at J = 4096, on workgroups that spend most of their time in a nine-step LDS tree; a
-        // second running sum over m2 chunk pairs costs 3 additions per pair and leaves the trees 1 / m2 of their elements.
-        // WSNARK_TAIL_L2 = 1 / 2 / 4 / 8 (1: off); A/B: profiles/r06_tail_l2_ab.txt
-        // (table plans whose pieces' rows are folded on the GPU: the host branch that knows the W row, msm_finish_t)
-        long v = tuning_get("TAIL_L2", (I.flat && I.NB >= (1u << 17)) ? WS_TAIL_L2_DEFAULT : 1);      // (2^16 buckets and fewer: no gain measured, call c47 / c48)
-        if ((v == 2 || v == 4 || v == 8) && I.flat && I.tP > 1 && I.J1 >= 8u * (uint32_t)v) I.m2 = (uint32_t)v;      // (the trees keep at least eight pairs)
-    }
-    I.m = I.m1 * I.m2;
-    I.J = I.J1 / I.m2;
-    while ((1u << I.logJ) < I.J) I.logJ++;
-    I.nsum = I.logJ + 1 + ((I.flat || I.tP > 1) ? 1 : 0) + (I.m2 > 1 ? 1 : 0);      // U_0 .. U_{logJ-1}, A [, T [, W]]
-    I.reduce = I.tP > 1;
-    {
-        uint32_t logP = 0;
-        while ((1u << logP) < I.tP) logP++;
-        I.nrows = I.reduce ? I.logJ + 1 + logP + (I.m2 > 1 ? 1 : 0) : I.nsum;      // (the W row of a second chunk level comes last)
-    }
+    uint32_t tbits = I.flat ? (big_set ? 15u : 11u) : 31u;      // buckets per tail piece; per-window plans: the whole window
+    { const long v = tuning_get("TAIL_BITS", 0); if (v >= 3 && v <= 20) tbits = (uint32_t)v; }
+    G.tNB = (tbits >= 31 || I.NB < (1u << tbits)) ? I.NB : (1u << tbits);
+    G.tP = I.NB / G.tNB;
+    if (G.tP > 256) { G.tP = 256; G.tNB = I.NB / 256; }        // (msm_rows folds a group's pieces in one workgroup)
+    G.groups = I.flat ? 1 : I.W;
+    G.tW = G.groups * G.tP;
+    G.m1 = G.tNB < chunk ? G.tNB : chunk;
+    G.J1 = G.tNB / G.m1;
+    // Second chunk level for the bucket sets of table plans from 2^17 buckets on: the masked tree rows cost (logJ / 2 + 2) J additions per piece,
+    // i.e. half of what msm_chunks itself does at J = 4096, on workgroups that spend most of their time in a nine-step LDS tree; a
+    // second running sum over m2 chunk pairs costs 3 additions per pair and leaves the trees 1 / m2 of their elements.
+    // WSNARK_TAIL_L2 = 1 / 2 / 4 / 8 (1: off); A/B: profiles/r06_tail_l2_ab.txt
+    // (table plans whose pieces' rows are folded on the GPU: the host chain that knows the W row, horner_table_folded)
+    const long l2 = tuning_get("TAIL_L2", (I.flat && I.NB >= (1u << 17)) ? WS_TAIL_L2_DEFAULT : 1);      // (2^16 buckets and fewer: no gain measured, call c47 / c48)
+    if ((l2 == 2 || l2 == 4 || l2 == 8) && I.flat && G.tP > 1 && G.J1 >= 8u * (uint32_t)l2) G.m2 = (uint32_t)l2;      // (the trees keep at least eight pairs)
+    G.m = G.m1 * G.m2;
+    G.J = G.J1 / G.m2;
+    G.logJ = ceil_log2(G.J);
+    G.nsum = G.logJ + 1 + ((I.flat || G.tP > 1) ? 1 : 0) + (G.m2 > 1 ? 1 : 0);      // U_0 .. U_{logJ-1}, A [, T [, W]]
+    G.reduce = G.tP > 1;
+    G.nrows = G.reduce ? G.logJ + 1 + ceil_log2(G.tP) + (G.m2 > 1 ? 1 : 0) : G.nsum;      // (the W row of a second chunk level comes last)
     // task length cap: twice the mean bucket load
     I.lmax = (uint32_t)(2 * (((I.flat ? total : n) + I.NB - 1) / I.NB));
     if (I.flat && I.NB < (1u << 19) && total >= ((uint64_t)1 << 22) && total / I.NB > 64) {
@@ -1425,72 +1421,75 @@ int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t 
     // further only adds combine work (measured on a rank's share of a 2^20 key over 8 ranks: 2.07 vs 2.12 ms,
     // profiles/r03_s14_small_sums.txt).
     uint32_t lmin = 32;
-    {
-        if (I.nbuckets < (1u << 16) && total >= ((uint64_t)1 << 16)) {
-            const uint32_t by_tasks = (uint32_t)((total + (1u << 17) - 1) >> 17);
-            if (by_tasks < I.lmax) I.lmax = by_tasks;
-            lmin = 8;
-        } else if (I.flat && I.nbuckets == (1u << 16) && I.lmax > 16) {
-            // Round 4, exactly 2^16 bucket runs (a rank's share of a 2^20 key over 8 ranks, 2^17 proofs): with the shorter reduction
-            // tails the accumulations are what is left of such a sum, and a lane's chain of ~30 additions (G2: 0.7 ms whatever the
-            // parallelism) is their floor -- runs cut at 16 entries + the G1 sets in one launch (msm_g1_launch_batch): the rank's four
-            // witness sums 1.80 -> 1.66 ms (profiles/r04_s4_shard_sweep.txt; round 3 had measured the opposite with its longer tails).
-            I.lmax = 16;
-            lmin = 16;
-        }
+    if (I.nbuckets < (1u << 16) && total >= ((uint64_t)1 << 16)) {
+        const uint32_t by_tasks = (uint32_t)((total + (1u << 17) - 1) >> 17);
+        if (by_tasks < I.lmax) I.lmax = by_tasks;
+        lmin = 8;
+    } else if (I.flat && I.nbuckets == (1u << 16) && I.lmax > 16) {
+        // Round 4, exactly 2^16 bucket runs (a rank's share of a 2^20 key over 8 ranks, 2^17 proofs): with the shorter reduction
+        // tails the accumulations are what is left of such a sum, and a lane's chain of ~30 additions (G2: 0.7 ms whatever the
+        // parallelism) is their floor -- runs cut at 16 entries + the G1 sets in one launch (msm_g1_launch_batch): the rank's four
+        // witness sums 1.80 -> 1.66 ms (profiles/r04_s4_shard_sweep.txt; round 3 had measured the opposite with its longer tails).
+        I.lmax = 16;
+        lmin = 16;
     }
     { const long v = tuning_get("MSM_LMAX", 0); if (v >= 4 && v <= 65536) { I.lmax = (uint32_t)v; lmin = 4; } }
     if (I.lmax < lmin) I.lmax = lmin;
     I.hot_cap = (uint32_t)(total / I.lmax) + I.nbuckets + 16;
-    const uint32_t c = I.c, W = I.W, nbuckets = I.nbuckets, lmax = I.lmax;
+    { const long v = tuning_get("MSM_HOT_MIN", 0); I.hot_min = v >= 2 ? (uint32_t)v : HOT_MIN; }      // (WSNARK_MSM_HOT_MIN: lets small tests reach the hot-bucket path)
 
-    int rc = wait_plan_users(M, M.cur, s);
-    if (rc) return rc;
-    MsmScratch& S = M.plan[M.cur].S;
-    WS_HIP_CHECK(S.vals_out.reserve(total * 4));
-    WS_HIP_CHECK(S.bstart.reserve((size_t)nbuckets * 4));
-    WS_HIP_CHECK(S.bend.reserve((size_t)nbuckets * 4));
-    WS_HIP_CHECK(S.counters.reserve((size_t)CNT_BINS * 4 + ((size_t)PRESORT_MAX_BINS + 1) * 4 * 3));
-    WS_HIP_CHECK(S.tasks.reserve((size_t)I.hot_cap * sizeof(Task)));
-    WS_HIP_CHECK(S.multi.reserve((size_t)I.hot_cap * sizeof(MultiBucket)));
-    uint32_t hot_min = HOT_MIN;      // (WSNARK_MSM_HOT_MIN: lets small tests reach the hot-bucket path)
-    { const long v = tuning_get("MSM_HOT_MIN", 0); if (v >= 2) hot_min = (uint32_t)v; }
-    I.hot_min = hot_min;
-    WS_HIP_CHECK(S.hot.reserve(((size_t)I.hot_cap / hot_min + 16) * sizeof(HotBucket)));
-
-    // counters: [0] partial slots, [1] multi-task buckets, [3] total tasks; [16..271] length histogram,
-    // [272..527] cursors
-    // (the coarse-bin counts of the grouping pass follow at [1024 ..]: one memset clears both)
-    uint32_t* d_cnt = S.counters.as<uint32_t>();
     // grouping-pass geometry (swept in rounds 1-2, profiles/r01_sweep_presort_*.txt, r02_sweep_presort_geometry.txt): 1024 scalars per
-    // workgroup of 1024 threads, 8 low bucket bits sorted per bin
-    uint32_t env_lo = 8;
-    const uint32_t env_tile = 1024, env_thr = 1024;
-    { const long v = tuning_get("MSM_LO_BITS", 0); if (v >= 1 && v <= (long)PRESORT_MAX_LO) env_lo = (uint32_t)v; }   // (tests: the 4096 bins of 7 low bits of a 2^20 table plan, at small sizes)
+    // workgroup of 1024 threads, 8 low bucket bits sorted per bin (grouping by coarse bins + per-bin LDS counting sort: the kernels above)
+    MsmGrouping& ps = info->ps;
+    const uint32_t c = I.c;
+    uint32_t& lo_bits = ps.lo_bits = 8;
+    { const long v = tuning_get("MSM_LO_BITS", 0); if (v >= 1 && v <= (long)PRESORT_MAX_LO) lo_bits = (uint32_t)v; }   // (tests: the 4096 bins of 7 low bits of a 2^20 table plan, at small sizes)
     const bool env_e64 = tuning_get("MSM_ENTRY64", 0) != 0;      // (tests: the 8-byte grouping entries a 2^24 table key needs, at small sizes)
-    uint32_t lo_bits = env_lo > PRESORT_MAX_LO ? PRESORT_MAX_LO : env_lo;
     if (lo_bits > c - 1) lo_bits = c - 1;
-    const uint32_t Wb = I.flat ? 1 : W;        // bucket sets the bins are spread over
+    const uint32_t Wb = I.flat ? 1 : I.W;        // bucket sets the bins are spread over
     while ((uint64_t)Wb * (I.NB >> lo_bits) > PRESORT_MAX_BINS && lo_bits < c - 1 && lo_bits < PRESORT_MAX_LO) lo_bits++;
     // one bucket set: keep about as many bins (= workgroups of the per-bin sort) as the 16-window plans have
     // (not below 7 low bits: with 64 LDS counters per bin the counting sort's atomics collide -- 0.94 ms instead of 0.15-0.22 ms)
     while (I.flat && (I.NB >> lo_bits) < 2048 && lo_bits > 7) lo_bits--;
-    uint32_t idx_bits = 1;
-    while (((uint64_t)1 << idx_bits) < (I.flat ? (uint64_t)I.Wall * n : n)) idx_bits++;
+    const uint32_t idx_bits = ps.idx_bits = std::max(1u, ceil_log2(I.flat ? (uint64_t)I.Wall * n : n));
     // large inputs (2^24 pairs): give up low bucket bits while that keeps the entries at 4 bytes and the bin count in range
     while (!env_e64 && idx_bits + 1 + lo_bits > 32 && lo_bits > 1 && (uint64_t)Wb * (I.NB >> (lo_bits - 1)) <= PRESORT_MAX_BINS) lo_bits--;
-    const uint32_t HB = I.NB >> lo_bits, nbins = Wb * HB;
-    if (nbins > PRESORT_MAX_BINS) { set_last_error("msm: grouping pass geometry out of range"); return WS_ERR_SIZE; }
-    {
-        // ---- grouping by coarse bins + per-bin LDS counting sort (see the kernels above) ----
-        const bool e32 = !env_e64 && idx_bits + 1 + lo_bits <= 32;
-        WS_HIP_CHECK(S.entries.reserve(total * (e32 ? 4 : 8)));
-        WS_HIP_CHECK(hipMemsetAsync(S.counters.p, 0, (CNT_BINS + 3 * ((size_t)nbins + 1)) * 4, s));   // (counts, starts, cursors)
-        I.ps_valid = true;
-        I.ps_lo_bits = lo_bits; I.ps_idx_bits = idx_bits; I.ps_nbins = nbins; I.ps_e32 = e32;
-        I.ps_HB = HB; I.ps_tile = env_tile; I.ps_thr = env_thr;
-    }
-    (void)d_cnt; (void)hot_min; (void)lmax; (void)nbuckets;
+    ps.HB = I.NB >> lo_bits;
+    ps.nbins = Wb * ps.HB;
+    if (ps.nbins > PRESORT_MAX_BINS) { set_last_error("msm: grouping pass geometry out of range"); return WS_ERR_SIZE; }
+    ps.e32 = !env_e64 && idx_bits + 1 + lo_bits <= 32;
+    ps.valid = true;
+    return WS_OK;
+}
+
+// the plan's own buffers (msm_plan_begin; msm_plan_variant for its copy of everything behind the coarse bins)
+static int reserve_plan_buffers(MsmScratch& S, const MsmPlanInfo& info) {
+    const MsmShape& I = info.shape;
+    WS_HIP_CHECK(S.vals_out.reserve(I.n * I.W * 4));
+    WS_HIP_CHECK(S.bstart.reserve((size_t)I.nbuckets * 4));
+    WS_HIP_CHECK(S.bend.reserve((size_t)I.nbuckets * 4));
+    WS_HIP_CHECK(S.counters.reserve((size_t)CNT_BINS * 4 + ((size_t)PRESORT_MAX_BINS + 1) * 4 * 3));
+    WS_HIP_CHECK(S.tasks.reserve((size_t)I.hot_cap * sizeof(Task)));
+    WS_HIP_CHECK(S.multi.reserve((size_t)I.hot_cap * sizeof(MultiBucket)));
+    WS_HIP_CHECK(S.hot.reserve(((size_t)I.hot_cap / I.hot_min + 16) * sizeof(HotBucket)));
+    return WS_OK;
+}
+
+int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t table_c) {
+    if (!ctx()) return WS_ERR_NOINIT;
+    if (!s) s = L.stream;
+    MsmWorkspace& M = ws(L);
+    MsmPlanInfo& I = M.plan[M.cur].info;
+    int rc = msm_plan_geometry(n, sh, table_c, &I);
+    if (rc || I.shape.n == 0) return rc;
+    if ((rc = wait_plan_users(M, M.cur, s))) return rc;
+    MsmScratch& S = M.plan[M.cur].S;
+    if ((rc = reserve_plan_buffers(S, I))) return rc;
+    WS_HIP_CHECK(S.entries.reserve(I.shape.n * I.shape.W * (I.ps.e32 ? 4 : 8)));
+    // counters: [0] partial slots, [1] multi-task buckets, [3] total tasks; [16..271] length histogram,
+    // [272..527] cursors
+    // (the coarse-bin counts of the grouping pass follow at [1024 ..]: one memset clears both)
+    WS_HIP_CHECK(hipMemsetAsync(S.counters.p, 0, (CNT_BINS + 3 * ((size_t)I.ps.nbins + 1)) * 4, s));   // (counts, starts, cursors)
     I.building = true;
     return WS_OK;
 }
@@ -1500,27 +1499,42 @@ int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t 
 static bool presort_stage_scatter() { const long v = tuning_get("PRESORT_STAGE", 1); return v == 1 || v == 2; }
 static bool presort_stage_bins() { const long v = tuning_get("PRESORT_STAGE", 1); return v == 1 || v == 3; }
 
-// the per-bin sort of a plan (mask: of its variant)
-static void launch_presort_bins(const MsmPlanInfo& I, uint32_t bthr, const MsmScratch& src, const uint32_t* bin_start, MsmScratch& S, uint32_t* hist,
-                                const uint8_t* mask, uint32_t mask_mod, hipStream_t s) {
-    const dim3 grid(I.ps_nbins), blk(bthr);
+// The per-bin sort of a plan (mask: of its variant) and the task list behind it -- what msm_plan_finish and msm_plan_variant share.
+// `info` and `src` belong to the plan whose coarse bins are read (S itself, or the plan S becomes a variant of), S to the plan that is written.
+static int launch_bins_and_tasks(const MsmPlanInfo& info, const MsmScratch& src, MsmScratch& S, const uint8_t* mask, uint32_t mask_mod, hipStream_t s) {
+    KernelTimer& T = ctx()->timer;
+    const MsmGrouping& ps = info.ps;
+    const uint32_t nbuckets = info.shape.nbuckets, lmax = info.shape.lmax;
+    const dim3 grid(ps.nbins), blk(ps.bthr);
+    const uint32_t* bin_start = src.counters.as<uint32_t>() + CNT_BINS + (ps.nbins + 1);
+    uint32_t* d_cnt = S.counters.as<uint32_t>();
+    uint32_t* hist = d_cnt + CNT_HIST;
     uint32_t* vals = S.vals_out.as<uint32_t>();
     uint32_t* bs = S.bstart.as<uint32_t>();
     uint32_t* be = S.bend.as<uint32_t>();
-    if (I.ps_e32 && presort_stage_bins())
-        hipLaunchKernelGGL((presort_bins<uint32_t, true>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, I.ps_lo_bits, I.ps_idx_bits, vals, bs, be,
-                           I.lmax, hist, mask, mask_mod);
-    else if (I.ps_e32)
-        hipLaunchKernelGGL((presort_bins<uint32_t, false>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, I.ps_lo_bits, I.ps_idx_bits, vals, bs, be,
-                           I.lmax, hist, mask, mask_mod);
+    T.begin("msm_presort_bins", s);
+    if (ps.e32 && presort_stage_bins())
+        hipLaunchKernelGGL((presort_bins<uint32_t, true>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod);
+    else if (ps.e32)
+        hipLaunchKernelGGL((presort_bins<uint32_t, false>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod);
     else
-        hipLaunchKernelGGL((presort_bins<uint64_t, false>), grid, blk, 0, s, src.entries.as<uint64_t>(), bin_start, I.ps_lo_bits, I.ps_idx_bits, vals, bs, be,
-                           I.lmax, hist, mask, mask_mod);
+        hipLaunchKernelGGL((presort_bins<uint64_t, false>), grid, blk, 0, s, src.entries.as<uint64_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod);
+    T.end(s);
+    WS_HIP_CHECK(hipGetLastError());
+    T.begin("msm_plan", s);
+    hipLaunchKernelGGL(msm_plan_emit, dim3(ceil_div_u64(nbuckets, 256)), dim3(256), 0, s, bs, be, nbuckets, lmax, hist, d_cnt + CNT_CURSOR,
+                       S.tasks.as<Task>(), d_cnt, S.multi.as<MultiBucket>(), S.hot.as<HotBucket>(), info.shape.hot_min);
+    hipLaunchKernelGGL(msm_plan_emit_hot, dim3(64), dim3(256), 0, s, S.hot.as<HotBucket>(), d_cnt, lmax, S.tasks.as<Task>());
+    T.end(s);
+    WS_HIP_CHECK(hipGetLastError());
+    return WS_OK;
 }
 
-static PresortArgs plan_presort_args(const MsmPlanInfo& I, const Fe* d_scalars, uint32_t i0, uint32_t i_end) {
-    return PresortArgs{d_scalars, (uint32_t)I.n, I.c, I.Wall, I.w_off, I.w_stride, i0, i_end, I.ps_lo_bits, I.ps_HB, I.ps_nbins, I.ps_tile,
-                       I.ps_idx_bits, nullptr, I.flat ? 1u : 0u};
+static PresortArgs plan_presort_args(const MsmPlanInfo& info, const Fe* d_scalars, uint32_t i0, uint32_t i_end) {
+    const MsmShape& I = info.shape;
+    const MsmGrouping& ps = info.ps;
+    return PresortArgs{d_scalars, (uint32_t)I.n, I.c, I.Wall, I.w_off, I.w_stride, i0, i_end, ps.lo_bits, ps.HB, ps.nbins, ps.tile,
+                       ps.idx_bits, nullptr, I.flat ? 1u : 0u};
 }
 
 int msm_plan_count(Lane& L, const Fe* d_scalars, uint64_t i0, uint64_t i1, hipStream_t s) {
@@ -1529,15 +1543,15 @@ int msm_plan_count(Lane& L, const Fe* d_scalars, uint64_t i0, uint64_t i1, hipSt
     if (!s) s = L.stream;
     MsmWorkspace& M = ws(L);
     MsmPlanInfo& I = M.plan[M.cur].info;
-    if (I.n == 0 && I.valid) return WS_OK;                 // (nothing to group: n == 0, or a rank that owns no window)
+    if (I.shape.n == 0 && I.valid) return WS_OK;           // (nothing to group: n == 0, or a rank that owns no window)
     if (!I.building) { set_last_error("msm_plan_count: no plan is being built"); return WS_ERR_ARG; }
-    if (!d_scalars || i0 > i1 || i1 > I.n) return WS_ERR_ARG;
-    if (!I.ps_valid || i0 == i1) return WS_OK;             // (the hipCUB pipeline has no histogram pass)
+    if (!d_scalars || i0 > i1 || i1 > I.shape.n) return WS_ERR_ARG;
+    if (i0 == i1) return WS_OK;
     MsmScratch& S = M.plan[M.cur].S;
     uint32_t* bin_count = S.counters.as<uint32_t>() + CNT_BINS;
     const PresortArgs PA = plan_presort_args(I, d_scalars, (uint32_t)i0, (uint32_t)i1);
     X->timer.begin("msm_presort_count", s);
-    hipLaunchKernelGGL(presort_count, dim3(ceil_div_u64(i1 - i0, I.ps_tile)), dim3(I.ps_thr), 0, s, PA, bin_count);
+    hipLaunchKernelGGL(presort_count, dim3(ceil_div_u64(i1 - i0, I.ps.tile)), dim3(I.ps.thr), 0, s, PA, bin_count);
     X->timer.end(s);
     WS_HIP_CHECK(hipGetLastError());
     return WS_OK;
@@ -1549,64 +1563,45 @@ int msm_plan_finish(Lane& L, const Fe* d_scalars, hipStream_t s) {
     if (!s) s = L.stream;
     MsmWorkspace& M = ws(L);
     MsmPlanInfo& I = M.plan[M.cur].info;
-    if (I.n == 0 && I.valid) return WS_OK;
+    if (I.shape.n == 0 && I.valid) return WS_OK;
     if (!I.building) { set_last_error("msm_plan_finish: no plan is being built"); return WS_ERR_ARG; }
     if (!d_scalars) return WS_ERR_ARG;
     I.building = false;
     MsmScratch& S = M.plan[M.cur].S;
     KernelTimer& T = X->timer;
-    const uint64_t n = I.n, total = n * I.W;
-    const uint32_t nbuckets = I.nbuckets, lmax = I.lmax, hot_min = I.hot_min;
-    uint32_t* d_cnt = S.counters.as<uint32_t>();
-    if (I.ps_valid) {
-        const uint32_t nbins = I.ps_nbins;
-        const bool e32 = I.ps_e32;
-        uint32_t* bin_count = d_cnt + CNT_BINS;
-        uint32_t* bin_start = bin_count + (nbins + 1);
-        uint32_t* bin_cursor = bin_start + (nbins + 1);
-        const PresortArgs PA = plan_presort_args(I, d_scalars, 0u, (uint32_t)n);
-        const dim3 grid(ceil_div_u64(n, I.ps_tile)), blk(I.ps_thr);
-        const bool once = I.Wall <= PRESORT_ONCE_W && I.ps_tile == I.ps_thr;
-        if (!once) {
-            T.begin("msm_presort_scan", s);
-            hipLaunchKernelGGL(presort_scan, dim3(1), dim3(256), 0, s, bin_count, nbins, bin_start, bin_cursor);
-            T.end(s);
-        }
-        T.begin("msm_presort_scatter", s);
-        if (once && e32 && presort_stage_scatter())
-            hipLaunchKernelGGL((presort_scatter_once<uint32_t, true>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint32_t>());
-        else if (once && e32) hipLaunchKernelGGL((presort_scatter_once<uint32_t, false>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint32_t>());
-        else if (once) hipLaunchKernelGGL((presort_scatter_once<uint64_t, false>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint64_t>());
-        else if (e32) hipLaunchKernelGGL(presort_scatter<uint32_t>, grid, blk, 0, s, PA, bin_cursor, S.entries.as<uint32_t>());
-        else hipLaunchKernelGGL(presort_scatter<uint64_t>, grid, blk, 0, s, PA, bin_cursor, S.entries.as<uint64_t>());
+    const uint64_t n = I.shape.n, total = n * I.shape.W;
+    const uint32_t nbins = I.ps.nbins;
+    const bool e32 = I.ps.e32;
+    uint32_t* bin_count = S.counters.as<uint32_t>() + CNT_BINS;
+    uint32_t* bin_start = bin_count + (nbins + 1);
+    uint32_t* bin_cursor = bin_start + (nbins + 1);
+    const PresortArgs PA = plan_presort_args(I, d_scalars, 0u, (uint32_t)n);
+    const dim3 grid(ceil_div_u64(n, I.ps.tile)), blk(I.ps.thr);
+    const bool once = I.shape.Wall <= PRESORT_ONCE_W && I.ps.tile == I.ps.thr;
+    if (!once) {
+        T.begin("msm_presort_scan", s);
+        hipLaunchKernelGGL(presort_scan, dim3(1), dim3(256), 0, s, bin_count, nbins, bin_start, bin_cursor);
         T.end(s);
-        // one workgroup per bin, about eight entries per thread (two rounds of four loads in flight)
-        uint32_t bthr = (uint32_t)((total / nbins / 8 + 63) / 64 * 64);
-        bthr = bthr < 64 ? 64 : bthr > 1024 ? 1024 : bthr;
-        T.begin("msm_presort_bins", s);
-        launch_presort_bins(I, bthr, S, bin_start, S, d_cnt + CNT_HIST, nullptr, 0u, s);
-        T.end(s);
-        WS_HIP_CHECK(hipGetLastError());
-        I.ps_bthr = bthr;
-    } else {
-        set_last_error("msm_plan_finish: the plan has no grouping pass");
-        return WS_ERR_ARG;
     }
-    T.begin("msm_plan", s);
-    hipLaunchKernelGGL(msm_plan_emit, dim3(ceil_div_u64(nbuckets, 256)), dim3(256), 0, s, S.bstart.as<uint32_t>(),
-                       S.bend.as<uint32_t>(), nbuckets, lmax, d_cnt + CNT_HIST, d_cnt + CNT_CURSOR, S.tasks.as<Task>(), d_cnt,
-                       S.multi.as<MultiBucket>(), S.hot.as<HotBucket>(), hot_min);
-    hipLaunchKernelGGL(msm_plan_emit_hot, dim3(64), dim3(256), 0, s, S.hot.as<HotBucket>(), d_cnt, lmax, S.tasks.as<Task>());
+    T.begin("msm_presort_scatter", s);
+    if (once && e32 && presort_stage_scatter())
+        hipLaunchKernelGGL((presort_scatter_once<uint32_t, true>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint32_t>());
+    else if (once && e32) hipLaunchKernelGGL((presort_scatter_once<uint32_t, false>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint32_t>());
+    else if (once) hipLaunchKernelGGL((presort_scatter_once<uint64_t, false>), grid, blk, 0, s, PA, bin_count, bin_start, bin_cursor, S.entries.as<uint64_t>());
+    else if (e32) hipLaunchKernelGGL(presort_scatter<uint32_t>, grid, blk, 0, s, PA, bin_cursor, S.entries.as<uint32_t>());
+    else hipLaunchKernelGGL(presort_scatter<uint64_t>, grid, blk, 0, s, PA, bin_cursor, S.entries.as<uint64_t>());
     T.end(s);
-    WS_HIP_CHECK(hipGetLastError());
+    // one workgroup per bin, about eight entries per thread (two rounds of four loads in flight)
+    const uint32_t bthr = (uint32_t)((total / nbins / 8 + 63) / 64 * 64);
+    I.ps.bthr = bthr < 64 ? 64 : bthr > 1024 ? 1024 : bthr;
+    const int rc = launch_bins_and_tasks(I, S, S, nullptr, 0u, s);
+    if (rc) return rc;
     // task / partial counts stay on the device (counters[3], [1], [0]); by construction
     // tasks <= total/lmax + nbuckets <= hot_cap, so the worst-case grids below always cover them
-    I.ntasks = I.hot_cap;
-    I.nmulti = 0;
+    I.ntasks = I.shape.hot_cap;
     I.valid = true;
     return WS_OK;
 }
-
 
 int msm_plan_dev(Lane& L, const Fe* d_scalars, uint64_t n, WindowShard sh, hipStream_t s, uint32_t table_c) {
     if (n && !d_scalars) return WS_ERR_ARG;
@@ -1617,8 +1612,7 @@ int msm_plan_dev(Lane& L, const Fe* d_scalars, uint64_t n, WindowShard sh, hipSt
 }
 
 int msm_plan_variant(Lane& L, int src_id, int dst_id, const uint8_t* d_mask, hipStream_t s) {
-    Context* X = ctx();
-    if (!X) return WS_ERR_NOINIT;
+    if (!ctx()) return WS_ERR_NOINIT;
     if (!s) s = L.stream;
     if (src_id < 0 || src_id >= kPlans || dst_id < 0 || dst_id >= kPlans || src_id == dst_id || !d_mask) return WS_ERR_ARG;
     MsmWorkspace& M = ws(L);
@@ -1626,34 +1620,15 @@ int msm_plan_variant(Lane& L, int src_id, int dst_id, const uint8_t* d_mask, hip
     MsmScratch& SS = M.plan[src_id].S;
     MsmPlanInfo& I = M.plan[dst_id].info;
     MsmScratch& S = M.plan[dst_id].S;
-    if (!src.valid || !src.ps_valid || src.n == 0) { set_last_error("msm_plan_variant: the source plan has no shared grouping pass"); return WS_ERR_ARG; }
+    if (!src.valid || !src.ps.valid || src.shape.n == 0) { set_last_error("msm_plan_variant: the source plan has no shared grouping pass"); return WS_ERR_ARG; }
     int rc = wait_plan_users(M, dst_id, s);
     if (rc) return rc;
     I = src;
-    I.ps_valid = false;
+    I.ps.valid = false;
     I.valid = false;
-    const uint64_t total = src.n * src.W;
-    WS_HIP_CHECK(S.vals_out.reserve(total * 4));
-    WS_HIP_CHECK(S.bstart.reserve((size_t)src.nbuckets * 4));
-    WS_HIP_CHECK(S.bend.reserve((size_t)src.nbuckets * 4));
-    WS_HIP_CHECK(S.counters.reserve((size_t)CNT_BINS * 4 + ((size_t)PRESORT_MAX_BINS + 1) * 4 * 3));
-    WS_HIP_CHECK(S.tasks.reserve((size_t)src.hot_cap * sizeof(Task)));
-    WS_HIP_CHECK(S.multi.reserve((size_t)src.hot_cap * sizeof(MultiBucket)));
-    WS_HIP_CHECK(S.hot.reserve(((size_t)src.hot_cap / src.hot_min + 16) * sizeof(HotBucket)));
-    uint32_t* d_cnt = S.counters.as<uint32_t>();
+    if ((rc = reserve_plan_buffers(S, src))) return rc;
     WS_HIP_CHECK(hipMemsetAsync(S.counters.p, 0, (size_t)CNT_BINS * 4, s));
-    const uint32_t* bin_start = SS.counters.as<uint32_t>() + CNT_BINS + (src.ps_nbins + 1);
-    KernelTimer& T = X->timer;
-    T.begin("msm_presort_bins", s);
-    launch_presort_bins(src, src.ps_bthr, SS, bin_start, S, d_cnt + CNT_HIST, d_mask, src.flat ? (uint32_t)src.n : 0u, s);
-    T.end(s);
-    T.begin("msm_plan", s);
-    hipLaunchKernelGGL(msm_plan_emit, dim3(ceil_div_u64(src.nbuckets, 256)), dim3(256), 0, s, S.bstart.as<uint32_t>(),
-                       S.bend.as<uint32_t>(), src.nbuckets, src.lmax, d_cnt + CNT_HIST, d_cnt + CNT_CURSOR, S.tasks.as<Task>(), d_cnt,
-                       S.multi.as<MultiBucket>(), S.hot.as<HotBucket>(), src.hot_min);
-    hipLaunchKernelGGL(msm_plan_emit_hot, dim3(64), dim3(256), 0, s, S.hot.as<HotBucket>(), d_cnt, src.lmax, S.tasks.as<Task>());
-    T.end(s);
-    WS_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_bins_and_tasks(src, SS, S, d_mask, src.shape.flat ? (uint32_t)src.shape.n : 0u, s))) return rc;      // (the source's bin starts and thread count)
     I.valid = true;
     return WS_OK;
 }
@@ -1683,7 +1658,7 @@ static int msm_acc_sets(Lane& L, MsmPending* const* Ps, int nsets, int which, hi
         as.hot_done[k] = Q.S.hot_done.template as<uint32_t>();
         if (k < nsets && Q.info.ntasks > ntasks) ntasks = Q.info.ntasks;
         if (k < nsets) {
-            const MsmPlanInfo& QI = Q.info;
+            const MsmShape& QI = Q.info.shape;
             const uint64_t mean = (QI.n * QI.W + QI.nbuckets - 1) / (QI.nbuckets ? QI.nbuckets : 1);
             if (2 * (uint64_t)QI.lmax < 3 * mean) {        // task cap below 1.5 x the mean load: most buckets are cut
                 const uint32_t want = (QI.nbuckets + 63) / 64;
@@ -1710,6 +1685,13 @@ static int msm_acc_sets(Lane& L, MsmPending* const* Ps, int nsets, int which, hi
 // `prepared`: d_points are already in C's internal domain (msm_prepare_points).
 // defer_kernels: only the launch slot and its buffers are set up; the caller accumulates several such launches in ONE batched
 // launch (msm_acc_sets)
+// Bytes of launch P's rows that reach the host: nrows per group when the pieces are folded on the GPU (their nsum rows per piece then stay in
+// d_rows), nsum per piece otherwise.  The ONE place: msm_launch_acc sizes the pinned h_sums with it, msm_launch_tail_levels copies as many.
+static size_t host_rows_bytes(const MsmPending& P) {
+    const MsmTail& G = P.info.tail;
+    return (G.reduce ? (size_t)G.groups * G.nrows : (size_t)G.tW * G.nsum) * (P.which ? sizeof(G2::Pt) : sizeof(G1::Pt));
+}
+
 template <class C, class H>
 static int msm_launch_acc(Lane& L, int which, const typename H::Aff* d_points_ref, bool prepared, int* slot_out, hipStream_t s, bool defer_kernels = false) {
     typedef typename C::PtP Pt;      // packed accumulator in global memory (same bytes as H::Pt)
@@ -1720,7 +1702,7 @@ static int msm_launch_acc(Lane& L, int which, const typename H::Aff* d_points_re
     MsmWorkspace& M = ws(L);
     const MsmPlanInfo& I = M.plan[M.cur].info;
     if (!I.valid) { set_last_error("msm: no plan"); return WS_ERR_ARG; }
-    if (I.n && !d_points_ref) return WS_ERR_ARG;
+    if (I.shape.n && !d_points_ref) return WS_ERR_ARG;
     int slot = -1;
     for (int i = 0; i < kPendingSlots; i++) if (!M.slot[i].active) { slot = i; break; }
     if (slot < 0) { set_last_error("msm: too many unfinished launches"); return WS_ERR_ARG; }
@@ -1729,25 +1711,24 @@ static int msm_launch_acc(Lane& L, int which, const typename H::Aff* d_points_re
     P.info = I;
     P.plan_id = M.cur;
     P.partner = -1;
-    if (I.n == 0) { P.active = true; *slot_out = slot; return WS_OK; }   // multiexp with n=0 leaves pr unchanged
+    if (I.shape.n == 0) { P.active = true; *slot_out = slot; return WS_OK; }   // multiexp with n=0 leaves pr unchanged
     const typename C::AffP* d_points = reinterpret_cast<const typename C::AffP*>(d_points_ref);
-    const uint64_t n = I.n;
-    const uint32_t W = I.tW, nbuckets = I.nbuckets, J = I.J, nsum = I.nsum;
+    const MsmShape& Sh = I.shape;
+    const MsmTail& G = I.tail;
+    const uint32_t W = G.tW, J = G.J, nsum = G.nsum;
 
     MsmScratch& S = P.S;                        // this launch's accumulation buffers (the plan's own are read by the kernels)
     // Everything runs in order on the caller's stream.  Tried and measured slower on MI355X (rounds 1, 3, 5): accumulations on
     // concurrent streams (cache thrash), and the WHOLE reduction tail on another (or a high-priority) stream: docs/HISTORY.md, DESIGN.md
     // section 5.  (Its latency levels alone on another stream do pay: msm_launch_tail.)
-    WS_HIP_CHECK(S.buckets.reserve((size_t)nbuckets * sizeof(Pt)));
-    WS_HIP_CHECK(S.partials.reserve((size_t)I.hot_cap * sizeof(Pt)));
+    WS_HIP_CHECK(S.buckets.reserve((size_t)Sh.nbuckets * sizeof(Pt)));
+    WS_HIP_CHECK(S.partials.reserve((size_t)Sh.hot_cap * sizeof(Pt)));
     // (level-1 chunk pairs first; with a second chunk level its W * J pairs follow them in the same buffers)
-    WS_HIP_CHECK(S.chunkS.reserve(((size_t)W * I.J1 + (I.m2 > 1 ? (size_t)2 * W * J : 0)) * sizeof(Pt)));      // S, then S' and W
-    WS_HIP_CHECK(S.chunkA.reserve(((size_t)W * I.J1 + (I.m2 > 1 ? (size_t)W * J : 0)) * sizeof(Pt)));          // A, then A'
-    // rows that reach the host: nrows per group when the pieces are folded on the GPU (their nsum rows per piece then stay in
-    // d_rows), nsum per piece otherwise
-    const size_t sums_bytes = (I.reduce ? (size_t)I.groups * I.nrows : (size_t)W * nsum) * sizeof(Pt);
+    WS_HIP_CHECK(S.chunkS.reserve(((size_t)W * G.J1 + (G.m2 > 1 ? (size_t)2 * W * J : 0)) * sizeof(Pt)));      // S, then S' and W
+    WS_HIP_CHECK(S.chunkA.reserve(((size_t)W * G.J1 + (G.m2 > 1 ? (size_t)W * J : 0)) * sizeof(Pt)));          // A, then A'
+    const size_t sums_bytes = host_rows_bytes(P);
     WS_HIP_CHECK(P.d_sums.reserve(sums_bytes));
-    if (I.reduce) WS_HIP_CHECK(P.d_rows.reserve((size_t)W * nsum * sizeof(Pt)));
+    if (G.reduce) WS_HIP_CHECK(P.d_rows.reserve((size_t)W * nsum * sizeof(Pt)));
     WS_HIP_CHECK(S.tree_half.reserve((size_t)W * 6 * sizeof(Pt)));
     {
         const size_t db = (size_t)W * 3 * sizeof(uint32_t);
@@ -1761,20 +1742,20 @@ static int msm_launch_acc(Lane& L, int which, const typename H::Aff* d_points_re
     }
     if (!P.ev) WS_HIP_CHECK(hipEventCreate(&P.ev));
     // (slots wait for hot-bucket slice sums: at most one per HOT_SLICE tasks plus one per hot bucket)
-    WS_HIP_CHECK(S.hot_sums.reserve(((size_t)I.hot_cap / HOT_SLICE + (size_t)I.hot_cap / I.hot_min + 32) * sizeof(Pt)));
+    WS_HIP_CHECK(S.hot_sums.reserve(((size_t)Sh.hot_cap / HOT_SLICE + (size_t)Sh.hot_cap / Sh.hot_min + 32) * sizeof(Pt)));
     // completion counters of the combine kernel's hot-bucket stage: cleared when (re)allocated, left at zero by every launch
     {
-        const size_t hot_bytes = ((size_t)I.hot_cap / I.hot_min + 16) * 4;
+        const size_t hot_bytes = ((size_t)Sh.hot_cap / Sh.hot_min + 16) * 4;
         if (!S.hot_done.p || S.hot_done.bytes < hot_bytes) { WS_HIP_CHECK(S.hot_done.alloc(hot_bytes)); WS_HIP_CHECK(hipMemsetAsync(S.hot_done.p, 0, hot_bytes, s)); }
     }
 
     KernelTimer& T = X->timer;
-    if (I.flat && !prepared) { set_last_error("msm: a table plan needs a prepared fixed-base table"); return WS_ERR_ARG; }
+    if (Sh.flat && !prepared) { set_last_error("msm: a table plan needs a prepared fixed-base table"); return WS_ERR_ARG; }
     if (C::Field::kInternalDomain && !prepared) {
-        WS_HIP_CHECK(S.points_conv.reserve((size_t)n * sizeof(typename C::AffP)));
+        WS_HIP_CHECK(S.points_conv.reserve((size_t)Sh.n * sizeof(typename C::AffP)));
         T.begin("msm_convert_points", s);
-        hipLaunchKernelGGL(msm_convert_points<C>, dim3(ceil_div_u64(n, 256)), dim3(256), 0, s, d_points,
-                           S.points_conv.as<typename C::AffP>(), n);
+        hipLaunchKernelGGL(msm_convert_points<C>, dim3(ceil_div_u64(Sh.n, 256)), dim3(256), 0, s, d_points,
+                           S.points_conv.as<typename C::AffP>(), Sh.n);
         T.end(s);
         d_points = S.points_conv.as<typename C::AffP>();
     }
@@ -1795,10 +1776,9 @@ static int msm_launch_acc(Lane& L, int which, const typename H::Aff* d_points_re
 template <class C> struct TailCurve { typedef C type; typedef C paired; };
 template <> struct TailCurve<G1R29> { typedef G1R29I type; typedef G1P29 paired; };      // (round 6: one G1 point on two lanes, curve_pair.h)
 template <> struct TailCurve<G2R29> { typedef G2P29 type; typedef G2Q29 paired; };       // (round 6: one G2 point on FOUR lanes for msm_tree / msm_rows)
-// WSNARK_TAIL_PAIR_G1 (default 1): the G1 reduction tails on lane pairs -- seven product steps per addition instead of fourteen
-static bool tail_pair_g1() { return tuning_get("TAIL_PAIR_G1", 1) != 0; }
-static bool tail_quad_g2() { return tuning_get("TAIL_QUAD_G2", 1) != 0; }
-template <class C> static bool tail_split() { return sizeof(typename C::AffP) > 64 ? tail_quad_g2() : tail_pair_g1(); }
+// WSNARK_TAIL_PAIR_G1 (default 1): the G1 reduction tails on lane pairs -- seven product steps per addition instead of fourteen;
+// WSNARK_TAIL_QUAD_G2 (default 1): the G2 ones on lane quads
+template <class C> static bool tail_split() { return tuning_get(sizeof(typename C::AffP) > 64 ? "TAIL_QUAD_G2" : "TAIL_PAIR_G1", 1) != 0; }
 // CC: the curve of msm_chunks (throughput-bound: 2 additions per bucket on every lane of the chip -- the one-lane form is the cheaper
 // one there), C: the curve of msm_tree / msm_rows (latency-bound LDS reductions: the lane-paired forms halve every step).  Same buffers.
 // second_slot >= 0 (one launch only): that launch's buckets are added to the first one's bucket by bucket in msm_chunks, and the rows
@@ -1807,7 +1787,7 @@ template <class C>
 static void tail_sets(Lane& L, const int* slot_ids, int nslots, int second_slot, TailSets<C>& ts) {
     typedef typename PointIO<C>::Stored St;
     MsmPending* slots = ws(L).slot;
-    const MsmPlanInfo& I = slots[slot_ids[0]].info;
+    const MsmTail& I = slots[slot_ids[0]].info.tail;
     for (int k = 0; k < 4; k++) {
         MsmPending& P = slots[slot_ids[k < nslots ? k : 0]];
         ts.buckets[k] = P.S.buckets.template as<St>();
@@ -1839,8 +1819,8 @@ static int msm_launch_tail_chunks(Lane& L, const int* slot_ids, int nslots, hipS
     static_assert(sizeof(typename PointIO<CC>::Stored) == sizeof(St), "the chunk and tree kernels share their buffers");
     Context* X = ctx();
     if (!s) s = L.stream;
-    const MsmPlanInfo& I = ws(L).slot[slot_ids[0]].info;
-    if (I.n == 0) return WS_OK;
+    if (ws(L).slot[slot_ids[0]].info.shape.n == 0) return WS_OK;
+    const MsmTail& I = ws(L).slot[slot_ids[0]].info.tail;
     TailSets<C> ts;
     tail_sets<C>(L, slot_ids, nslots, second_slot, ts);
     const uint32_t W = I.tW;
@@ -1869,8 +1849,9 @@ static int msm_launch_tail_levels(Lane& L, const int* slot_ids, int nslots, hipS
     Context* X = ctx();
     if (!s) s = L.stream;
     MsmPending* slots = ws(L).slot;
-    const MsmPlanInfo& I = slots[slot_ids[0]].info;
-    if (I.n == 0) return WS_OK;
+    if (slots[slot_ids[0]].info.shape.n == 0) return WS_OK;
+    const MsmTail& I = slots[slot_ids[0]].info.tail;
+    static_assert(sizeof(St) == sizeof(G1::Pt) || sizeof(St) == sizeof(G2::Pt), "the rows are the host's points (host_rows_bytes)");
     TailSets<C> ts;
     tail_sets<C>(L, slot_ids, nslots, second_slot, ts);
     const uint32_t J = I.J, logJ = I.logJ, nsum = I.nsum, LPP = IO::LPP, W = I.tW;
@@ -1894,7 +1875,6 @@ static int msm_launch_tail_levels(Lane& L, const int* slot_ids, int nslots, hipS
                        nsum);
     T.end(s);
     WS_HIP_CHECK(hipGetLastError());
-    size_t sums_bytes;
     if (I.reduce) {
         uint32_t rslots = 1;
         while (rslots < I.tP && rslots < smax && rslots * LPP < (uint32_t)TreeBound<C>::value) rslots <<= 1;
@@ -1902,13 +1882,10 @@ static int msm_launch_tail_levels(Lane& L, const int* slot_ids, int nslots, hipS
         hipLaunchKernelGGL(msm_rows<C>, dim3(I.nrows, I.groups, nslots), dim3(rslots * LPP), (size_t)rslots * sizeof(St), s, ts, I.tP, logJ, nsum, I.nrows, I.m2 > 1 ? I.nrows - 1 : 0xFFFFFFFFu);
         T.end(s);
         WS_HIP_CHECK(hipGetLastError());
-        sums_bytes = (size_t)I.groups * I.nrows * sizeof(St);
-    } else {
-        sums_bytes = (size_t)W * nsum * sizeof(St);
     }
     for (int k = 0; k < nslots; k++) {
         MsmPending& P = slots[slot_ids[k]];
-        WS_HIP_CHECK(hipMemcpyAsync(P.h_sums, P.d_sums.p, sums_bytes, hipMemcpyDeviceToHost, s));
+        WS_HIP_CHECK(hipMemcpyAsync(P.h_sums, P.d_sums.p, host_rows_bytes(P), hipMemcpyDeviceToHost, s));      // (what msm_launch_acc sized h_sums for)
         WS_HIP_CHECK(hipEventRecord(P.ev, s));
     }
     // (the second launch's plan and buckets are read until here: whoever rewrites them waits for this event, wait_plan_users)
@@ -1932,7 +1909,7 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
     int rc = msm_launch_tail_chunks<C, CC>(L, slot_ids, nslots, s, second_slot);
     if (rc) return rc;
     MsmPending& P0 = ws(L).slot[slot_ids[0]];
-    if (s_levels && s_levels != s && P0.info.n) {
+    if (s_levels && s_levels != s && P0.info.shape.n) {
         if (!P0.ev_chunks) WS_HIP_CHECK(hipEventCreateWithFlags(&P0.ev_chunks, hipEventDisableTiming));
         WS_HIP_CHECK(hipEventRecord(P0.ev_chunks, s));
         WS_HIP_CHECK(hipStreamWaitEvent(s_levels, P0.ev_chunks, 0));
@@ -1941,6 +1918,12 @@ static int msm_launch_tail(Lane& L, const int* slot_ids, int nslots, hipStream_t
     }
     return msm_launch_tail_levels<C>(L, slot_ids, nslots, s_levels, second_slot);
 }
+// the tail of sums accumulated on curve C: tail_split<C>() chooses the curves the tail's kernels run on
+template <class C>
+static int msm_launch_tail_for(Lane& L, const int* slot_ids, int nslots, hipStream_t s, int second_slot = -1, hipStream_t s_levels = nullptr) {
+    return tail_split<C>() ? msm_launch_tail<typename TailCurve<C>::paired, typename TailCurve<C>::type>(L, slot_ids, nslots, s, second_slot, s_levels)
+                           : msm_launch_tail<typename TailCurve<C>::type>(L, slot_ids, nslots, s, second_slot, s_levels);
+}
 
 template <class C, class H>
 static int msm_launch(Lane& L, int which, const typename H::Aff* d_points_ref, bool prepared, int* slot_out, hipStream_t s, hipStream_t s_levels) {
@@ -1948,8 +1931,7 @@ static int msm_launch(Lane& L, int which, const typename H::Aff* d_points_ref, b
     s_levels = tail_levels_queue(L, s, s_levels);
     int rc = msm_launch_acc<C, H>(L, which, d_points_ref, prepared, slot_out, s);
     if (rc) return rc;
-    rc = tail_split<C>() ? msm_launch_tail<typename TailCurve<C>::paired, typename TailCurve<C>::type>(L, slot_out, 1, s, -1, s_levels)
-                         : msm_launch_tail<typename TailCurve<C>::type>(L, slot_out, 1, s, -1, s_levels);
+    rc = msm_launch_tail_for<C>(L, slot_out, 1, s, -1, s_levels);
     if (rc) msm_abort_slots(L, slot_out, 1, s, nullptr);
     return rc;
 }
@@ -1965,13 +1947,13 @@ int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, b
     const int keep = M.cur;
     for (int k = 0; k < nsets; k++) slots[k] = -1;
     int rc = WS_OK;
-    // Very small sums (fewer bucket runs than the chip has lanes in one wavefront per SIMD, see msm_plan_begin): the sets are
+    // Very small sums (fewer bucket runs than the chip has lanes in one wavefront per SIMD, see msm_plan_geometry): the sets are
     // accumulated by ONE launch (blockIdx.y = set) and run beside each other; from 2^16 runs on one launch per set, back to
     // back, measures better (same box, profiles/r03_s14_small_sums.txt: a rank's share of a 2^20 key over 8 ranks 2.08 vs 2.33 ms,
     // 2^18 proofs 4.15 vs 4.45 ms, 2^19 6.2 vs 6.43 ms; 2^14 / 2^16 proofs the other way: 1.55 vs 2.1 ms, 1.93 vs 2.4 ms with the
     // shorter tasks)
     const MsmPlanInfo& I0 = M.plan[plan_ids ? plan_ids[0] : M.cur].info;
-    const bool batched = nsets > 1 && I0.valid && I0.n && I0.nbuckets <= (1u << 16);
+    const bool batched = nsets > 1 && I0.valid && I0.shape.n && I0.shape.nbuckets <= (1u << 16);
     for (int k = 0; k < nsets && !rc; k++) {
         if (plan_ids) msm_select_plan(L, plan_ids[k]);
         rc = msm_launch_acc<G1R29, G1>(L, 0, d_points[k], prepared, &slots[k], s, batched);
@@ -1982,8 +1964,7 @@ int msm_g1_launch_batch(Lane& L, const Affine<Fq>* const* d_points, int nsets, b
         for (int k = 0; k < nsets; k++) Ps[k] = &M.slot[slots[k]];
         rc = msm_acc_sets<G1R29>(L, Ps, nsets, 0, s);
     }
-    if (!rc) rc = tail_pair_g1() ? msm_launch_tail<TailCurve<G1R29>::paired, TailCurve<G1R29>::type>(L, slots, nsets, s, -1, s_levels)
-                                 : msm_launch_tail<TailCurve<G1R29>::type>(L, slots, nsets, s, -1, s_levels);
+    if (!rc) rc = msm_launch_tail_for<G1R29>(L, slots, nsets, s, -1, s_levels);
     if (rc) msm_abort_slots(L, slots, nsets, s, nullptr);
     return rc;
 }
@@ -1999,11 +1980,10 @@ int msm_g1_launch_acc_only(Lane& L, const Affine<Fq>* d_points, bool prepared, i
     return msm_launch_acc<G1R29, G1>(L, 0, d_points, prepared, slot, s);
 }
 // two launches of msm_g1_launch_acc_only share one reduction tail where that is possible
-static bool msm_tail_mergeable(const MsmPlanInfo& a, const MsmPlanInfo& b) {
+static bool msm_tail_mergeable(const MsmPlanInfo& pa, const MsmPlanInfo& pb) {
+    const MsmShape &a = pa.shape, &b = pb.shape;
     return a.n && b.n && a.flat && b.flat && a.c == b.c && a.W == b.W && a.Wall == b.Wall && a.w_off == b.w_off && a.w_stride == b.w_stride &&
-           a.NB == b.NB && a.nbuckets == b.nbuckets && a.tNB == b.tNB && a.tP == b.tP && a.tW == b.tW && a.groups == b.groups &&
-           a.m1 == b.m1 && a.m2 == b.m2 && a.m == b.m && a.J1 == b.J1 && a.J == b.J && a.logJ == b.logJ && a.nsum == b.nsum &&
-           a.nrows == b.nrows && a.reduce == b.reduce;
+           a.NB == b.NB && a.nbuckets == b.nbuckets && pa.tail == pb.tail;
 }
 // ONE reduction tail on `s` over the bucket-wise sum of two launches (both accumulated on queues that `s` is ordered behind).  The
 // sum of the two reaches the host in slot_a (msm_g1_finish); slot_b stays busy until then and is never finished itself.  Launches
@@ -2017,15 +1997,11 @@ int msm_g1_launch_tail_merged(Lane& L, int slot_a, int slot_b, hipStream_t s, bo
     if (!A.active || !B.active || A.which != 0 || B.which != 0) return WS_ERR_ARG;
     int rc = WS_OK;
     if (msm_tail_mergeable(A.info, B.info)) {
-        rc = tail_pair_g1() ? msm_launch_tail<TailCurve<G1R29>::paired, TailCurve<G1R29>::type>(L, &slot_a, 1, s, slot_b)
-                            : msm_launch_tail<TailCurve<G1R29>::type>(L, &slot_a, 1, s, slot_b);
+        rc = msm_launch_tail_for<G1R29>(L, &slot_a, 1, s, slot_b);
         if (!rc) { A.partner = slot_b; *merged = true; }
     } else {
-        for (const int* one : {&slot_a, &slot_b}) {
-            if (rc) break;
-            rc = tail_pair_g1() ? msm_launch_tail<TailCurve<G1R29>::paired, TailCurve<G1R29>::type>(L, one, 1, s)
-                                : msm_launch_tail<TailCurve<G1R29>::type>(L, one, 1, s);
-        }
+        for (const int* one : {&slot_a, &slot_b})
+            if (!rc) rc = msm_launch_tail_for<G1R29>(L, one, 1, s);
     }
     return rc;
 }
@@ -2040,7 +2016,7 @@ static MsmPending* live_slot(Lane& L, int slot, int which) {
 }
 bool msm_ready(Lane& L, int slot) {
     MsmPending* P = live_slot(L, slot, -1);
-    return P && (P->info.n == 0 || (P->ev && hipEventQuery(P->ev) == hipSuccess));
+    return P && (P->info.shape.n == 0 ||(P->ev && hipEventQuery(P->ev) == hipSuccess));
 }
 int msm_g1_finish(Lane& L, int slot, XYZZ<Fq>* out_host) {
     MsmPending* P = live_slot(L, slot, 0);
@@ -2344,24 +2320,24 @@ int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table
     msm_select_plan(L, 0);
     if ((rc = msm_plan_dev(L, L.host_in[0].as<Fe>(), n, sh, s, table_c))) return rc;
     int id = 0;
-    if (h_mask && M.plan[0].info.n) {
+    if (h_mask && M.plan[0].info.shape.n) {
         WS_HIP_CHECK(L.host_in[1].reserve((size_t)n));
         if ((rc = upload_staged(L.host_in[1].p, h_mask, (size_t)n, s))) return rc;
         if ((rc = msm_plan_variant(L, 0, 2, L.host_in[1].as<uint8_t>(), s))) return rc;
         id = 2;
     }
     WS_HIP_CHECK(hipStreamSynchronize(s));
-    const MsmPlanInfo& I = M.plan[id].info;
-    const MsmPlanInfo& I0 = M.plan[0].info;          // (the variant shares the plain plan's coarse bins)
+    const MsmShape& I = M.plan[id].info.shape;
+    const MsmGrouping& ps = M.plan[0].info.ps;       // (the variant shares the plain plan's coarse bins)
     if (I.n == 0) return WS_OK;                      // (no pair, or a shard that owns no window: all words zero)
     const MsmScratch& S = M.plan[id].S;
     uint32_t cnt[8], nvals = 0;
     WS_HIP_CHECK(hipMemcpy(cnt, S.counters.p, sizeof cnt, hipMemcpyDeviceToHost));
-    WS_HIP_CHECK(hipMemcpy(&nvals, M.plan[0].S.counters.as<uint32_t>() + CNT_BINS + (I0.ps_nbins + 1) + I0.ps_nbins, 4, hipMemcpyDeviceToHost));
+    WS_HIP_CHECK(hipMemcpy(&nvals, M.plan[0].S.counters.as<uint32_t>() + CNT_BINS + (ps.nbins + 1) + ps.nbins, 4, hipMemcpyDeviceToHost));
     const uint32_t words[kMsmPlanInfoWords] = {
         I.c, I.Wall, I.W, I.w_off, I.w_stride, I.NB, I.nbuckets, I.flat ? 1u : 0u, I.lmax, I.hot_min,
-        I0.ps_lo_bits, I0.ps_idx_bits, I0.ps_nbins, I0.ps_e32 ? 1u : 0u, (I.Wall <= PRESORT_ONCE_W && I0.ps_tile == I0.ps_thr) ? 1u : 0u,
-        cnt[0], cnt[1], cnt[3], cnt[4], cnt[5], nvals, I0.ps_bthr, (uint32_t)I.n, 0u};
+        ps.lo_bits, ps.idx_bits, ps.nbins, ps.e32 ? 1u : 0u, (I.Wall <= PRESORT_ONCE_W && ps.tile == ps.thr) ? 1u : 0u,
+        cnt[0], cnt[1], cnt[3], cnt[4], cnt[5], nvals, ps.bthr, (uint32_t)I.n, 0u};
     // every size against what the plan's buffers hold, then against the caller's capacities
     if (cnt[3] > I.hot_cap || cnt[1] > I.hot_cap || cnt[4] > I.hot_cap / I.hot_min + 16 || (uint64_t)nvals > I.n * I.W) {
         set_last_error("selftest_msm_plan: the plan's counters exceed its buffers");
@@ -2380,6 +2356,24 @@ int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table
     if (multi && cnt[1]) WS_HIP_CHECK(hipMemcpy(multi, S.multi.p, (size_t)cnt[1] * sizeof(MultiBucket), hipMemcpyDeviceToHost));
     if (hot && cnt[4]) WS_HIP_CHECK(hipMemcpy(hot, S.hot.p, (size_t)cnt[4] * sizeof(HotBucket), hipMemcpyDeviceToHost));
     memcpy(info, words, sizeof words);
+    return WS_OK;
+}
+
+// ---- test hook (wsnark_selftest_msm_geometry): msm_plan_geometry's decisions as words (the order: include/wsnark.h) ----
+// No device, no context, no lane.  table_c == kMsmTableAuto: the width msm_table_window gives n pairs, as the key loaders ask for it.
+int selftest_msm_geometry(uint64_t n, uint32_t table_c, WindowShard sh, uint32_t* words) {
+    memset(words, 0, kMsmGeometryWords * sizeof(uint32_t));
+    MsmPlanInfo info;
+    const int rc = msm_plan_geometry(n, sh, table_c == kMsmTableAuto ? msm_table_window(n) : table_c, &info);
+    const MsmShape& I = info.shape;
+    const MsmGrouping& ps = info.ps;
+    const MsmTail& G = info.tail;
+    if (rc || I.n == 0) return rc;                   // (an error, no pair, or a shard that owns no window: all words zero)
+    const uint32_t w[kMsmGeometryWords] = {
+        (uint32_t)I.n, I.c, I.Wall, I.W, I.w_off, I.w_stride, I.NB, I.nbuckets, I.flat ? 1u : 0u, I.lmax, I.hot_min, I.hot_cap,
+        ps.lo_bits, ps.idx_bits, ps.nbins, ps.bthr, ps.HB, ps.tile, ps.thr, ps.valid ? 1u : 0u, ps.e32 ? 1u : 0u,
+        G.tW, G.tNB, G.tP, G.groups, G.m1, G.m2, G.m, G.J1, G.J, G.logJ, G.nsum, G.nrows, G.reduce};
+    memcpy(words, w, sizeof w);
     return WS_OK;
 }
 

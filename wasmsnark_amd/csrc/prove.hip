@@ -981,8 +981,6 @@ int groth16_prove_dist(ProvingKey* K, const Fe* d_witness, size_t witness_len, c
     uint8_t rec[kDistRecord];
     memset(rec, 0, sizeof rec);
     int exchanges = 0;
-    uint32_t log_n = 0;
-    while ((1u << log_n) < K->domain) log_n++;
     if (!rc) {
         MsmSums M;
         const CalcHFn calc_h = [&](hipStream_t s2, Fe* d_h) {

@@ -311,8 +311,7 @@ int batch_pass(ProvingKey* K, Lane& L, hipStream_t s, const BatchBufs& U, const 
     Context* X = K->owner;
     KernelTimer& T = X->timer;
     const uint32_t nv = K->n_vars, dom = K->domain, nwin = (256 + c - 1) / c;
-    int bits = 0;
-    while ((1u << bits) < dom) bits++;
+    const int bits = (int)ceil_log2(dom);
     int rc;
     // the scalars first: the multiples of delta need nothing else
     WS_HIP_CHECK(hipMemcpyAsync(U.sc, sc_host, (size_t)B * 96, hipMemcpyHostToDevice, s));
