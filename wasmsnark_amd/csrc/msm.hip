@@ -60,6 +60,14 @@ struct MsmScratch {
     DevBuf chunkS, chunkA, sums, points_conv;
     DevBuf hot_done;                 // device-scope completion counters of msm_combine_all (zero between launches)
     DevBuf tree_half, tree_done;     // msm_tree: halves of the unmasked rows and their completion counters (zero between launches)
+    // a plan's counter words (`counters`: two header blocks, then the coarse bins): which header block the current build uses, and what
+    // the fused planner's builds have left at zero for the next one (plan_counters_begin)
+    uint32_t blk = 0;                // header block of the current build: counters + blk * CNT_BLOCK
+    bool hdr_clean = false;          // the OTHER header block is zero
+    uint32_t bins_clean = 0;         // the bin counts and cursors of a plan of this many bins are zero (0: not known to be)
+    const void* cnt_ptr = nullptr;   // the allocation and the queue the two flags above were earned on
+    hipStream_t cnt_stream = nullptr;
+    bool fused = false;              // the current build runs the fused planner (the switch as msm_plan_begin / msm_plan_variant read it)
 };
 
 // ---------------------------------------------------------------------------
@@ -73,10 +81,14 @@ struct MsmScratch {
 // (vs 160 MB digits + ~830 MB three-pass radix sort + 64 MB bounds).
 // ---------------------------------------------------------------------------
 static const uint32_t PRESORT_MAX_BINS = 4096; // W * HB, 16 KiB of LDS counters
-// layout of a plan's counter block (u32 words): [0] partial slots, [1] multi-task buckets, [3] total tasks, [4] hot buckets,
-// [5] hot slices, [6] tasks of segment 0; task-length histograms of the two task segments at CNT_HIST (2 x 256), their
-// rank cursors at CNT_CURSOR (2 x 256), the coarse-bin counts / starts / cursors of the grouping pass from CNT_BINS on
-static const uint32_t CNT_HIST = 16, CNT_CURSOR = 16 + 512, CNT_BINS = 2048;
+// layout of a plan's counter words (u32).  A HEADER block of CNT_BLOCK words: [0] partial slots, [1] multi-task buckets, [3] total
+// tasks, [4] hot buckets, [5] hot slices, [6] tasks of segment 0, [7] the fused planner's arrival counter (zero between launches);
+// task-length histograms of the two task segments at CNT_HIST (2 x 256), their rank cursors at CNT_CURSOR (2 x 256).  A plan slot has
+// TWO header blocks, used by its builds in alternation (MsmScratch::blk; plan_counters gives the current one): a build's planner
+// clears the block the build before it used, so that no build starts with a memset (WSNARK_PLAN_FUSED).  The coarse-bin counts /
+// starts / cursors of the grouping pass follow from CNT_BINS on, once per slot: they die inside the build (presort_bins clears the
+// counts and the cursors; the starts are rewritten by every build and read by the plan's variants).
+static const uint32_t CNT_HIST = 16, CNT_CURSOR = 16 + 512, CNT_ARRIVE = 7, CNT_BLOCK = 2048, CNT_BINS = 2 * CNT_BLOCK;
 
 // calls f(k, d, neg) for every owned window k (local index) with a non-zero signed digit d in [1, NB]
 template <class Fn>
@@ -415,13 +427,16 @@ __global__ __launch_bounds__(1024) void presort_bins(const E* __restrict__ entri
                                                        uint32_t lo_bits, uint32_t idx_bits, uint32_t* __restrict__ vals_out,
                                                        uint32_t* __restrict__ bstart, uint32_t* __restrict__ bend,
                                                        uint32_t lmax, uint32_t* __restrict__ hist,
-                                                       const uint8_t* __restrict__ mask, uint32_t mask_mod) {
+                                                       const uint8_t* __restrict__ mask, uint32_t mask_mod, uint32_t* __restrict__ bin_dead) {
     __shared__ uint32_t sub[1u << PRESORT_MAX_LO];
     __shared__ uint32_t off[1u << PRESORT_MAX_LO];
     __shared__ uint32_t wsum[17];
     __shared__ uint32_t lhist[256];
     const uint32_t bin = blockIdx.x, SUB = 1u << lo_bits;
     const uint32_t s = bin_start[bin], e = bin_start[bin + 1];
+    // bin_dead (the fused planner's builds): the bin counts, with the cursors two arrays of gridDim.x + 1 words behind them.  The
+    // scatter was their last reader; this bin's two words are zero again for the slot's next build.
+    if (bin_dead && threadIdx.x == 0) { bin_dead[bin] = 0; bin_dead[2 * (gridDim.x + 1) + bin] = 0; }
     for (uint32_t t = threadIdx.x; t < SUB; t += blockDim.x) sub[t] = 0;
     for (uint32_t t = threadIdx.x; t < 256; t += blockDim.x) lhist[t] = 0;
     __syncthreads();
@@ -718,6 +733,127 @@ __global__ __launch_bounds__(256) void msm_plan_emit_hot(const HotBucket* __rest
         for (uint32_t k = threadIdx.x; k + 1 < h.ntasks; k += blockDim.x)
             tasks[h.task_base + k] = Task{PARTIAL_FLAG | (h.first_partial + k), h.start + k * lmax, lmax};
         if (threadIdx.x == 0)
+            tasks[h.rem_index] = Task{PARTIAL_FLAG | (h.first_partial + h.ntasks - 1), h.start + (h.ntasks - 1) * lmax, h.rem};
+    }
+}
+
+// The two kernels above as ONE launch (WSNARK_PLAN_FUSED, the default), with the planner's device atomics untied.  msm_plan_emit
+// starts a workgroup per 256 buckets, and each sends a returning atomic per length key it holds to the 256 cursor words (eight cache
+// lines) and one per split bucket to counters[0] / [1]: 2 048 workgroups x ~35 keys on a uniform 2^20 witness, and the kernel took a
+// constant 46-50 us for a few microseconds of memory traffic.  Here a workgroup of PLAN_THREADS threads covers SPAN buckets,
+// SPAN / PLAN_THREADS per thread with their bounds' loads in flight together; LDS atomics rank the buckets' tasks within the
+// workgroup by key as before and also sum its partial slots, multi and hot records and hot slices, so that the device sees one
+// returning atomic per key held and ONE each for counters[0], [1], [4], [5] per workgroup.  The hot buckets' task lists are written
+// by the workgroup that arrives last at counters[CNT_ARRIVE] (device scope, fences on both sides, left at zero: as msm_tree and
+// msm_combine_all find their last workgroup); no workgroup waits for another.  Workgroup 0 clears `retired`, the header block of
+// the slot's previous build.
+// Measured at 2^19 buckets (profiles/plan_fused_ab.txt): the time follows the NUMBER OF WORKGROUPS, with its minimum at 512 (two
+// per CU) -- 22 us per build at SPAN = 1024 (with one bucket per thread, 1024 threads, the same), 30 us at 2 048, 50 us at 4 096;
+// workgroups of 256 threads: 33 us at 512 buckets each, 59 us at 256 (more than the two kernels replaced: the scan, the barriers
+// and the arrival are paid per workgroup).
+static const uint32_t PLAN_THREADS = 512;
+template <uint32_t SPAN>
+__global__ __launch_bounds__(PLAN_THREADS) void msm_plan_fused(const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ bend,
+                                                        uint32_t nbuckets, uint32_t lmax, uint32_t hot_min, uint32_t* counters,
+                                                        Task* tasks, MultiBucket* __restrict__ multi, HotBucket* hot,
+                                                        uint32_t* __restrict__ retired) {
+    constexpr uint32_t THREADS = PLAN_THREADS;
+    static_assert(THREADS % 256 == 0 && THREADS <= 1024 && SPAN % THREADS == 0 && SPAN / THREADS <= 16, "whole rows of buckets, at most 16 per thread; a thread per key");
+    constexpr uint32_t PER = SPAN / THREADS;
+    __shared__ uint32_t lcnt[256];
+    __shared__ uint32_t lbase[256];
+    __shared__ uint32_t first[256];          // start of key k's slots = number of tasks with a longer key
+    __shared__ uint32_t wsum[17];
+    __shared__ uint32_t wg[5];               // the workgroup's partial slots, multi records, hot records, hot slices; [4]: last to arrive
+    __shared__ uint32_t wgb[4];              // where they start in counters[0], [1], [4], [5]
+    const uint32_t tid = threadIdx.x;
+    uint32_t s[PER], cnt[PER];
+#pragma unroll
+    for (uint32_t j = 0; j < PER; j++) {
+        const uint32_t b = blockIdx.x * SPAN + j * THREADS + tid;
+        s[j] = b < nbuckets ? bstart[b] : 0;
+        cnt[j] = b < nbuckets ? bend[b] : 0;
+    }
+    if (blockIdx.x == 0 && retired)
+        for (uint32_t k = tid; k < CNT_BLOCK; k += THREADS) retired[k] = 0;
+    if (tid < 256) lcnt[tid] = 0;
+    if (tid < 5) wg[tid] = 0;
+    {
+        // first[k] = tasks with a longer key than k: the exclusive scan of the (complete) histogram from key 255 down
+        uint32_t total;
+        const uint32_t longer = block_exclusive_scan(tid < 256 ? counters[CNT_HIST + 255 - tid] : 0u, wsum, &total);
+        if (tid < 256) first[255 - tid] = longer;
+        if (blockIdx.x == 0 && tid == 0) counters[3] = total;
+    }
+    __syncthreads();
+    uint32_t r255[PER], rrem[PER], pofs[PER], ridx[PER], hsl[PER];
+#pragma unroll
+    for (uint32_t j = 0; j < PER; j++) {
+        cnt[j] -= s[j];
+        r255[j] = rrem[j] = pofs[j] = ridx[j] = hsl[j] = 0;
+        if (cnt[j]) {
+            const uint32_t nt = (cnt[j] + lmax - 1) / lmax, rem = cnt[j] - (nt - 1) * lmax;
+            if (nt > 1) {
+                r255[j] = atomicAdd(&lcnt[255], nt - 1);
+                pofs[j] = atomicAdd(&wg[0], nt);
+                if (nt >= hot_min) {
+                    ridx[j] = atomicAdd(&wg[2], 1u);
+                    hsl[j] = atomicAdd(&wg[3], (nt + HOT_SLICE - 1) / HOT_SLICE);
+                } else {
+                    ridx[j] = atomicAdd(&wg[1], 1u);
+                }
+            }
+            rrem[j] = atomicAdd(&lcnt[len_key(rem, lmax)], 1u);
+        }
+    }
+    __syncthreads();
+    // the workgroup's device atomics: one per key it holds, one per counter it adds to
+    if (tid < 256) {
+        const uint32_t held = lcnt[tid];
+        lbase[tid] = held ? first[tid] + atomicAdd(&counters[CNT_CURSOR + tid], held) : 0;
+        if (tid < 4) {
+            const uint32_t add = wg[tid];
+            wgb[tid] = add ? atomicAdd(&counters[tid < 2 ? tid : tid + 2], add) : 0;     // counters[0], [1], [4], [5]
+        }
+    }
+    __syncthreads();
+    const bool hot_here = wg[2] != 0;
+#pragma unroll
+    for (uint32_t j = 0; j < PER; j++) {
+        if (!cnt[j]) continue;
+        const uint32_t b = blockIdx.x * SPAN + j * THREADS + tid;
+        const uint32_t nt = (cnt[j] + lmax - 1) / lmax, rem = cnt[j] - (nt - 1) * lmax;
+        const uint32_t at_rem = lbase[len_key(rem, lmax)] + rrem[j];
+        if (nt == 1) {
+            tasks[at_rem] = Task{b, s[j], rem};
+            continue;
+        }
+        const uint32_t pbase = wgb[0] + pofs[j], at_full = lbase[255] + r255[j];
+        if (nt >= hot_min) {      // (its task list: the last workgroup, below; its combine: msm_combine_all's hot stage)
+            hot[wgb[2] + ridx[j]] = HotBucket{b, pbase, nt, at_full, at_rem, s[j], rem, wgb[3] + hsl[j]};
+            continue;
+        }
+        multi[wgb[1] + ridx[j]] = MultiBucket{b, pbase, nt};
+        for (uint32_t k = 0; k + 1 < nt; k++) tasks[at_full + k] = Task{PARTIAL_FLAG | (pbase + k), s[j] + k * lmax, lmax};
+        tasks[at_rem] = Task{PARTIAL_FLAG | (pbase + nt - 1), s[j] + (nt - 1) * lmax, rem};
+    }
+    // arrival: hot records are visible to the device before their workgroup is counted.  A fence writes the L2's dirty lines back --
+    // the whole task list -- and on a uniform witness no workgroup has a hot record, so only those that do pay for one (wg[2]: the
+    // workgroup's hot records, the same for every thread; measured: profiles/plan_fused_ab.txt)
+    if (hot_here) __threadfence();
+    __syncthreads();
+    if (tid == 0) wg[4] = atomicAdd(&counters[CNT_ARRIVE], 1u) + 1 == gridDim.x ? 1u : 0u;
+    __syncthreads();
+    if (!wg[4]) return;
+    if (tid == 0) counters[CNT_ARRIVE] = 0;
+    const uint32_t nhot = atomicAdd(&counters[4], 0u);                // (complete: every workgroup added its share before it arrived)
+    if (!nhot) return;
+    __threadfence();                                                  // every workgroup's hot records are visible from here on
+    for (uint32_t hb = 0; hb < nhot; hb++) {
+        const HotBucket h = hot[hb];
+        for (uint32_t k = tid; k + 1 < h.ntasks; k += THREADS)
+            tasks[h.task_base + k] = Task{PARTIAL_FLAG | (h.first_partial + k), h.start + k * lmax, lmax};
+        if (tid == 0)
             tasks[h.rem_index] = Task{PARTIAL_FLAG | (h.first_partial + h.ntasks - 1), h.start + (h.ntasks - 1) * lmax, h.rem};
     }
 }
@@ -1221,6 +1357,8 @@ void msm_abort_slots(Lane& L, const int* slots, int nslots, hipStream_t a, hipSt
     if (!L.msm) return;
     for (int k = 0; k < nslots; k++)
         if (slots[k] >= 0 && slots[k] < kPendingSlots) L.msm->slot[slots[k]].active = false;
+    // (whatever the plans' builds had left at zero for their next build is no longer relied on: the next ones start with a memset)
+    for (auto& p : L.msm->plan) { p.S.hdr_clean = false; p.S.bins_clean = 0; }
 }
 
 // ---- the host's Horner chains over the rows a tail has left in pinned memory (msm_finish_t picks one).  Three forms, kept apart on
@@ -1475,6 +1613,39 @@ static int reserve_plan_buffers(MsmScratch& S, const MsmPlanInfo& info) {
     return WS_OK;
 }
 
+// the header block of a plan's current build: what every reader of counters[] takes
+static uint32_t* plan_counters(const MsmScratch& S) { return S.counters.as<uint32_t>() + (size_t)S.blk * CNT_BLOCK; }
+
+// WSNARK_PLAN_FUSED: 1 (default) = the planner as one launch (msm_plan_fused) and no memset in front of a build in steady state;
+// 0 = msm_plan_emit + msm_plan_emit_hot behind a memset, as before.  PLAN_SPAN: buckets per workgroup of the fused planner.
+static bool plan_fused_switch() { return tuning_get("PLAN_FUSED", 1) != 0; }
+static const uint32_t PLAN_SPAN_DEFAULT = 1024;
+
+// Zeroed counter words for a build of plan scratch S on queue s (nbins: of the plan's own grouping pass; 0: a variant, which reads
+// its source's bins).  Steady state of the fused planner: the slot's last build ended well on this queue and left the other header
+// block (its planner) and the bin counts and cursors (its presort_bins) at zero -- the build moves to the other block, no launch.
+// The other block is free: the caller has put the queue behind every user of the slot's plan (wait_plan_users).  Anything else -- the
+// slot's first build, another bin count, allocation or queue, a build that was abandoned or failed (the flags are set where a build
+// ends well: plan_counters_done), msm_abort_slots, the switch off -- is one memset of everything, as before.
+static int plan_counters_begin(MsmScratch& S, uint32_t nbins, hipStream_t s) {
+    S.fused = plan_fused_switch();
+    const bool steady = S.fused && S.hdr_clean && S.cnt_ptr == S.counters.p && S.cnt_stream == s && (nbins == 0 || S.bins_clean == nbins);
+    S.hdr_clean = false;
+    if (nbins) S.bins_clean = 0;
+    if (steady) { S.blk ^= 1u; return WS_OK; }
+    S.blk = 0;
+    if (!nbins) S.bins_clean = 0;        // (a memset on another queue or allocation: nothing older is relied on)
+    WS_HIP_CHECK(hipMemsetAsync(S.counters.p, 0, (CNT_BINS + (nbins ? 3 * ((size_t)nbins + 1) : 0)) * 4, s));   // (headers; counts, starts, cursors)
+    return WS_OK;
+}
+static void plan_counters_done(MsmScratch& S, uint32_t nbins, hipStream_t s) {
+    if (!S.fused) return;
+    S.hdr_clean = true;
+    if (nbins) S.bins_clean = nbins;
+    S.cnt_ptr = S.counters.p;
+    S.cnt_stream = s;
+}
+
 int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t table_c) {
     if (!ctx()) return WS_ERR_NOINIT;
     if (!s) s = L.stream;
@@ -1486,10 +1657,7 @@ int msm_plan_begin(Lane& L, uint64_t n, WindowShard sh, hipStream_t s, uint32_t 
     MsmScratch& S = M.plan[M.cur].S;
     if ((rc = reserve_plan_buffers(S, I))) return rc;
     WS_HIP_CHECK(S.entries.reserve(I.shape.n * I.shape.W * (I.ps.e32 ? 4 : 8)));
-    // counters: [0] partial slots, [1] multi-task buckets, [3] total tasks; [16..271] length histogram,
-    // [272..527] cursors
-    // (the coarse-bin counts of the grouping pass follow at [1024 ..]: one memset clears both)
-    WS_HIP_CHECK(hipMemsetAsync(S.counters.p, 0, (CNT_BINS + 3 * ((size_t)I.ps.nbins + 1)) * 4, s));   // (counts, starts, cursors)
+    if ((rc = plan_counters_begin(S, I.ps.nbins, s))) return rc;
     I.building = true;
     return WS_OK;
 }
@@ -1507,24 +1675,38 @@ static int launch_bins_and_tasks(const MsmPlanInfo& info, const MsmScratch& src,
     const uint32_t nbuckets = info.shape.nbuckets, lmax = info.shape.lmax;
     const dim3 grid(ps.nbins), blk(ps.bthr);
     const uint32_t* bin_start = src.counters.as<uint32_t>() + CNT_BINS + (ps.nbins + 1);
-    uint32_t* d_cnt = S.counters.as<uint32_t>();
+    uint32_t* d_cnt = plan_counters(S);
     uint32_t* hist = d_cnt + CNT_HIST;
+    // fused builds of a plan's own bins: presort_bins clears the bin counts and cursors behind their last reader, the scatter
+    uint32_t* bin_dead = (S.fused && !mask) ? S.counters.as<uint32_t>() + CNT_BINS : nullptr;
     uint32_t* vals = S.vals_out.as<uint32_t>();
     uint32_t* bs = S.bstart.as<uint32_t>();
     uint32_t* be = S.bend.as<uint32_t>();
     T.begin("msm_presort_bins", s);
     if (ps.e32 && presort_stage_bins())
-        hipLaunchKernelGGL((presort_bins<uint32_t, true>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod);
+        hipLaunchKernelGGL((presort_bins<uint32_t, true>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod, bin_dead);
     else if (ps.e32)
-        hipLaunchKernelGGL((presort_bins<uint32_t, false>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod);
+        hipLaunchKernelGGL((presort_bins<uint32_t, false>), grid, blk, 0, s, src.entries.as<uint32_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod, bin_dead);
     else
-        hipLaunchKernelGGL((presort_bins<uint64_t, false>), grid, blk, 0, s, src.entries.as<uint64_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod);
+        hipLaunchKernelGGL((presort_bins<uint64_t, false>), grid, blk, 0, s, src.entries.as<uint64_t>(), bin_start, ps.lo_bits, ps.idx_bits, vals, bs, be, lmax, hist, mask, mask_mod, bin_dead);
     T.end(s);
     WS_HIP_CHECK(hipGetLastError());
     T.begin("msm_plan", s);
-    hipLaunchKernelGGL(msm_plan_emit, dim3(ceil_div_u64(nbuckets, 256)), dim3(256), 0, s, bs, be, nbuckets, lmax, hist, d_cnt + CNT_CURSOR,
-                       S.tasks.as<Task>(), d_cnt, S.multi.as<MultiBucket>(), S.hot.as<HotBucket>(), info.shape.hot_min);
-    hipLaunchKernelGGL(msm_plan_emit_hot, dim3(64), dim3(256), 0, s, S.hot.as<HotBucket>(), d_cnt, lmax, S.tasks.as<Task>());
+    if (S.fused) {
+        uint32_t* retired = S.counters.as<uint32_t>() + (size_t)(S.blk ^ 1u) * CNT_BLOCK;
+        const long span = tuning_get("PLAN_SPAN", PLAN_SPAN_DEFAULT);
+        auto launch = [&](auto kernel, uint32_t sp) {
+            hipLaunchKernelGGL(kernel, dim3(ceil_div_u64(nbuckets, sp)), dim3(PLAN_THREADS), 0, s, bs, be, nbuckets, lmax, info.shape.hot_min, d_cnt,
+                               S.tasks.as<Task>(), S.multi.as<MultiBucket>(), S.hot.as<HotBucket>(), retired);
+        };
+        if (span == 2048) launch(msm_plan_fused<2048>, 2048u);
+        else if (span == 4096) launch(msm_plan_fused<4096>, 4096u);
+        else launch(msm_plan_fused<PLAN_SPAN_DEFAULT>, PLAN_SPAN_DEFAULT);
+    } else {
+        hipLaunchKernelGGL(msm_plan_emit, dim3(ceil_div_u64(nbuckets, 256)), dim3(256), 0, s, bs, be, nbuckets, lmax, hist, d_cnt + CNT_CURSOR,
+                           S.tasks.as<Task>(), d_cnt, S.multi.as<MultiBucket>(), S.hot.as<HotBucket>(), info.shape.hot_min);
+        hipLaunchKernelGGL(msm_plan_emit_hot, dim3(64), dim3(256), 0, s, S.hot.as<HotBucket>(), d_cnt, lmax, S.tasks.as<Task>());
+    }
     T.end(s);
     WS_HIP_CHECK(hipGetLastError());
     return WS_OK;
@@ -1600,6 +1782,7 @@ int msm_plan_finish(Lane& L, const Fe* d_scalars, hipStream_t s) {
     // tasks <= total/lmax + nbuckets <= hot_cap, so the worst-case grids below always cover them
     I.ntasks = I.shape.hot_cap;
     I.valid = true;
+    plan_counters_done(S, nbins, s);
     return WS_OK;
 }
 
@@ -1627,9 +1810,10 @@ int msm_plan_variant(Lane& L, int src_id, int dst_id, const uint8_t* d_mask, hip
     I.ps.valid = false;
     I.valid = false;
     if ((rc = reserve_plan_buffers(S, src))) return rc;
-    WS_HIP_CHECK(hipMemsetAsync(S.counters.p, 0, (size_t)CNT_BINS * 4, s));
+    if ((rc = plan_counters_begin(S, 0u, s))) return rc;
     if ((rc = launch_bins_and_tasks(src, SS, S, d_mask, src.shape.flat ? (uint32_t)src.shape.n : 0u, s))) return rc;      // (the source's bin starts and thread count)
     I.valid = true;
+    plan_counters_done(S, 0u, s);
     return WS_OK;
 }
 
@@ -1649,7 +1833,7 @@ static int msm_acc_sets(Lane& L, MsmPending* const* Ps, int nsets, int which, hi
         as.points[k] = reinterpret_cast<const typename C::AffP*>(Q.d_points_used);
         as.vals[k] = QS.vals_out.as<uint32_t>();
         as.tasks[k] = QS.tasks.as<Task>();
-        as.counters[k] = QS.counters.as<uint32_t>();
+        as.counters[k] = plan_counters(QS);
         as.multi[k] = QS.multi.as<MultiBucket>();
         as.hot[k] = QS.hot.as<HotBucket>();
         as.buckets[k] = Q.S.buckets.template as<Pt>();
@@ -2318,6 +2502,15 @@ int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table
         if ((rc = upload_staged(L.host_in[0].p, h_scalars, (size_t)n * 32, s))) return rc;
     }
     msm_select_plan(L, 0);
+    if (n && tuning_get("PLAN_HOOK_ABANDON", 0) != 0) {
+        // (tests: a build given up between msm_plan_begin and msm_plan_finish, with its histogram taken -- what a proof that fails
+        //  while its witness arrives leaves behind.  The next build of the slot must not rely on anything this one touched.)
+        if ((rc = msm_plan_begin(L, n, sh, s, table_c))) return rc;
+        if ((rc = msm_plan_count(L, L.host_in[0].as<Fe>(), 0, n, s))) return rc;
+        WS_HIP_CHECK(hipStreamSynchronize(s));
+        set_last_error("selftest_msm_plan: the build was abandoned on request (PLAN_HOOK_ABANDON)");
+        return WS_ERR_ARG;
+    }
     if ((rc = msm_plan_dev(L, L.host_in[0].as<Fe>(), n, sh, s, table_c))) return rc;
     int id = 0;
     if (h_mask && M.plan[0].info.shape.n) {
@@ -2332,12 +2525,24 @@ int selftest_msm_plan(Lane& L, const void* h_scalars, uint64_t n, uint32_t table
     if (I.n == 0) return WS_OK;                      // (no pair, or a shard that owns no window: all words zero)
     const MsmScratch& S = M.plan[id].S;
     uint32_t cnt[8], nvals = 0;
-    WS_HIP_CHECK(hipMemcpy(cnt, S.counters.p, sizeof cnt, hipMemcpyDeviceToHost));
+    WS_HIP_CHECK(hipMemcpy(cnt, plan_counters(S), sizeof cnt, hipMemcpyDeviceToHost));
     WS_HIP_CHECK(hipMemcpy(&nvals, M.plan[0].S.counters.as<uint32_t>() + CNT_BINS + (ps.nbins + 1) + ps.nbins, 4, hipMemcpyDeviceToHost));
+    // word 23: what the build must have left at zero and did not -- the planner's arrival counter, the slot's other header block,
+    // and (fused builds) the bin counts and cursors of the grouping pass.  Words, counted.
+    uint32_t left = cnt[CNT_ARRIVE] ? 1u : 0u;
+    {
+        std::vector<uint32_t> w(std::max<size_t>(CNT_BLOCK, 3 * ((size_t)ps.nbins + 1)));
+        WS_HIP_CHECK(hipMemcpy(w.data(), S.counters.as<uint32_t>() + (size_t)(S.blk ^ 1u) * CNT_BLOCK, (size_t)CNT_BLOCK * 4, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < CNT_BLOCK; k++) left += w[k] ? 1u : 0u;
+        if (M.plan[0].S.fused) {
+            WS_HIP_CHECK(hipMemcpy(w.data(), M.plan[0].S.counters.as<uint32_t>() + CNT_BINS, 3 * ((size_t)ps.nbins + 1) * 4, hipMemcpyDeviceToHost));
+            for (uint32_t k = 0; k <= ps.nbins; k++) left += (w[k] ? 1u : 0u) + (w[2 * ((size_t)ps.nbins + 1) + k] ? 1u : 0u);
+        }
+    }
     const uint32_t words[kMsmPlanInfoWords] = {
         I.c, I.Wall, I.W, I.w_off, I.w_stride, I.NB, I.nbuckets, I.flat ? 1u : 0u, I.lmax, I.hot_min,
         ps.lo_bits, ps.idx_bits, ps.nbins, ps.e32 ? 1u : 0u, (I.Wall <= PRESORT_ONCE_W && ps.tile == ps.thr) ? 1u : 0u,
-        cnt[0], cnt[1], cnt[3], cnt[4], cnt[5], nvals, ps.bthr, (uint32_t)I.n, 0u};
+        cnt[0], cnt[1], cnt[3], cnt[4], cnt[5], nvals, ps.bthr, (uint32_t)I.n, left};
     // every size against what the plan's buffers hold, then against the caller's capacities
     if (cnt[3] > I.hot_cap || cnt[1] > I.hot_cap || cnt[4] > I.hot_cap / I.hot_min + 16 || (uint64_t)nvals > I.n * I.W) {
         set_last_error("selftest_msm_plan: the plan's counters exceed its buffers");
