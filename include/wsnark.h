@@ -1027,6 +1027,54 @@ int wsnark_points_info(const wsnark_points_t* handle, int* group, uint64_t* n, u
 int wsnark_points_msm(wsnark_points_t* handle, const void* scalars, uint64_t n, void* out);
 int wsnark_points_msm_dev(wsnark_points_t* handle, const void* d_scalars, uint64_t n, void* out_host, void* stream);
 
+/* ---- KZG commitments on a powers-of-tau transcript: commit, open, verify (csrc/kzg.hip): NO reference counterpart ----
+ * The tau_g1 array of a transcript (wsnark_powers_t) is also the structured reference string of the KZG scheme that snarkjs' PLONK and
+ * FFLONK, gnark's PLONK and halo2-KZG use on this curve: C = sum_k f[k] tau^k G commits to f, pi = commit((f - f(z)) / (X - z)) opens
+ * it at z, and two pairings check the opening.  The sums are the resident-bases sums above, the transform is wsnark_fr_ntt's; the
+ * division by (X - z) and the fold of several polynomials under a challenge are kernels of their own (DESIGN.md "KZG").
+ *   Scalars -- coefficients, z, gamma, y -- are 32-byte plain little-endian integers; inputs may be any 256-bit value and are taken
+ *   mod r, outputs are canonical.  A polynomial is len coefficients, lowest degree first; count polynomials are stored back to back.
+ *   G1 points are 64-byte affine Montgomery points, x == 0 is infinity; a result at infinity is 64 zero bytes and every other result
+ *   is affine and canonical: results compare byte for byte.
+ *   wsnark_kzg_srs_load: tau_g1[k] = tau^k g1, k < n, n in [1, 2^24], on the host; they become resident as wsnark_points_load makes
+ *     them (window tables where they fit).  Every power gets the audit's two cheap tests: a coordinate >= q, a point off the curve
+ *     or one at infinity is WSNARK_ERR_FORMAT, and wsnark_last_error names the first index.  tau_g1[0] is the commitment generator
+ *     and need not be the standard one.  Whether the points ARE the powers of one tau is wsnark_powers_check's question, not this
+ *     call's.  The handle is read-only after the load: any number of threads may commit and open on it at once.
+ *   wsnark_fr_poly_eval: out_y[i] = f_i(z).  wsnark_fr_poly_divide: out_q = (f - f(z)) / (X - z), len - 1 coefficients (none for
+ *     len == 1), out_y32 = f(z); _dev: d_poly and d_q resident and NOT overlapping, the value still goes to the host.  len in
+ *     [1, 2^24]; z = 0 and z >= r are ordinary inputs.
+ *   wsnark_kzg_commit: out[i] = sum_k f_i[k] tau_g1[k], len <= n.  form 0: coefficients.  form 1: len evaluations on the size-len
+ *     domain of wsnark_fr_ntt (len a power of two): the call runs the inverse transform first.  For len < n the sum runs over the
+ *     first len points or, padded with zeros, over the whole table, whichever was measured faster (KZG_PAD_PCT); same bytes.
+ *   wsnark_kzg_open: out_y[i] = f_i(z) for every polynomial, and ONE proof pi = commit(q), q the quotient of F = sum_i gamma^i f_i
+ *     at z.  count == 1 ignores gamma, which may then be NULL.  gamma is the caller's Fiat-Shamir challenge.
+ *   wsnark_kzg_verify: with C = sum gamma^i C_i and y = sum gamma^i y_i it checks e(C - y g1 + z pi, g2) == e(pi, tau g2) on the
+ *     host (the curve and pairing of wsnark_groth16_verify); it needs no wsnark_init.  g2_tau_g2_256 = g2 | tau g2, 128 bytes each.
+ *     An unreduced coordinate is WSNARK_ERR_FORMAT; an off-curve point, a G2 point outside the subgroup, g1, g2 or tau g2 at infinity
+ *     give *valid = 0; pi or a C_i at infinity is legal (a constant polynomial's proof is infinity).
+ *   Errors: NULL pointers or a NULL handle WSNARK_ERR_ARG; len == 0, len > n, len > 2^24, count > 65535, count x len > 2^28, a len that is no
+ *     power of two with form 1: WSNARK_ERR_SIZE; count == 0: WSNARK_OK and nothing is touched; every call but wsnark_kzg_verify
+ *     before wsnark_init: WSNARK_ERR_NOINIT.  On every error the outputs are left untouched.  Each call takes a lane.
+ *   Out of scope: G2 commitments; openings of one polynomial at several points; a batch verifier with a single verdict; Fiat-Shamir
+ *     transcripts; readers of .ptau, halo2 or gnark SRS files; group (multi-GPU) and sharded handles. */
+typedef struct wsnark_kzg_srs wsnark_kzg_srs_t;
+int wsnark_kzg_srs_load(const void* tau_g1, uint64_t n, wsnark_kzg_srs_t** out_handle);
+void wsnark_kzg_srs_free(wsnark_kzg_srs_t* handle);      /* NULL ignored */
+int wsnark_kzg_srs_info(const wsnark_kzg_srs_t* handle, uint64_t* n, uint64_t* table_bytes);
+int wsnark_fr_poly_eval(const void* polys, uint64_t len, uint64_t count, const void* z32, void* out_y);
+int wsnark_fr_poly_divide(const void* poly, uint64_t len, const void* z32, void* out_q, void* out_y32);
+int wsnark_fr_poly_divide_dev(const void* d_poly, uint64_t len, const void* z32, void* d_q, void* out_y32_host, void* stream);
+int wsnark_kzg_commit(wsnark_kzg_srs_t* handle, const void* polys, uint64_t len, uint64_t count, int form, void* out_commitments);
+int wsnark_kzg_commit_dev(wsnark_kzg_srs_t* handle, const void* d_polys, uint64_t len, uint64_t count, int form, void* out_commitments_host,
+                          void* stream);
+int wsnark_kzg_open(wsnark_kzg_srs_t* handle, const void* polys, uint64_t len, uint64_t count, const void* z32, const void* gamma32,
+                    void* out_y, void* out_proof64);
+int wsnark_kzg_open_dev(wsnark_kzg_srs_t* handle, const void* d_polys, uint64_t len, uint64_t count, const void* z32, const void* gamma32,
+                        void* out_y_host, void* out_proof64_host, void* stream);
+int wsnark_kzg_verify(const void* g1_64, const void* g2_tau_g2_256, const void* commitments, uint64_t count, const void* z32,
+                      const void* gamma32, const void* ys, const void* proof64, int* valid);
+
 /* ---- several GPUs in ONE process (csrc/group.hip; round 5) ----
  * The reference's host is one process that starts W workers (src/bn128.js:173-265, `build()`), cuts every multi-exponentiation
  * into W contiguous ranges of the pairs, posts one to each worker and adds the partial results (:353-415), and runs the five

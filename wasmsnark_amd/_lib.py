@@ -32,6 +32,8 @@ SYMBOLS = [
     "wsnark_selftest_msm_geometry", "wsnark_selftest_msm_accumulate",
     "wsnark_timing_enable", "wsnark_timing_reset", "wsnark_timing_report", "wsnark_peak_probe", "wsnark_tuning_set", "wsnark_host_alloc", "wsnark_host_free",
     "wsnark_points_load", "wsnark_points_free", "wsnark_points_info", "wsnark_points_msm", "wsnark_points_msm_dev",
+    "wsnark_kzg_srs_load", "wsnark_kzg_srs_free", "wsnark_kzg_srs_info", "wsnark_fr_poly_eval", "wsnark_fr_poly_divide", "wsnark_fr_poly_divide_dev",
+    "wsnark_kzg_commit", "wsnark_kzg_commit_dev", "wsnark_kzg_open", "wsnark_kzg_open_dev", "wsnark_kzg_verify",
     "wsnark_group_create", "wsnark_group_free", "wsnark_group_size", "wsnark_group_pkey_load", "wsnark_group_pkey_load_sections", "wsnark_group_pkey_load_file", "wsnark_group_pkey_free",
     "wsnark_group_pkey_info", "wsnark_group_pkey_wait_tables", "wsnark_group_prove", "wsnark_group_last_blinding", "wsnark_group_g1_msm", "wsnark_group_g2_msm",
 ]
@@ -203,6 +205,18 @@ class Lib:
         c.wsnark_points_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
         c.wsnark_points_msm.argtypes = [vp, vp, u64, vp]
         c.wsnark_points_msm_dev.argtypes = [vp, vp, u64, vp, vp]
+        c.wsnark_kzg_srs_load.argtypes = [vp, u64, C.POINTER(vp)]
+        c.wsnark_kzg_srs_free.argtypes = [vp]
+        c.wsnark_kzg_srs_free.restype = None
+        c.wsnark_kzg_srs_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        c.wsnark_fr_poly_eval.argtypes = [vp, u64, u64, vp, vp]
+        c.wsnark_fr_poly_divide.argtypes = [vp, u64, vp, vp, vp]
+        c.wsnark_fr_poly_divide_dev.argtypes = [vp, u64, vp, vp, vp, vp]
+        c.wsnark_kzg_commit.argtypes = [vp, vp, u64, u64, C.c_int, vp]
+        c.wsnark_kzg_commit_dev.argtypes = [vp, vp, u64, u64, C.c_int, vp, vp]
+        c.wsnark_kzg_open.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp]
+        c.wsnark_kzg_open_dev.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, vp]
+        c.wsnark_kzg_verify.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(C.c_int)]
         c.wsnark_group_create.argtypes = [C.POINTER(C.c_int), u32, C.POINTER(vp)]
         c.wsnark_group_free.argtypes = [vp]
         c.wsnark_group_free.restype = None

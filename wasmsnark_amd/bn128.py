@@ -712,6 +712,87 @@ class ResidentPoints:
             pass
 
 
+def _scalar32(v, name):
+    """A scalar argument as 32 plain little-endian bytes: an int (any value below 2^256) or 32 bytes."""
+    if isinstance(v, int):
+        return v.to_bytes(32, "little")
+    b = bytes(v)
+    if len(b) != 32:
+        raise ValueError("%s: expected an int or 32 bytes" % name)
+    return b
+
+
+def _polys(polys):
+    """(bytes, len, count) of one polynomial (bytes) or of several of one length (a list of bytes), stored back to back"""
+    if isinstance(polys, (bytes, bytearray, memoryview)):
+        polys = [polys]
+    polys = [bytes(p) for p in polys]
+    if not polys or len(polys[0]) % 32 or any(len(p) != len(polys[0]) for p in polys):
+        raise ValueError("polynomials: whole 32-byte coefficients, all of one length")
+    return b"".join(polys), len(polys[0]) // 32, len(polys)
+
+
+class KzgSrs:
+    """The tau_g1 powers of a transcript resident as a KZG reference string (wsnark_kzg_srs_load): commitments and openings of
+    polynomials given as 32-byte plain little-endian coefficients, lowest degree first.  One polynomial (bytes) gives one result, a list
+    gives a list."""
+
+    def __init__(self, lib, tau_g1):
+        self._lib = lib
+        b, nbytes = _ro(tau_g1)
+        if nbytes % 64:
+            raise ValueError("tau_g1: not a whole number of 64-byte points")
+        self.n = nbytes // 64
+        self._h = C.c_void_p()
+        lib.check(lib.c.wsnark_kzg_srs_load(b, self.n, C.byref(self._h)))
+
+    def info(self):
+        n, nb = C.c_uint64(), C.c_uint64()
+        self._lib.check(self._lib.c.wsnark_kzg_srs_info(self._h, C.byref(n), C.byref(nb)))
+        return {"n": n.value, "bytes": nb.value}
+
+    def commit(self, polys, form=0):
+        """form 0: coefficients; form 1: evaluations on the domain of Bn128.fft (a power-of-two length)"""
+        blob, ln, count = _polys(polys)
+        out = (C.c_uint8 * (64 * count))()
+        self._lib.check(self._lib.c.wsnark_kzg_commit(self._h, blob, ln, count, int(form), out))
+        out = bytes(out)
+        return out if isinstance(polys, (bytes, bytearray, memoryview)) else [out[64 * i:64 * i + 64] for i in range(count)]
+
+    def commit_dev(self, d_polys, length, count=1, form=0, stream=None):
+        out = (C.c_uint8 * (64 * count))()
+        self._lib.check(self._lib.c.wsnark_kzg_commit_dev(self._h, d_polys, length, count, int(form), out, stream))
+        return [bytes(out)[64 * i:64 * i + 64] for i in range(count)]
+
+    def open(self, polys, z, gamma=None):
+        """(ys, proof): y_i = f_i(z) for every polynomial and ONE proof for sum_i gamma^i f_i (gamma: the caller's challenge; not
+        needed for one polynomial)"""
+        blob, ln, count = _polys(polys)
+        return self._open(self._lib.c.wsnark_kzg_open, blob, ln, count, z, gamma, ())
+
+    def open_dev(self, d_polys, length, count, z, gamma=None, stream=None):
+        return self._open(self._lib.c.wsnark_kzg_open_dev, d_polys, length, count, z, gamma, (stream,))
+
+    def _open(self, fn, polys, ln, count, z, gamma, tail):
+        if count > 1 and gamma is None:
+            raise ValueError("open: several polynomials need the challenge gamma")
+        ys, proof = (C.c_uint8 * (32 * count))(), (C.c_uint8 * 64)()
+        self._lib.check(fn(self._h, polys, ln, count, _scalar32(z, "z"), None if gamma is None else _scalar32(gamma, "gamma"), ys, proof, *tail))
+        ys = bytes(ys)
+        return [ys[32 * i:32 * i + 32] for i in range(count)], bytes(proof)
+
+    def free(self):
+        if self._h:
+            self._lib.c.wsnark_kzg_srs_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def _out_bytes(n):
     """(a new bytes object of n bytes for the library to FILL, its address).  PyBytes_FromStringAndSize(NULL, n) is the C API's own way
     to make a bytes object whose contents the caller writes before anybody else sees it: a key of half a gigabyte then costs neither
@@ -1123,6 +1204,41 @@ class Bn128:
         self.lib.check(self.lib.c.wsnark_selftest_msm_accumulate(g, p, np_ // sz, v, nv, t, nt, out))
         o = bytes(out)
         return [o[i * osz:(i + 1) * osz] for i in range(nt)]
+
+    # --- KZG on a transcript's tau_g1 powers (csrc/kzg.hip; no reference counterpart) ---
+    def load_srs(self, tau_g1):
+        """tau_g1: tau^k g1, k < n, 64-byte points (a transcript's array or a prefix of it) -> KzgSrs"""
+        return KzgSrs(self.lib, tau_g1)
+
+    def kzg_verify(self, g1, g2_pair, commitments, z, ys, proof, gamma=None):
+        """e(C - y g1 + z pi, g2) == e(pi, tau g2) for C = sum gamma^i C_i, y = sum gamma^i y_i.  g2_pair: g2 | tau g2 (256 bytes);
+        commitments, ys: bytes or lists of 64- / 32-byte items.  Host only."""
+        cs = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(commitments)
+        yb = ys if isinstance(ys, (bytes, bytearray)) else b"".join(ys)
+        count = len(cs) // 64
+        if len(cs) % 64 or len(yb) != 32 * count or len(g1) != 64 or len(g2_pair) != 256 or len(proof) != 64:
+            raise ValueError("kzg_verify: 64-byte G1 points, a 256-byte G2 pair, one 32-byte y per commitment")
+        if count > 1 and gamma is None:
+            raise ValueError("kzg_verify: several commitments need the challenge gamma")
+        valid = C.c_int(-1)
+        self.lib.check(self.lib.c.wsnark_kzg_verify(bytes(g1), bytes(g2_pair), bytes(cs), count, _scalar32(z, "z"),
+                                                    None if gamma is None else _scalar32(gamma, "gamma"), bytes(yb), bytes(proof), C.byref(valid)))
+        return valid.value == 1
+
+    def poly_eval(self, polys, z):
+        """[f_i(z)] as 32-byte plain values (one value for one polynomial given as bytes)"""
+        blob, ln, count = _polys(polys)
+        out = (C.c_uint8 * (32 * count))()
+        self.lib.check(self.lib.c.wsnark_fr_poly_eval(blob, ln, count, _scalar32(z, "z"), out))
+        out = bytes(out)
+        return out if isinstance(polys, (bytes, bytearray, memoryview)) else [out[32 * i:32 * i + 32] for i in range(count)]
+
+    def poly_divide(self, poly, z):
+        """(q, y): q = (f - f(z)) / (X - z), len - 1 coefficients, and y = f(z)"""
+        blob, ln, _ = _polys(poly)
+        q, y = (C.c_uint8 * max(32 * (ln - 1), 1))(), (C.c_uint8 * 32)()
+        self.lib.check(self.lib.c.wsnark_fr_poly_divide(blob, ln, _scalar32(z, "z"), q, y))
+        return bytes(q)[:32 * (ln - 1)], bytes(y)
 
     def load_points(self, g, points):
         """Make a point set resident as fixed-base tables (no reference counterpart): see ResidentPoints."""

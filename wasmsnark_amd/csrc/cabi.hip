@@ -479,6 +479,65 @@ int wsnark_powers_check(const wsnark_powers_t* powers, uint32_t flags, const voi
     REQUIRE_CTX();
     return powers_check(powers, flags, (const uint8_t*)seed32, rep);
 }
+// ---- KZG commitments on powers of tau (kzg.hip).  Before wsnark_init no handle can exist: that is said first ----
+#define REQUIRE_SRS_CTX(h)                                                   \
+    if (!ctx()) { set_last_error("wsnark_init() has not been called"); return WSNARK_ERR_NOINIT; } \
+    if (!(h)) return WSNARK_ERR_ARG;                                         \
+    CtxScope _srs_scope(kzg_context(reinterpret_cast<const KzgSrs*>(h)))
+int wsnark_kzg_srs_load(const void* tau_g1, uint64_t n, wsnark_kzg_srs_t** out_handle) {
+    REQUIRE_CTX();
+    KzgSrs* S = nullptr;
+    int rc = kzg_srs_load(tau_g1, n, out_handle ? &S : nullptr);
+    if (rc) return rc;
+    *out_handle = reinterpret_cast<wsnark_kzg_srs_t*>(S);
+    return WSNARK_OK;
+}
+void wsnark_kzg_srs_free(wsnark_kzg_srs_t* h) {
+    if (!h) return;
+    CtxScope scope(kzg_context(reinterpret_cast<const KzgSrs*>(h)));
+    kzg_srs_free(reinterpret_cast<KzgSrs*>(h));
+}
+int wsnark_kzg_srs_info(const wsnark_kzg_srs_t* h, uint64_t* n, uint64_t* bytes) {
+    if (!h) return WSNARK_ERR_ARG;
+    kzg_srs_info(reinterpret_cast<const KzgSrs*>(h), n, bytes);
+    return WSNARK_OK;
+}
+int wsnark_fr_poly_eval(const void* polys, uint64_t len, uint64_t count, const void* z32, void* out_y) {
+    REQUIRE_CTX();
+    return fr_poly_eval(polys, len, count, (const uint8_t*)z32, out_y);
+}
+int wsnark_fr_poly_divide(const void* poly, uint64_t len, const void* z32, void* out_q, void* out_y32) {
+    REQUIRE_CTX();
+    return fr_poly_divide(poly, len, (const uint8_t*)z32, out_q, out_y32, false, nullptr);
+}
+int wsnark_fr_poly_divide_dev(const void* d_poly, uint64_t len, const void* z32, void* d_q, void* out_y32_host, void* stream) {
+    REQUIRE_CTX();
+    return fr_poly_divide(d_poly, len, (const uint8_t*)z32, d_q, out_y32_host, true, (hipStream_t)stream);
+}
+int wsnark_kzg_commit(wsnark_kzg_srs_t* h, const void* polys, uint64_t len, uint64_t count, int form, void* out_commitments) {
+    REQUIRE_SRS_CTX(h);
+    return kzg_commit(reinterpret_cast<KzgSrs*>(h), polys, len, count, form, false, out_commitments, nullptr);
+}
+int wsnark_kzg_commit_dev(wsnark_kzg_srs_t* h, const void* d_polys, uint64_t len, uint64_t count, int form, void* out_commitments_host, void* stream) {
+    REQUIRE_SRS_CTX(h);
+    return kzg_commit(reinterpret_cast<KzgSrs*>(h), d_polys, len, count, form, true, out_commitments_host, (hipStream_t)stream);
+}
+int wsnark_kzg_open(wsnark_kzg_srs_t* h, const void* polys, uint64_t len, uint64_t count, const void* z32, const void* gamma32, void* out_y,
+                    void* out_proof64) {
+    REQUIRE_SRS_CTX(h);
+    return kzg_open(reinterpret_cast<KzgSrs*>(h), polys, len, count, (const uint8_t*)z32, (const uint8_t*)gamma32, false, out_y, out_proof64, nullptr);
+}
+int wsnark_kzg_open_dev(wsnark_kzg_srs_t* h, const void* d_polys, uint64_t len, uint64_t count, const void* z32, const void* gamma32,
+                        void* out_y_host, void* out_proof64_host, void* stream) {
+    REQUIRE_SRS_CTX(h);
+    return kzg_open(reinterpret_cast<KzgSrs*>(h), d_polys, len, count, (const uint8_t*)z32, (const uint8_t*)gamma32, true, out_y_host,
+                    out_proof64_host, (hipStream_t)stream);
+}
+int wsnark_kzg_verify(const void* g1_64, const void* g2_tau_g2_256, const void* commitments, uint64_t count, const void* z32, const void* gamma32,
+                      const void* ys, const void* proof64, int* valid) {
+    return kzg_verify((const uint8_t*)g1_64, (const uint8_t*)g2_tau_g2_256, (const uint8_t*)commitments, count, (const uint8_t*)z32,
+                      (const uint8_t*)gamma32, (const uint8_t*)ys, (const uint8_t*)proof64, valid);
+}
 int wsnark_pkey_delta_verify(const void* old_pkey, size_t old_len, const void* new_pkey, size_t new_len, const void* seed32,
                              wsnark_pkey_delta_verdict_t* out) {
     REQUIRE_CTX();

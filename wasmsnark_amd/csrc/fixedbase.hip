@@ -126,19 +126,24 @@ int points_msm(ResidentPoints* H, const void* scalars, bool on_device, uint64_t 
         if ((rc = upload_staged(L->host_in[0].p, scalars, (size_t)n * 32, s))) return rc;
         d_sc = L->host_in[0].as<Fe>();
     }
-    msm_select_plan(*L, 0);
-    if ((rc = msm_plan_dev(*L, d_sc, n, WindowShard{}, s, H->table_c))) return rc;
+    return points_msm_lane(*L, H, d_sc, n, out, s);
+}
+int points_msm_lane(Lane& L, ResidentPoints* H, const Fe* d_scalars, uint64_t len, void* out, hipStream_t s) {
+    if (len == 0 || len > H->n) return WS_ERR_SIZE;
+    int rc;
+    msm_select_plan(L, 0);
+    if ((rc = msm_plan_dev(L, d_scalars, len, WindowShard{}, s, len == H->n ? H->table_c : 0))) return rc;
     int slot = -1;
     if (H->which == 0) {
-        if ((rc = msm_g1_launch(*L, H->table.as<Affine<Fq>>(), true, &slot, s))) return rc;
+        if ((rc = msm_g1_launch(L, H->table.as<Affine<Fq>>(), true, &slot, s))) return rc;
         XYZZ<Fq> r;
-        if ((rc = msm_g1_finish(*L, slot, &r))) return rc;
+        if ((rc = msm_g1_finish(L, slot, &r))) return rc;
         const Jac<Fq> j = G1::to_affine_jac(r);
         memcpy(out, &j, sizeof j);
     } else {
-        if ((rc = msm_g2_launch(*L, H->table.as<Affine<Fq2>>(), true, &slot, s))) return rc;
+        if ((rc = msm_g2_launch(L, H->table.as<Affine<Fq2>>(), true, &slot, s))) return rc;
         XYZZ<Fq2> r;
-        if ((rc = msm_g2_finish(*L, slot, &r))) return rc;
+        if ((rc = msm_g2_finish(L, slot, &r))) return rc;
         const Jac<Fq2> j = G2::to_affine_jac(r);
         memcpy(out, &j, sizeof j);
     }

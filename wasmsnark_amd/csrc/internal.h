@@ -89,6 +89,7 @@ struct Lane {
     DevBuf witness, h;                          // per-proof device buffers (grow-only)
     DevBuf batch_ws;                            // batch proving (provebatch.hip): index lists, partial sums, window sums of a chunk (grow-only)
     DevBuf verify_ws;                           // batch verification (pairing.hip): key tables, per-proof points, Miller values (grow-only)
+    DevBuf kzg_ws;                              // KZG (kzg.hip): folded polynomial, quotient, tile values and carries of the division (grow-only)
     hipEvent_t ev_start = nullptr, ev_tail = nullptr, ev_h = nullptr;   // cross-queue ordering of one proof
     hipEvent_t ev_plan = nullptr, ev_g2 = nullptr;                      // ... witness plan ready / G2 sum enqueued (third queue); ev_tail: the tail levels given to the third queue
 };
@@ -473,8 +474,27 @@ int points_load(int which, const void* h_points, uint64_t n, ResidentPoints** ou
 void points_free(ResidentPoints* H);
 void points_info(const ResidentPoints* H, int* which, uint64_t* n, uint32_t* table_c, uint32_t* rows, uint64_t* bytes);
 int points_msm(ResidentPoints* H, const void* scalars, bool on_device, uint64_t n, void* out, hipStream_t s);
+// the same sum on a lane the caller holds, over the FIRST len points of the set and len device-resident scalars: len == n goes through
+// the window tables, a shorter prefix through a per-window plan over row 0 of the table (the points themselves)
+int points_msm_lane(Lane& L, ResidentPoints* H, const Fe* d_scalars, uint64_t len, void* out, hipStream_t s);
 int g1_mul_base_batch(const void* base, const void* scalars, uint64_t n, void* out);
 int g2_mul_base_batch(const void* base, const void* scalars, uint64_t n, void* out);
+
+// ---- KZG commitments on powers of tau (kzg.hip; include/wsnark.h has the contracts) ----
+struct KzgSrs;
+Context* kzg_context(const KzgSrs* S);
+int kzg_srs_load(const void* tau_g1, uint64_t n, KzgSrs** out);
+void kzg_srs_free(KzgSrs* S);
+void kzg_srs_info(const KzgSrs* S, uint64_t* n, uint64_t* bytes);
+// y[i] = f_i(z) for count polynomials of len coefficients each, on the host
+int fr_poly_eval(const void* polys, uint64_t len, uint64_t count, const uint8_t* z32, void* out_y);
+// q = (f - f(z)) / (X - z), y = f(z); poly and q on the host or (on_device) resident, y always to the host
+int fr_poly_divide(const void* poly, uint64_t len, const uint8_t* z32, void* q, void* out_y32, bool on_device, hipStream_t s);
+int kzg_commit(KzgSrs* S, const void* polys, uint64_t len, uint64_t count, int form, bool on_device, void* out_commitments, hipStream_t s);
+int kzg_open(KzgSrs* S, const void* polys, uint64_t len, uint64_t count, const uint8_t* z32, const uint8_t* gamma32, bool on_device, void* out_y,
+             void* out_proof64, hipStream_t s);
+int kzg_verify(const uint8_t* g1_64, const uint8_t* g2_pair256, const uint8_t* commitments, uint64_t count, const uint8_t* z32,
+               const uint8_t* gamma32, const uint8_t* ys, const uint8_t* proof64, int* valid);      // host only
 
 // ---- device self-tests and peak probes (selftest.hip) ----
 int selftest_field(int which, int impl, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n);

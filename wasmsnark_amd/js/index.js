@@ -300,6 +300,35 @@ class Bn128 {
      * fixed-base window tables -- later g1_multiexp / g2_multiexp calls that pass the handle instead of the bytes pay neither the
      * points' upload nor the per-window plans (about half the time of a 2^20 sum).  group: 1 or 2. */
     loadPoints(group, points) { return addon.loadPoints(group, points); }
+    /* No counterpart in the reference: KZG commitments on a transcript's tauG1 powers (include/wsnark.h: wsnark_kzg_*).  Scalars --
+     * coefficients, z, gamma, values -- are 32 bytes plain little-endian, reduced mod r; a polynomial is len coefficients, lowest degree
+     * first, count of them back to back; points are 64-byte affine Montgomery points, infinity is zero bytes.
+     * kzgLoadSrs(tauG1) resolves to a handle (freed by the GC); a bad power or one at infinity rejects with the first index.
+     * kzgCommit(srs, polys, len, opts): opts.form === 1 takes evaluations on the domain of fft(); resolves to count x 64 bytes.
+     * kzgOpen(srs, polys, len, z, gamma): {ys: count x 32 bytes, proof: 64 bytes}, ONE proof for sum_i gamma^i f_i; gamma (the caller's
+     * Fiat-Shamir challenge) may be left out for one polynomial.
+     * kzgVerify(g1, g2Pair (g2 | tau g2), commitments, z, ys, proof, gamma): boolean, on the host.
+     * polyEval(polys, len, z): count x 32 bytes.  polyDivide(poly, z): {q: (f - f(z)) / (X - z), y: f(z)}. */
+    _kzgReady() {
+        if (!this._live) throw new Error("wsnark: this Bn128 object has been terminated");
+        if (this._group) throw new Error("wsnark: the KZG calls run on a single GPU (build a Bn128 without {devices})");
+    }
+    async kzgLoadSrs(tauG1) { this._kzgReady(); asBytes(tauG1); return addon.kzgLoadSrs(tauG1); }
+    async kzgCommit(srs, polys, len, opts) { this._kzgReady(); asBytes(polys); return addon.kzgCommit(srs, polys, len, opts && opts.form === 1 ? 1 : 0); }
+    async kzgOpen(srs, polys, len, z, gamma) {
+        this._kzgReady();
+        asBytes(polys);
+        const ab = await addon.kzgOpen(srs, polys, len, z, gamma || null);
+        return { ys: ab.slice(0, ab.byteLength - 64), proof: ab.slice(ab.byteLength - 64) };
+    }
+    async kzgVerify(g1, g2Pair, commitments, z, ys, proof, gamma) { return addon.kzgVerify(g1, g2Pair, commitments, z, gamma || null, ys, proof); }
+    async polyEval(polys, len, z) { this._kzgReady(); asBytes(polys); return addon.polyEval(polys, len, z); }
+    async polyDivide(poly, z) {
+        this._kzgReady();
+        asBytes(poly);
+        const ab = await addon.polyDivide(poly, z);
+        return { q: ab.slice(0, ab.byteLength - 32), y: ab.slice(ab.byteLength - 32) };
+    }
     calcH(signals, polsA, polsB, nSignals, domainSize) { return addon.calcH(signals, polsA, polsB, nSignals, domainSize); }
     fft(buf, odd) { return addon.fft(buf, odd | 0, false); }
     ifft(buf, odd) { return addon.fft(buf, odd | 0, true); }

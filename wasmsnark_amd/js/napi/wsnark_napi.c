@@ -24,6 +24,7 @@ typedef struct wsnark_points wsnark_points_t;
 typedef struct wsnark_group wsnark_group_t;
 typedef struct wsnark_group_pkey wsnark_group_pkey_t;
 typedef struct wsnark_circuit_res wsnark_circuit_res_t;
+typedef struct wsnark_kzg_srs wsnark_kzg_srs_t;
 static struct {
     void* h;
     int (*init)(int);
@@ -115,6 +116,14 @@ static struct {
     int (*proof_compress)(const void*, uint64_t, int, void*, uint8_t*);
     int (*proof_decompress)(const void*, uint64_t, int, void*, uint8_t*);
     int (*verify_batch_compressed)(const void*, size_t, const void*, uint64_t, const void*, uint64_t, int, uint8_t*);
+    /* KZG on powers of tau (include/wsnark.h: wsnark_kzg_*, wsnark_fr_poly_eval, wsnark_fr_poly_divide) */
+    int (*kzg_srs_load)(const void*, uint64_t, wsnark_kzg_srs_t**);
+    void (*kzg_srs_free)(wsnark_kzg_srs_t*);
+    int (*kzg_commit)(wsnark_kzg_srs_t*, const void*, uint64_t, uint64_t, int, void*);
+    int (*kzg_open)(wsnark_kzg_srs_t*, const void*, uint64_t, uint64_t, const void*, const void*, void*, void*);
+    int (*kzg_verify)(const void*, const void*, const void*, uint64_t, const void*, const void*, const void*, const void*, int*);
+    int (*poly_eval)(const void*, uint64_t, uint64_t, const void*, void*);
+    int (*poly_divide)(const void*, uint64_t, const void*, void*, void*);
     char dir[4096];
 } L;
 
@@ -171,6 +180,8 @@ static int load_lib(char* err, size_t errlen) {
     SYM(verify_batch_compressed, "wsnark_groth16_verify_batch_compressed")
     SYM(zkey_info, "wsnark_zkey_info") SYM(zkey_import, "wsnark_zkey_import") SYM(zkey_export, "wsnark_zkey_export") SYM(zkey_export_size, "wsnark_zkey_export_size")
     SYM(pkey_load_zkey, "wsnark_pkey_load_zkey") SYM(pkey_load_zkey_file, "wsnark_pkey_load_zkey_file") SYM(zkey_vk_len, "wsnark_zkey_vk_len") SYM(zkey_vk_len_file, "wsnark_zkey_vk_len_file")
+    SYM(kzg_srs_load, "wsnark_kzg_srs_load") SYM(kzg_srs_free, "wsnark_kzg_srs_free") SYM(kzg_commit, "wsnark_kzg_commit") SYM(kzg_open, "wsnark_kzg_open")
+    SYM(kzg_verify, "wsnark_kzg_verify") SYM(poly_eval, "wsnark_fr_poly_eval") SYM(poly_divide, "wsnark_fr_poly_divide")
 #undef SYM
     return 0;
 }
@@ -201,7 +212,8 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
        OP_LOADKEY_FILE, OP_LOADKEY_ZKEY, OP_LOADKEY_ZKEY_FILE, OP_GROUP_LOADKEY_FILE, OP_VERIFY_BATCH, OP_CHECK_KEY, OP_CONTRIBUTE, OP_DELTA_VERIFY, OP_GROUP_NTT, OP_NEW_KEY,
        OP_MUL_POINTS, OP_POWERS_CONTRIBUTE, OP_POWERS_CHECK, OP_CHECK_KEY_CIRCUIT, OP_CIRCUIT_LOAD, OP_WITNESS_CHECK,
        OP_CIRCUIT_WITNESS_CHECK, OP_PROVE_BATCH, OP_CIRCUIT_WITNESS_CHECK_BATCH, OP_CIRCUIT_FROM_ROWS, OP_CIRCUIT_LOAD_ROWS, OP_ZKEY_IMPORT, OP_ZKEY_EXPORT,
-       OP_CODEC_POINTS, OP_CODEC_PROOFS, OP_VERIFY_BATCH_COMPRESSED };
+       OP_CODEC_POINTS, OP_CODEC_PROOFS, OP_VERIFY_BATCH_COMPRESSED,
+       OP_KZG_LOAD, OP_KZG_COMMIT, OP_KZG_OPEN, OP_KZG_VERIFY, OP_POLY_EVAL, OP_POLY_DIVIDE };
 /* A group and the keys loaded on it.  The JS side holds them as externals; a key's finalizer must not touch a group that
  * terminate() has already freed (wsnark_group_free frees the keys that are left), so every group handle carries a `live` flag
  * that outlives the group itself and every key handle points at its group's handle. */
@@ -217,6 +229,7 @@ enum { OP_G1, OP_G2, OP_NTT, OP_CALCH, OP_PROVE, OP_LOADKEY, OP_VERIFY, OP_HASH,
 #define TAG_GROUP 0x77736e4752503031ull
 #define TAG_GKEY 0x77736e474b593031ull
 #define TAG_CIRCUIT 0x77736e4349523031ull
+#define TAG_SRS 0x77736e5352533031ull
 typedef struct { uint64_t tag; void* p; } handle_t;                 /* a key (wsnark_pkey_t*), a point set (wsnark_points_t*) or a resident circuit */
 typedef struct { uint64_t tag; wsnark_group_t* g; int live; int inflight; int refs; } group_ref_t;
 typedef struct { uint64_t tag; wsnark_group_pkey_t* k; group_ref_t* gr; } gkey_ref_t;
@@ -265,6 +278,7 @@ typedef struct {
     gkey_ref_t* gk;
     group_ref_t* gr_used;       /* the group this job runs on (counted in its `inflight`), or NULL */
     wsnark_points_t* pts;
+    wsnark_kzg_srs_t* srs;       /* OP_KZG_LOAD: the new handle; OP_KZG_COMMIT, OP_KZG_OPEN: the one summed over */
     wsnark_circuit_res_t* circ;  /* OP_CIRCUIT_LOAD: the new handle; OP_CIRCUIT_WITNESS_CHECK: the one checked against */
     uint64_t cap;               /* the witness checks: entries the two lists hold */
     uint8_t* out;
@@ -562,6 +576,19 @@ static void job_execute(napi_env env, void* data) {
         if (!j->rc) j->rc = L.group_last_blinding(j->gk->gr->g, j->out + 384, j->out + 416);
         break;
     case OP_GROUP_WAIT_TABLES: j->rc = L.group_pkey_wait_tables(j->gk->k); break;
+    /* KZG: u0 = len (coefficients per polynomial), na = count x len x 32; r32 = z, s32 = gamma or NULL */
+    case OP_KZG_LOAD: j->rc = L.kzg_srs_load(j->a, j->na / 64, &j->srs); break;
+    case OP_KZG_COMMIT: j->rc = L.kzg_commit(j->srs, j->a, j->u0, j->na / 32 / j->u0, j->i0, j->out); break;
+    case OP_KZG_OPEN: {      /* out = count values | the proof */
+        const uint64_t count = j->na / 32 / j->u0;
+        j->rc = L.kzg_open(j->srs, j->a, j->u0, count, j->r32, j->s32, j->out, j->out + 32 * count);
+        break;
+    }
+    case OP_KZG_VERIFY:      /* in: g1, g2 | tau g2, commitments, ys, proof */
+        j->rc = L.kzg_verify(j->in[0], j->in[1], j->in[2], j->nin[2] / 64, j->r32, j->s32, j->in[3], j->in[4], &j->i0);
+        break;
+    case OP_POLY_EVAL: j->rc = L.poly_eval(j->a, j->u0, j->na / 32 / j->u0, j->r32, j->out); break;
+    case OP_POLY_DIVIDE: j->rc = L.poly_divide(j->a, j->na / 32, j->r32, j->out, j->out + j->na - 32); break;      /* out = q | y */
     case OP_POINTS_LOAD: j->rc = L.points_load(j->i0, j->a, j->na / (j->i0 == 2 ? 128 : 64), &j->pts); break;
     case OP_POINTS_MSM: j->rc = L.points_msm(j->pts, j->a, j->na / 32, j->out); break;
     case OP_HASH:
@@ -601,6 +628,11 @@ static void circuit_finalize(napi_env env, void* data, void* hint) {
     (void)env; (void)hint;
     handle_t* h = (handle_t*)data;
     if (h) { if (h->p) L.circuit_free((wsnark_circuit_res_t*)h->p); h->tag = 0; free(h); }
+}
+static void srs_finalize(napi_env env, void* data, void* hint) {
+    (void)env; (void)hint;
+    handle_t* h = (handle_t*)data;
+    if (h) { if (h->p) L.kzg_srs_free((wsnark_kzg_srs_t*)h->p); h->tag = 0; free(h); }
 }
 static void gkey_finalize(napi_env env, void* data, void* hint) {
     (void)env; (void)hint;
@@ -646,7 +678,19 @@ static void job_complete(napi_env env, napi_status status, void* data) {
         } else {
             napi_resolve_deferred(env, j->deferred, res);
         }
-    } else if (j->op == OP_VERIFY) {
+    } else if (j->op == OP_KZG_LOAD) {
+        handle_t* h = new_handle(TAG_SRS, j->srs);
+        if (!h || napi_create_external(env, h, srs_finalize, NULL, &res) != napi_ok) {      /* nothing would ever free the tables */
+            napi_value msg, e;
+            L.kzg_srs_free(j->srs);
+            free(h);
+            napi_create_string_utf8(env, "wsnark_napi: out of memory for the reference string's handle", NAPI_AUTO_LENGTH, &msg);
+            napi_create_error(env, NULL, msg, &e);
+            napi_reject_deferred(env, j->deferred, e);
+        } else {
+            napi_resolve_deferred(env, j->deferred, res);
+        }
+    } else if (j->op == OP_VERIFY || j->op == OP_KZG_VERIFY) {
         napi_get_boolean(env, j->i0 != 0, &res);
         napi_resolve_deferred(env, j->deferred, res);
     } else if (j->op == OP_LOADKEY || j->op == OP_LOADKEY_FILE) {
@@ -1458,6 +1502,102 @@ static napi_value js_points_msm(napi_env env, napi_callback_info info) {
     return start_job(env, j, "wsnark_points_msm");
 }
 
+/* ---- KZG on powers of tau ----
+ * a 32-byte scalar argument; null / undefined where the call allows it */
+static int get_scalar32(napi_env env, napi_value v, int optional, uint8_t** p) {
+    napi_valuetype t;
+    size_t n = 0;
+    *p = NULL;
+    if (optional && napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined)) return 1;
+    return get_bytes(env, v, p, &n) && n == 32;
+}
+/* kzgLoadSrs(tauG1) -> Promise<handle> */
+static napi_value js_kzg_load(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_KZG_LOAD;
+    if (argc < 1 || !get_bytes(env, argv[0], &j->a, &j->na) || j->na == 0 || j->na % 64) FAIL(env, j, "expected (a whole number of 64-byte G1 points)");
+    keep(env, j, argv[0]);
+    return start_job(env, j, "wsnark_kzg_srs_load");
+}
+/* (polys, len) of kzgCommit / kzgOpen / polyEval: count x len coefficients of 32 bytes */
+static int get_polys(napi_env env, napi_value polys, napi_value len, job_t* j) {
+    return get_bytes(env, polys, &j->a, &j->na) && napi_get_value_uint32(env, len, &j->u0) == napi_ok && j->u0 != 0 && j->na != 0 &&
+           j->na % ((size_t)32 * j->u0) == 0;
+}
+/* kzgCommit(handle, polys, len, form 0 | 1) -> Promise<ArrayBuffer count x 64> */
+static napi_value js_kzg_commit(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_KZG_COMMIT;
+    if (argc < 4 || !(j->srs = (wsnark_kzg_srs_t*)get_plain(env, argv[0], TAG_SRS)) || !get_polys(env, argv[1], argv[2], j) ||
+        napi_get_value_int32(env, argv[3], &j->i0) != napi_ok)
+        FAIL(env, j, "expected (reference string handle, count x len 32-byte coefficients, len, form 0 | 1)");
+    j->nout = j->na / 32 / j->u0 * 64; j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[0]); keep(env, j, argv[1]);
+    return start_job(env, j, "wsnark_kzg_commit");
+}
+/* kzgOpen(handle, polys, len, z32, gamma32 | null) -> Promise<ArrayBuffer count x 32 values | the 64-byte proof> */
+static napi_value js_kzg_open(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_KZG_OPEN;
+    if (argc < 5 || !(j->srs = (wsnark_kzg_srs_t*)get_plain(env, argv[0], TAG_SRS)) || !get_polys(env, argv[1], argv[2], j) ||
+        !get_scalar32(env, argv[3], 0, &j->r32) || !get_scalar32(env, argv[4], 1, &j->s32) || (!j->s32 && j->na / 32 / j->u0 > 1))
+        FAIL(env, j, "expected (reference string handle, count x len 32-byte coefficients, len, z (32 bytes), gamma (32 bytes; null for one polynomial))");
+    j->nout = j->na / 32 / j->u0 * 32 + 64; j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[0]); keep(env, j, argv[1]); keep(env, j, argv[3]);
+    if (j->s32) keep(env, j, argv[4]);
+    return start_job(env, j, "wsnark_kzg_open");
+}
+/* kzgVerify(g1, g2 | tau g2, commitments, z32, gamma32 | null, ys, proof) -> Promise<boolean>; host only */
+static napi_value js_kzg_verify(napi_env env, napi_callback_info info) {
+    size_t argc = 7; napi_value argv[7];
+    static const int at[5] = {0, 1, 2, 5, 6};
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_KZG_VERIFY;
+    int ok = argc >= 7;
+    for (int k = 0; ok && k < 5; k++) ok = get_bytes(env, argv[at[k]], &j->in[k], &j->nin[k]);
+    if (!ok || j->nin[0] != 64 || j->nin[1] != 256 || j->nin[2] == 0 || j->nin[2] % 64 || j->nin[3] != j->nin[2] / 2 || j->nin[4] != 64 ||
+        !get_scalar32(env, argv[3], 0, &j->r32) || !get_scalar32(env, argv[4], 1, &j->s32) || (!j->s32 && j->nin[2] > 64))
+        FAIL(env, j, "expected (g1 (64 bytes), g2 | tau g2 (256), count commitments (64 each), z (32), gamma (32; null for one commitment), count values (32 each), proof (64))");
+    for (int k = 0; k < 7; k++)
+        if (k != 4 || j->s32) keep(env, j, argv[k]);
+    return start_job(env, j, "wsnark_kzg_verify");
+}
+/* polyEval(polys, len, z32) -> Promise<ArrayBuffer count x 32> */
+static napi_value js_poly_eval(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_POLY_EVAL;
+    if (argc < 3 || !get_polys(env, argv[0], argv[1], j) || !get_scalar32(env, argv[2], 0, &j->r32))
+        FAIL(env, j, "expected (count x len 32-byte coefficients, len, z (32 bytes))");
+    j->nout = j->na / j->u0; j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[0]); keep(env, j, argv[2]);
+    return start_job(env, j, "wsnark_fr_poly_eval");
+}
+/* polyDivide(poly, z32) -> Promise<ArrayBuffer (len - 1) x 32 quotient | the 32-byte value> */
+static napi_value js_poly_divide(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    job_t* j = (job_t*)calloc(1, sizeof *j);
+    j->op = OP_POLY_DIVIDE;
+    if (argc < 2 || !get_bytes(env, argv[0], &j->a, &j->na) || j->na == 0 || j->na % 32 || !get_scalar32(env, argv[1], 0, &j->r32))
+        FAIL(env, j, "expected (len 32-byte coefficients, z (32 bytes))");
+    j->nout = j->na; j->out = (uint8_t*)calloc(j->nout, 1);
+    if (!j->out) FAIL(env, j, "out of memory");
+    keep(env, j, argv[0]); keep(env, j, argv[1]);
+    return start_job(env, j, "wsnark_fr_poly_divide");
+}
+
 /* ---- several GPUs in this one process ----
  * groupCreate([device, ...]) -> group handle (synchronous: contexts and worker threads are created at once) */
 static napi_value js_group_create(napi_env env, napi_callback_info info) {
@@ -1724,6 +1864,12 @@ static napi_value module_init(napi_env env, napi_value exports) {
         {"circuitCheckWitnesses", NULL, js_circuit_check_witnesses, NULL, NULL, NULL, napi_default, NULL},
         {"checkWitness", NULL, js_check_witness, NULL, NULL, NULL, napi_default, NULL},
         {"proofToObject", NULL, js_proof_to_object, NULL, NULL, NULL, napi_default, NULL},
+        {"kzgLoadSrs", NULL, js_kzg_load, NULL, NULL, NULL, napi_default, NULL},
+        {"kzgCommit", NULL, js_kzg_commit, NULL, NULL, NULL, napi_default, NULL},
+        {"kzgOpen", NULL, js_kzg_open, NULL, NULL, NULL, napi_default, NULL},
+        {"kzgVerify", NULL, js_kzg_verify, NULL, NULL, NULL, napi_default, NULL},
+        {"polyEval", NULL, js_poly_eval, NULL, NULL, NULL, napi_default, NULL},
+        {"polyDivide", NULL, js_poly_divide, NULL, NULL, NULL, napi_default, NULL},
         {"loadPoints", NULL, js_points_load, NULL, NULL, NULL, napi_default, NULL},
         {"pointsMultiexp", NULL, js_points_msm, NULL, NULL, NULL, napi_default, NULL},
         {"groupCreate", NULL, js_group_create, NULL, NULL, NULL, napi_default, NULL},
