@@ -442,6 +442,7 @@ struct Trace {
 struct MsmSums {
     XYZZ<Fq> A, B1, C, H;
     XYZZ<Fq2> B2;
+    bool have_B2 = false;         // B2 is already there when after_ab1 runs (the full-size arrangement finishes it first)
 };
 
 // CALC_H and the five MSMs (src/bn128.js:607-620) on lane L.  With a window shard other than {0, 1} the sums are
@@ -465,7 +466,7 @@ typedef std::function<int(hipStream_t, Fe*)> CalcHFn;
 // callers hand over host memory; the 32 B x nVars of H2D are inside every drop-in call).
 static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard sh, MsmSums* out, hipStream_t s,
                       const std::function<void(const MsmSums&)>& after_ab1 = nullptr, bool skip_h = false, const CalcHFn& calc_h = nullptr,
-                      const uint8_t* h_witness = nullptr, bool one_call = false) {
+                      const uint8_t* h_witness = nullptr, bool one_call = false, const std::function<void()>& on_first_launches = nullptr) {
     Trace tr;
     // a points-sharded key sums its own pairs: the witness slice [lo, lo + n_local) against the resident slice of every
     // section (all windows), h[hlo ..] against its hExps slice
@@ -543,6 +544,9 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
         if ((rc = enqueue_calc_h())) return rc;
         tr.mark("calc_h enqueued");
     }
+    // the GPU has the witness plan and CALC_H to work on: host work that only has to be done some time before the sums come back
+    // (the one-call prover starts its blinding's helper thread here, not in front of the first launch)
+    if (on_first_launches) on_first_launches();
     // one grouping pass for all four; A and B1/B2 may run on variants of the plan that leave out the variables
     // absent from their matrix (plan 0 = full, 2 = without B's absentees, 3 = without A's)
     int planA = 0, planB = 0;
@@ -570,6 +574,8 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
     // 0: off; 1: wherever the third queue exists (the small arrangement too: the batched G1 tail's levels behind B2 on its queue);
     // default: the full-size arrangement only.  Measured (profiles/tail_beside_acc_ab.txt): the levels start at once beside the running
     // accumulation and last several times their time alone; proofs 8.44 -> 8.29 ms at 2^20, 32.27 -> 31.37 ms at 2^22.
+    // (msm_combine_all and msm_chunks stay here.  Moved to the side queue as well, so that this queue goes from one accumulation
+    //  straight into the next, proofs measured 0.10 ms SLOWER: docs/HISTORY.md, "The host's end and start of a proof".)
     const long side_sw = msm_tail_side_switch();
     const bool side = overlap && L.stream3 && s != L.stream3 && s2 != L.stream3 && (side_sw == 1 || (side_sw != 0 && !small));
     hipStream_t s_side = side ? L.stream3 : s;
@@ -657,6 +663,7 @@ static int prove_msms(ProvingKey* K, Lane& L, const Fe* d_witness, WindowShard s
     tr.mark(ch_merged ? "plan(h) + accumulate H + one tail for C + H" : "plan(h) + launch H");
     const bool g2_fin = !small;                      // (small proofs: B2 ends on its own queue, A / B1 / C come first)
     if (g2_fin && (rc = msm_g2_finish(L, hB2, &out->B2))) return rc;
+    out->have_B2 = g2_fin;
     if ((rc = msm_g1_finish(L, hA, &out->A))) return rc;
     if ((rc = msm_g1_finish(L, hB1, &out->B1))) return rc;
     tr.mark(g2_fin ? "finish B2, A, B1" : "finish A, B1");
@@ -698,6 +705,8 @@ struct Blinding {
     Fe rr, ss, rs;                 // r mod r, s mod r, r*s mod r (plain)
     struct Pre { G1::Pt r_delta1, s_delta1, rs_delta1; G2::Pt s_delta2; };
     std::future<Pre> pre;
+    G1::Pt delta1;                 // the key's, for the helper thread (start_blinding_thread)
+    G2::Pt delta2;
     const uint8_t* rb() const { return reinterpret_cast<const uint8_t*>(&rr); }
     const uint8_t* sb() const { return reinterpret_cast<const uint8_t*>(&ss); }
     ~Blinding() { if (pre.valid()) pre.wait(); }
@@ -716,7 +725,8 @@ bool last_blinding(uint8_t* r32, uint8_t* s32) {
     if (s32) memcpy(s32, t_last_rs + 32, 32);
     return true;
 }
-static int start_blinding(ProvingKey* K, const uint8_t* r32, const uint8_t* s32, Blinding* B) {
+static void start_blinding_thread(Blinding* B);
+static int start_blinding(ProvingKey* K, const uint8_t* r32, const uint8_t* s32, Blinding* B, bool start_thread = true) {
     uint8_t rnd[64];
     if (!r32 || !s32) {
         if (os_random(rnd, 64)) { set_last_error("no entropy: getrandom(2) and /dev/urandom both failed"); return WS_ERR_ARG; }
@@ -731,9 +741,18 @@ static int start_blinding(ProvingKey* K, const uint8_t* r32, const uint8_t* s32,
     B->rr = Fr::reduce_full(B->rr);
     B->ss = Fr::reduce_full(B->ss);
     B->rs = Fr::from_mont(Fr::mul(Fr::to_mont(B->rr), Fr::to_mont(B->ss)));
+    B->delta1 = G1::from_affine(K->delta1);
+    B->delta2 = G2::from_affine(K->delta2);
+    if (start_thread) start_blinding_thread(B);
+    return WS_OK;
+}
+// the scalar multiplications that involve key points only, on a helper thread (creating it costs the caller tens of microseconds:
+// the one-call prover does it once the GPU has work)
+static void start_blinding_thread(Blinding* B) {
+    if (B->pre.valid()) return;
     const Fe rr = B->rr, ss = B->ss, rs = B->rs;
-    const G1::Pt delta1 = G1::from_affine(K->delta1);
-    const G2::Pt delta2 = G2::from_affine(K->delta2);
+    const G1::Pt delta1 = B->delta1;
+    const G2::Pt delta2 = B->delta2;
     B->pre = std::async(std::launch::async, [rr, ss, rs, delta1, delta2]() {
         Blinding::Pre p;
         p.r_delta1 = G1::mul_bytes(delta1, reinterpret_cast<const uint8_t*>(&rr), 32);
@@ -742,40 +761,48 @@ static int start_blinding(ProvingKey* K, const uint8_t* r32, const uint8_t* s32,
         p.s_delta2 = G2::mul_bytes(delta2, reinterpret_cast<const uint8_t*>(&ss), 32);
         return p;
     });
-    return WS_OK;
 }
 
 // src/bn128.js:671-718, in two steps: everything that needs only A and B1 (incl. the two 256-bit scalar
 // multiplications of pi_c) can run while the GPU is still busy with B2 and H
-struct EarlyParts { G1::Pt pi_a, s_pi_a, r_pib1; bool done = false; };
-static void prove_assemble_early(ProvingKey* K, const MsmSums& M, Blinding& B, Blinding::Pre& pp, EarlyParts* E) {
+struct EarlyParts { G1::Pt pi_a, s_pi_a, r_pib1; bool done = false, b_done = false; };
+// pi_a's and pi_b's 288 bytes are written where their inputs are known (both under C's accumulation in the full-size arrangement):
+// behind the last sum the host is left with pi_c.  The same operations as ever, in another order.
+static void prove_assemble_early(ProvingKey* K, const MsmSums& M, Blinding& B, Blinding::Pre& pp, EarlyParts* E, uint8_t* out384) {
     const G1::Pt alfa1 = G1::from_affine(K->alfa1), beta1 = G1::from_affine(K->beta1);
+    start_blinding_thread(&B);                                       // (callers that never reached prove_msms' hook)
     pp = B.pre.get();
     // pi_a = sum A + alfa1 + r*delta1                               (:671-673)
     E->pi_a = G1::add(G1::add(alfa1, M.A), pp.r_delta1);
+    // affine + fromMontgomery (:706-712); infinity prints as (0, 1, 0)
+    const Jac<Fq> a = G1::to_affine_jac(E->pi_a);
+    store_plain(out384 + 0, a.x); store_plain(out384 + 32, a.y); store_plain(out384 + 64, a.z);
     // pib1 = sum B1 + beta1 + s*delta1                              (:681-683)
     const G1::Pt pib1 = G1::add(G1::add(beta1, M.B1), pp.s_delta1);
     E->s_pi_a = G1::mul_bytes(E->pi_a, B.sb(), 32);                  // (:692)
     E->r_pib1 = G1::mul_bytes(pib1, B.rb(), 32);                     // (:696)
     E->done = true;
 }
-static void prove_assemble(ProvingKey* K, const MsmSums& M, Blinding& B, Blinding::Pre& pp, EarlyParts& E, uint8_t* out384) {
-    if (!E.done) prove_assemble_early(K, M, B, pp, &E);
+// pi_b, as soon as B2 and the blinding's s*delta2 are there
+static void prove_assemble_b(ProvingKey* K, const MsmSums& M, const Blinding::Pre& pp, EarlyParts* E, uint8_t* out384) {
     const G2::Pt beta2 = G2::from_affine(K->beta2);
     // pi_b = sum B2 + beta2 + s*delta2                              (:676-678)
-    G2::Pt pi_b = G2::add(G2::add(beta2, M.B2), pp.s_delta2);
+    const G2::Pt pi_b = G2::add(G2::add(beta2, M.B2), pp.s_delta2);
+    const Jac<Fq2> b = G2::to_affine_jac(pi_b);
+    store_plain(out384 + 96, b.x.c0); store_plain(out384 + 128, b.x.c1);
+    store_plain(out384 + 160, b.y.c0); store_plain(out384 + 192, b.y.c1);
+    store_plain(out384 + 224, b.z.c0); store_plain(out384 + 256, b.z.c1);
+    E->b_done = true;
+}
+static void prove_assemble(ProvingKey* K, const MsmSums& M, Blinding& B, Blinding::Pre& pp, EarlyParts& E, uint8_t* out384) {
+    if (!E.done) prove_assemble_early(K, M, B, pp, &E, out384);
+    if (!E.b_done) prove_assemble_b(K, M, pp, &E, out384);
     // pi_c = sum C + sum H + s*pi_a + r*pib1 - (r*s)*delta1         (:687-704)
     G1::Pt pi_c = G1::add(M.C, M.H);
     pi_c = G1::add(pi_c, E.s_pi_a);
     pi_c = G1::add(pi_c, E.r_pib1);
     pi_c = G1::add(pi_c, G1::neg(pp.rs_delta1));
-    // affine + fromMontgomery (:706-712); infinity prints as (0, 1, 0)
-    Jac<Fq> a = G1::to_affine_jac(E.pi_a), c = G1::to_affine_jac(pi_c);
-    Jac<Fq2> b = G2::to_affine_jac(pi_b);
-    store_plain(out384 + 0, a.x); store_plain(out384 + 32, a.y); store_plain(out384 + 64, a.z);
-    store_plain(out384 + 96, b.x.c0); store_plain(out384 + 128, b.x.c1);
-    store_plain(out384 + 160, b.y.c0); store_plain(out384 + 192, b.y.c1);
-    store_plain(out384 + 224, b.z.c0); store_plain(out384 + 256, b.z.c1);
+    const Jac<Fq> c = G1::to_affine_jac(pi_c);
     store_plain(out384 + 288, c.x); store_plain(out384 + 320, c.y); store_plain(out384 + 352, c.z);
 }
 
@@ -783,13 +810,18 @@ static void prove_assemble(ProvingKey* K, const MsmSums& M, Blinding& B, Blindin
 static int groth16_prove(ProvingKey* K, Lane& L, const Fe* d_witness, const uint8_t* r32, const uint8_t* s32, uint8_t* out384,
                          hipStream_t s, const uint8_t* h_witness = nullptr) {
     if (!s) s = L.stream;
+    // (nothing but argument checks in front of the first launches: the blinding's values here, its helper thread from the hook)
     Blinding B;
-    int rc = start_blinding(K, r32, s32, &B);
+    int rc = start_blinding(K, r32, s32, &B, false);
     if (rc) return rc;
     MsmSums M;
     Blinding::Pre pp;
     EarlyParts E;
-    if ((rc = prove_msms(K, L, d_witness, WindowShard{}, &M, s, [&](const MsmSums& m) { prove_assemble_early(K, m, B, pp, &E); }, false, nullptr, h_witness, true)))
+    const auto early = [&](const MsmSums& m) {
+        prove_assemble_early(K, m, B, pp, &E, out384);
+        if (m.have_B2) prove_assemble_b(K, m, pp, &E, out384);
+    };
+    if ((rc = prove_msms(K, L, d_witness, WindowShard{}, &M, s, early, false, nullptr, h_witness, true, [&]() { start_blinding_thread(&B); })))
         return rc;
     Trace tr;
     prove_assemble(K, M, B, pp, E, out384);
